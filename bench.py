@@ -4,6 +4,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --workload c4 [--gpus N] [--files 40000]             (BASELINE configs[3], strong scaling)
+    python bench.py --full                  (+ phases, roofline, single_call, secondary records, CPU baseline)
+    python bench.py --dump-outputs DIR      (+ the indices of the last timed step as DIR/indices.npy, float32)
+
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else it can measure or check
+is behind --full.
 
 A "step" is ONE decode (forward recurrence + final argmax + backtrace) of one synthetic batch of 512
 sequences x 500 frames x 1440 states (BASELINE configs[2]) that is already resident in HBM.  Consecutive
@@ -47,8 +52,16 @@ ROUTES = {0: 'generic', 1: 'dense', 3: 'resident', 4: 'rows', 5: 'cluster', 6: '
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=16)
+    ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 16 for c3, every batch of the job for c4)')
     ap.add_argument('--warmup', type=int, default=8)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, measure and check everything else: per-kernel phases and roofline, '
+                         'single_call, the secondary records, the CPU baseline and, under a collective, the per-rank '
+                         'report (each still subject to the --no-* options below); off: set up, warm up, time the steps, '
+                         'print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy '
+                         '(float32)')
     ap.add_argument('--workload', choices=['c3', 'c4'], default='c3',
                     help='c3 = BASELINE configs[2] (headline, weak scaling); c4 = configs[3]: ragged many-file job, '
                          'lengths 100..900, batches of 512 padded to the batch maximum, sharded over the ranks '
@@ -81,7 +94,18 @@ def parse_args(argv=None):
                          '(torbi/evaluate/core.py:24-33); uniform = the reference default (transition=None)')
     ap.add_argument('--half-width', type=float, default=87.2,
                     help='band half width in states for --transition banded (penn: 87.2)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = 16 if args.workload == 'c3' else 0
+    return args
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: each array as <folder>/<name>.npy in float32 (decoded state indices are exact in it)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    for name, tensor in arrays.items():
+        np.save(os.path.join(folder, f'{name}.npy'), tensor.detach().cpu().numpy().astype(np.float32))
 
 
 def self_launch(args):
@@ -341,7 +365,7 @@ class Bench:
                     'config': {'workload': f'{S} states, {T} frames, batch={B} per GPU (no HIP device: launch, '
                                            f'rendezvous and planning only)',
                                'launch_groups': self.balanced_groups(args.steps, args.group)}}
-            if self.collective:
+            if self.collective and args.full:
                 line['multi_gpu'] = self.rank_report(None, None, torch.zeros((B, T), dtype=torch.int32), B)
             return line
         dev = self.dev
@@ -382,13 +406,15 @@ class Bench:
         elapsed = self.max_over_ranks(local_elapsed)
         value = float(B) * T * args.steps * size / elapsed
         last_obs = obs[(self.balanced_groups(args.steps, group)[-1] - 1) % group]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'indices': indices})
 
         result = {
             'metric': METRIC, 'value': value, 'unit': 'timesteps/s', 'n_gpus': size, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
         }
-        if self.collective:
+        if self.collective and args.full:
             def alone(count):                  # the same steps WITHOUT the collective: what this rank does on its own
                 pipe.synchronize()
                 for n in self.balanced_groups(count, group):
@@ -411,9 +437,24 @@ class Bench:
                                   'algorithmic_bytes_per_launch': nbytes}
             return result
 
+        sizes = self.balanced_groups(args.steps, group)
+        result['config'] = {
+            'workload': (f'{S} states, {T} frames, batch={B} per GPU, fp32, dense transition'
+                         f'{" (BASELINE configs[2])" if (B, T, S) == (512, 500, 1440) else ""}; decode = forward + '
+                         f'argmax + backtrace, inputs resident in HBM') if args.transition == 'dense' else
+                        (f'{S} states, {T} frames, batch={B} per GPU, fp32, BANDED transition (half width '
+                         f'{args.half_width}, -inf outside; secondary workload)'),
+            'parallelism': f'batch-sharded x{size}' if size > 1 else 'single GPU',
+            'launch_groups': sizes, 'streams': args.pipeline,
+            'throughput_mode': f'{sum(sizes)} batches decoded as {len(sizes)} launch groups over {args.pipeline} '
+                               f'streams; ONE call on ONE batch is "single_call" (--full)',
+            'transition_preparation': 'reused across launch groups' if args.reuse_preparation
+            else 'rebuilt by every launch group'}
+        if not args.full:
+            return result
+
         # dominant kernel, measured live with hipEvents on the launch stream (include/torbi_hip.h: phase_ms) on a
         # full launch group, averaged over three profiled groups
-        sizes = self.balanced_groups(args.steps, group)
         g = max(sizes)
         spaces = [torch.empty(v.workspace_bytes(B, T, S), dtype=torch.uint8, device=dev) for _ in range(g)]
         prof, fwd_ms, bt_ms, prep_ms = [], 0.0, 0.0, 0.0
@@ -477,18 +518,7 @@ class Bench:
                         'stated here at the measured clock (2.5 issue cycles per vector instruction on average) -- both pipes '
                         'are more than half busy and do not overlap fully: that, not HBM, is what binds this kernel'}
         del spaces
-        result['config'] = {
-            'workload': (f'{S} states, {T} frames, batch={B} per GPU, fp32, dense transition'
-                         f'{" (BASELINE configs[2])" if (B, T, S) == (512, 500, 1440) else ""}; decode = forward + '
-                         f'argmax + backtrace, inputs resident in HBM') if args.transition == 'dense' else
-                        (f'{S} states, {T} frames, batch={B} per GPU, fp32, BANDED transition (half width '
-                         f'{args.half_width}, -inf outside; secondary workload)'),
-            'parallelism': f'batch-sharded x{size}' if size > 1 else 'single GPU',
-            'launch_groups': sizes, 'streams': args.pipeline, 'forward_path': route,
-            'throughput_mode': f'{sum(sizes)} batches decoded as {len(sizes)} launch groups over {args.pipeline} '
-                               f'streams; ONE call on ONE batch is "single_call"',
-            'transition_preparation': 'reused across launch groups' if args.reuse_preparation
-            else 'rebuilt by every launch group'}
+        result['config']['forward_path'] = route
         result['roofline'] = {
             'bound': 'valu_issue+lds' if route in ('resident', 'cluster') else 'valu_issue',
             'bound_note': 'achieved / peak / frac are the HBM figures BASELINE.json asks for (algorithmic bytes per launch '
@@ -950,16 +980,20 @@ class Bench:
         pipe.reserve(args.batch, tmax, S)
 
         def run():
+            last = None
             for observation, frames in batches:
-                pipe.decode(observation, frames, trans, init)
+                last = pipe.decode(observation, frames, trans, init)
             pipe.synchronize()
+            return last
 
         run()                                   # warm-up pass over the same batches
         self.fence(pipe)
         t0 = time.perf_counter()
-        run()
+        last = run()
         self.fence(pipe)
         elapsed = self.max_over_ranks(time.perf_counter() - t0)
+        if not quiet and args.dump_outputs and self.rank == 0 and last is not None:
+            dump_outputs(args.dump_outputs, {'indices': last})
         total_valid = self.sum_over_ranks(valid)
         total_padded = self.sum_over_ranks(padded)
         record = {'value': total_valid / elapsed, 'unit': 'timesteps/s', 'seconds': elapsed,
@@ -1048,7 +1082,7 @@ class Bench:
 
     def run_c4(self):
         args = self.args
-        record = self.c4_decode_only(args.files, args.steps if args.steps != 16 else 0)
+        record = self.c4_decode_only(args.files, args.steps)
         result = {'metric': 'timesteps decoded/sec, 1440 states, ragged many-file job (BASELINE configs[3])',
                   'value': record.get('value'), 'unit': 'timesteps/s', 'n_gpus': self.size,
                   'steps': record.get('batches'), 'warmup': record.get('batches'),

@@ -2,7 +2,8 @@
 
 Run in the build container (where /root/reference exists):
 
-    python tests/golden/generate.py
+    python tests/golden/generate.py              (every fixture below)
+    python tests/golden/generate.py ref-cases    (golden_ref_cases.npz only)
 
 The outputs (`*.npz`) are data: inputs and the index sequences the reference's own
 compiled CPU operator (oracle/_ref, built by oracle/build.py from
@@ -173,7 +174,27 @@ def main():
     add_large('g5_c5_first2_2x2000x4096', 2, 2000, 4096, seed=0)
     large['names'] = np.array(lnames)
     np.savez_compressed(os.path.join(OUT, 'golden_large.npz'), **large)
+    ref_cases()
+
+
+def ref_cases():
+    """golden_ref_cases.npz: the reference's indices on the fresh and non-finite inputs of tests/test_oracle.py (built there
+    from seeds) and a digest of those inputs."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import test_oracle
+    cases = {}
+    for kind, build, count in (('fresh', test_oracle.fresh_case, 6), ('nan', test_oracle.nan_case, 5)):
+        for seed in range(count):
+            case = build(seed)
+            name = f'{kind}_{seed}'
+            cases[name + '/indices'] = ref(*case, threads=2).astype(np.int32)
+            cases[name + '/inputs_sha256'] = np.array(test_oracle.inputs_digest(*case))
+            print(name, case[0].shape, cases[name + '/indices'][0, :8], flush=True)
+    np.savez_compressed(os.path.join(OUT, 'golden_ref_cases.npz'), **cases)
 
 
 if __name__ == '__main__':
-    main()
+    if sys.argv[1:] == ['ref-cases']:
+        ref_cases()
+    else:
+        main()

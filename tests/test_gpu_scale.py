@@ -136,7 +136,7 @@ def test_bench_with_the_collective_forced_prints_the_same_rate():
     for attempt in range(2):
         for force in ('0', '1'):
             run = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '16', '--warmup', '8',
-                                  '--no-secondary', '--no-cpu-baseline'], cwd=ROOT, env=_child_env(TORBI_FORCE_DIST=force),
+                                  '--full', '--no-secondary', '--no-cpu-baseline'], cwd=ROOT, env=_child_env(TORBI_FORCE_DIST=force),
                                  capture_output=True, text=True, timeout=900)
             assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
             line = json.loads([text for text in run.stdout.splitlines() if text.startswith('{')][-1])
@@ -154,3 +154,25 @@ def test_bench_with_the_collective_forced_prints_the_same_rate():
             else:
                 assert 'multi_gpu' not in line
     assert abs(rates['1'] - rates['0']) / rates['0'] < 0.10, rates
+
+
+def test_plain_bench_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line and nothing that needs
+    runs of its own, K timed steps, ms_per_step consistent with value, and the last step's indices in DIR/indices.npy.
+    9 steps in groups of 8 make the last step a group of one on the first observation buffer (seed 0), whose first four
+    items the reference decoded into tests/golden/golden_large.npz."""
+    out = tmp_path / 'outputs'
+    run = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '9', '--warmup', '2',
+                          '--dump-outputs', str(out)], cwd=ROOT, env=_child_env(), capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
+    line = json.loads(run.stdout.splitlines()[-1])
+    assert line['steps'] == 9 and line['warmup'] == 2 and line['config']['launch_groups'] == [8, 1]
+    assert line['unit'] == 'timesteps/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 - 512 * 500) < 1e-6 * 512 * 500
+    for moved in ('roofline', 'single_call', 'secondary', 'cpu_baseline', 'phases_ms', 'multi_gpu'):
+        assert moved not in line, moved
+    indices = np.load(out / 'indices.npy')
+    assert indices.dtype == np.float32 and indices.shape == (512, 500)
+    assert int(indices.min()) >= 0 and int(indices.max()) < 1440
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_large.npz'))
+    np.testing.assert_array_equal(indices[:4].astype(np.int32), g['g4_c3_first4_4x500x1440/indices'])

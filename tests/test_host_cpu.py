@@ -505,7 +505,8 @@ def test_bench_starts_its_own_ranks_and_dry_runs_without_a_gpu():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5',
+                          '--full'],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
@@ -523,6 +524,26 @@ def test_bench_starts_its_own_ranks_and_dry_runs_without_a_gpu():
     assert line['n_gpus'] == 2 and line['scaling'] == 'strong'
     assert line['decode_only']['batches_per_rank'] == [3, 3]
     assert line['decode_only']['valid_timesteps'] == float(synth.lengths(3000, 100, 900).sum())
+
+
+def test_plain_bench_run_takes_its_steps_and_leaves_the_rest_to_full():
+    """Without --full the line carries the headline and the launch plan of exactly --steps steps, and no per-rank report
+    (a measurement of its own); --steps defaults to 16 for the headline workload and to every batch for c4."""
+    if torch.cuda.device_count() > 0:
+        pytest.skip('a HIP device is present: the real benchmark would run')
+    import json
+    import subprocess
+    import sys
+    import bench
+    assert bench.parse_args([]).steps == 16 and bench.parse_args(['--workload', 'c4']).steps == 0
+    assert bench.parse_args(['--workload', 'c4', '--steps', '16']).steps == 16 and not bench.parse_args([]).full
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1'],
+                         capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.splitlines()[-1])
+    assert line['n_gpus'] == 2 and line['dry_run'] is True and line['steps'] == 3 and line['warmup'] == 1
+    assert line['config']['launch_groups'] == [3] and 'multi_gpu' not in line
 
 
 def test_command_line_takes_the_reference_flags(monkeypatch, tmp_path):

@@ -5,13 +5,14 @@ CPU operator (tests/golden/generate.py), and the toy is the reference's only kno
 test (reference tests/test_core.py:7-25).
 """
 import hashlib
+import os
 
 import numpy as np
 import pytest
 
 import oracle
 from torbi_amd import synth
-from conftest import SMALL_NAMES, LARGE_NAMES
+from conftest import GOLDEN, SMALL_NAMES, LARGE_NAMES
 
 
 @pytest.mark.parametrize('name', SMALL_NAMES)
@@ -70,40 +71,21 @@ def test_tail_is_filled_with_final_state():
     assert (got[0, 3:] == got[0, 3]).all()
 
 
-def _torbi_namespace_taken():
-    # torbi_amd.torch_op.register() (dispatcher tests) defines torbi::viterbi_decode in this process; the reference's
-    # own library defines it too and aborts when loaded second
-    import sys
-    module = sys.modules.get('torbi_amd.torch_op')
-    return module is not None and module._LIBRARY is not None
+# ---- the reference operator's answers on fresh and non-finite inputs (tests/golden/generate.py -> golden_ref_cases.npz) --
+# The inputs are regenerated from their seeds here; the fixture stores the reference's indices and a digest of the inputs it
+# was given, so that a change to the case builders below cannot go unnoticed.
 
-
-@pytest.mark.skipif(not oracle.ref_available(), reason='oracle/_ref not built (no /root/reference)')
-@pytest.mark.parametrize('seed', range(6))
-def test_oracle_equals_reference_operator_on_fresh_inputs(seed):
-    if _torbi_namespace_taken():
-        pytest.skip('torbi::viterbi_decode was registered by torbi_amd.torch_op in this process')
+def fresh_case(seed):
     rng = np.random.default_rng(seed)
     B, T, S = int(rng.integers(1, 5)), int(rng.integers(1, 40)), int(rng.integers(1, 300))
     obs, trans, init = synth.problem(B, T, S, seed=1000 + seed)
     if seed % 2:   # heavy ties
         obs, trans, init = np.round(obs / 4), np.round(trans / 4), np.round(init / 4)
     frames = rng.integers(1, T + 1, B).astype(np.int32)
-    want = oracle.ref_decode(obs, frames, trans, init, num_threads=2).numpy()
-    for mode in (0, 1):
-        assert np.array_equal(oracle.decode(obs, frames, trans, init, 3, mode), want)
+    return obs, frames, trans, init
 
 
-@pytest.mark.skipif(not oracle.ref_available(), reason='oracle/_ref not built (no /root/reference)')
-@pytest.mark.parametrize('seed', range(5))
-def test_oracle_follows_the_reference_operator_on_nan_inputs(seed):
-    """NaN and +inf inputs (the HIP path decodes such items again as the reference does: csrc/nonfinite.hpp): the ORACLE
-    restates the reference also there: a NaN candidate at prev-state 0 is never replaced (viterbi.cpp:94-100 starts its running maximum there),
-    later NaN candidates never win, and the final state is ATen's argmax, which takes the first NaN of a row
-    (viterbi.cpp:218).  Checked against the reference operator itself."""
-    if _torbi_namespace_taken():
-        pytest.skip('torbi::viterbi_decode was registered by torbi_amd.torch_op in this process')
-    rng = np.random.default_rng(100 + seed)
+def nan_case(seed):
     B, T, S = 3, 12, 40
     obs, trans, init = synth.problem(B, T, S, seed=2000 + seed)
     nan = np.float32('nan')
@@ -123,6 +105,39 @@ def test_oracle_follows_the_reference_operator_on_nan_inputs(seed):
         trans[6, 0] = -np.inf
         trans[5, 3] = -np.inf
     frames = np.array([T, T, T - 2], np.int32)
-    want = oracle.ref_decode(obs, frames, trans, init, num_threads=2).numpy()
+    return obs, frames, trans, init
+
+
+def inputs_digest(obs, frames, trans, init):
+    digest = hashlib.sha256()
+    for array, kind in ((obs, np.float32), (frames, np.int32), (trans, np.float32), (init, np.float32)):
+        a = np.ascontiguousarray(array, dtype=kind)
+        digest.update(repr(a.shape).encode())
+        digest.update(a.tobytes())
+    return digest.hexdigest()
+
+
+def _reference_answer(name, case):
+    g = np.load(os.path.join(GOLDEN, 'golden_ref_cases.npz'))
+    assert inputs_digest(*case) == str(g[name + '/inputs_sha256']), f'{name}: inputs differ from those the reference decoded'
+    return g[name + '/indices']
+
+
+@pytest.mark.parametrize('seed', range(6))
+def test_oracle_equals_reference_operator_on_fresh_inputs(seed):
+    case = fresh_case(seed)
+    want = _reference_answer(f'fresh_{seed}', case)
     for mode in (0, 1):
-        assert np.array_equal(oracle.decode(obs, frames, trans, init, 2, mode), want), mode
+        assert np.array_equal(oracle.decode(*case, 3, mode), want)
+
+
+@pytest.mark.parametrize('seed', range(5))
+def test_oracle_follows_the_reference_operator_on_nan_inputs(seed):
+    """NaN and +inf inputs (the HIP path decodes such items again as the reference does: csrc/nonfinite.hpp): the ORACLE
+    restates the reference also there: a NaN candidate at prev-state 0 is never replaced (viterbi.cpp:94-100 starts its running maximum there),
+    later NaN candidates never win, and the final state is ATen's argmax, which takes the first NaN of a row
+    (viterbi.cpp:218).  Checked against the reference operator's own answers on these inputs."""
+    case = nan_case(seed)
+    want = _reference_answer(f'nan_{seed}', case)
+    for mode in (0, 1):
+        assert np.array_equal(oracle.decode(*case, 2, mode), want), mode

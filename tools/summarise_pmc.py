@@ -13,7 +13,7 @@ summary = {k: {c: {'mean_per_dispatch': sum(v) / len(v), 'dispatches': len(v)} f
 # provenance of every summary: the commit of the box's snapshot, the profiled command; for the bench command also how many
 # batches one forward launch covered (bench.py scales `traffic` by it) and the cells that launch examined
 meta = {'units': 'FETCH_SIZE / WRITE_SIZE in KiB per dispatch', 'git': os.environ.get('GIT_HASH') or None,
-        'command': os.environ.get('PROFILE_CMD') or 'python3 bench.py --steps 8 --warmup 8 --no-cpu-baseline --no-secondary '
+        'command': os.environ.get('PROFILE_CMD') or 'python3 bench.py --full --steps 8 --warmup 8 --no-cpu-baseline --no-secondary '
                                                     '--no-single-call --pipeline 1',
         'passes': 'one rocprofv3 --kernel-trace --pmc pass per counter group (tools/collect_profiles.sh)'}
 try:

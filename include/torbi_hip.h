@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define TORBI_HIP_ABI_VERSION 15
+#define TORBI_HIP_ABI_VERSION 16
 
 #define TORBI_HIP_OK 0
 #define TORBI_HIP_EINVAL (-1)      /* null pointer / non-positive dimension            */
@@ -403,6 +403,39 @@ int torbi_hip_fill_synthetic(float *dst, uint64_t count, uint64_t start, int str
  * library as torbi_hip_read_rows / _write_files / _open_heads; they touch no device, and their first call from a reader thread
  * used to wait behind the HIP runtime's start-up on the calling thread (0.35-0.65 s per early batch of a cold job).
  */
+
+/*
+ * (ABI 16) Streaming decode: B independent streams, frames pushed in pieces, the indices of every frame returned as soon
+ * as no later frame can change them (torbi_amd/stream.py, STREAM.md).  Frame c of a stream is DECIDED once the
+ * survivor paths of ALL S states at the newest frame pass through one state at c; a push returns the frames up to the
+ * newest decided one, a flush the rest.  Concatenated, they are bit-identical to torbi_hip_viterbi_decode on the whole
+ * sequence (result contract above, NaN / +-inf included).
+ *
+ * State (caller-owned, device memory, torbi_hip_stream_state_bytes(B, S, capacity) bytes, no alignment beyond 4):
+ *     ring  [B][capacity][S] fp32   posterior rows of the pending frames (frame base + r in slot (base_slot + r) % capacity)
+ *     memo  [B][capacity]    int32  survivor-set sizes of earlier frontier walks (need no initialisation)
+ *     bp    [B][S]           int32  scratch
+ * Only the ring has to be kept when the state grows: a larger state takes the pending rows (and the newest row) in their
+ * new slots and a zeroed memo.  capacity >= pending + frames of every stream of a push, >= 1.
+ *
+ * info: [B][4] int32 device array per call: {pending, base_slot, frames, fresh}.  `pending` frames pushed and not yet
+ * returned, `base_slot` the slot of the first of them, `frames` (push: 0 .. Tc new frames of this stream; flush: 1 = flush
+ * this stream, 0 = leave it), `fresh` = 1 when the stream has no frame yet (its first row is obs[0] + initial).
+ *
+ * push: observation (B, Tc, S) (Tc may be 0); transition (S, S) [next][prev] and transition_t, the same matrix transposed
+ * ([prev][next]); initial (S,).  indices_out [B][out_capacity] int32 (out_capacity >= pending + frames): row b receives the
+ * stream's newly decided frames, oldest first; counts_out [B] int32 their number (-1: info does not fit capacity or
+ * out_capacity; nothing written).  The caller advances base_slot by counts_out[b] and pending by frames - counts_out[b].
+ * flush: the flagged streams' remaining frames (the final state is the first NaN of the newest row, otherwise its first
+ * maximum), counts_out as above; the caller then starts those streams afresh.
+ * TORBI_HIP_ERANGE for S > 8000.
+ */
+size_t torbi_hip_stream_state_bytes(int B, int S, int capacity);
+int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
+                          const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
+                          int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *state, size_t state_bytes, int capacity,
+                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
 
 #ifdef __cplusplus
 }

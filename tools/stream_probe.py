@@ -1,0 +1,110 @@
+"""Measure the streaming decoder (torbi_amd.StreamDecoder) on one MI355X; prints one JSON line.
+
+  (a) B=512, S=1440, dense synthetic matrix, 500 frames in pushes of 100: timesteps/s of the stream (flush included) and
+      of torbi_amd.decode on the same whole batch in the same process, and their ratio
+  (b) the same with posteriorgram-like rows and the reference's banded pitch matrix (half width 87.2)
+  (c) B=1, S=1440, 1-frame pushes: host wall time per push, p50 / p99
+  (d) state bytes per stream and the largest `pending` seen on (a) and (b)
+Every figure of (a)-(c) is the median of --repeats runs with its min and max, device synchronised around each timed span.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torbi_amd  # noqa: E402
+from torbi_amd import synth, viterbi  # noqa: E402
+
+
+def spread(values):
+    v = sorted(values)
+    return {'median': float(np.median(v)), 'min': float(v[0]), 'max': float(v[-1]), 'runs': len(v)}
+
+
+def peaked(B, T, S, dev):
+    gen = torch.Generator(device=dev).manual_seed(7)
+    logits = torch.randn((B, T, S), device=dev, generator=gen) * 2.0
+    centre = torch.randint(0, S, (B, T, 1), device=dev, generator=gen)
+    logits -= ((torch.arange(S, device=dev)[None, None, :] - centre).abs().float() / 12.0) ** 2
+    return torch.log_softmax(logits, dim=-1).clamp_(min=math.log(torch.finfo(torch.float32).tiny))
+
+
+def batch_case(obs, trans, init, push, repeats):
+    B, T, S = obs.shape
+    dev = obs.device
+    frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    stream_s, decode_s, pending_max = [], [], 0
+    viterbi.decode(obs, frames, trans, init)                # warm-up (library load, path choice)
+    for _ in range(repeats + 1):
+        dec = torbi_amd.StreamDecoder(B, S, trans, init, log_probs=True, gpu=0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(0, T, push):
+            dec.push(obs[:, t:t + push])
+            pending_max = max(pending_max, int(dec.pending.max()))
+        dec.flush()
+        torch.cuda.synchronize()
+        stream_s.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        viterbi.decode(obs, frames, trans, init)
+        torch.cuda.synchronize()
+        decode_s.append(time.perf_counter() - t0)
+    stream_s, decode_s = stream_s[1:], decode_s[1:]          # (the first pass grows the ring)
+    ts = [B * T / s for s in stream_s]
+    td = [B * T / s for s in decode_s]
+    return {'stream_timesteps_per_s': spread(ts), 'decode_timesteps_per_s': spread(td),
+            'ratio': spread([a / b for a, b in zip(ts, td)]), 'push_frames': push,
+            'state_bytes_per_stream': dec._state_bytes // B, 'pending_max': pending_max}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--batch', type=int, default=512)
+    ap.add_argument('--frames', type=int, default=500)
+    ap.add_argument('--states', type=int, default=1440)
+    ap.add_argument('--push', type=int, default=100)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--single-pushes', type=int, default=400)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    B, T, S = args.batch, args.frames, args.states
+    result = {'device': torch.cuda.get_device_name(0), 'B': B, 'T': T, 'S': S}
+
+    _, trans, init = synth.problem(1, 1, S, seed=0)
+    trans, init = torch.from_numpy(trans).to(dev), torch.from_numpy(init).to(dev)
+    obs = viterbi.fill_synthetic((B, T, S), synth.STREAM_OBSERVATION, seed=0, device=dev)
+    result['a_dense'] = batch_case(obs, trans, init, args.push, args.repeats)
+    del obs
+    band = torch.from_numpy(synth.banded_transition(S, 87.2)).to(dev)
+    flat = torch.full((S,), math.log(1. / S), dtype=torch.float32, device=dev)
+    obs = peaked(B, T, S, dev)
+    result['b_pitch'] = batch_case(obs, band, flat, args.push, args.repeats)
+
+    # (c) one live stream, one frame per push
+    one = obs[:1, :args.single_pushes + 20].contiguous()
+    runs = []
+    for _ in range(args.repeats):
+        dec = torbi_amd.StreamDecoder(1, S, band, flat, log_probs=True, gpu=0)
+        for t in range(20):                                  # warm-up pushes (ring growth)
+            dec.push(one[:, t:t + 1])
+        times = []
+        for t in range(20, one.shape[1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dec.push(one[:, t:t + 1])
+            times.append(time.perf_counter() - t0)
+        dec.flush()
+        runs.append((np.percentile(times, 50) * 1e3, np.percentile(times, 99) * 1e3))
+    result['c_single_push_ms'] = {'p50': spread([r[0] for r in runs]), 'p99': spread([r[1] for r in runs])}
+    result['d_bytes_per_pending_frame_per_stream'] = 4 * S + 4
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()

@@ -36,6 +36,7 @@
 #include "small_states.hpp"
 #include "band_forward.hpp"
 #include "band_tile_forward.hpp"
+#include "stream.hpp"
 
 namespace {
 
@@ -2380,6 +2381,88 @@ int torbi_hip_fill_synthetic(float *dst, uint64_t count, uint64_t start, int str
     const int grid = (int)(blocks < 8192 ? blocks : 8192);
     hipLaunchKernelGGL(fill_synthetic_kernel, dim3(grid), dim3(256), 0,
                        static_cast<hipStream_t>(stream), dst, count, start, key);
+    return (int)hipGetLastError();
+}
+
+// ---- streaming decode (stream.hpp) ----
+
+static size_t stream_ring_bytes(int B, int S, int capacity) { return (size_t)B * capacity * S * sizeof(float); }
+
+size_t torbi_hip_stream_state_bytes(int B, int S, int capacity) {
+    if (B < 1 || S < 1 || capacity < 1) return 0;
+    return stream_ring_bytes(B, S, capacity) + (size_t)B * capacity * sizeof(int32_t) + (size_t)B * S * sizeof(int32_t);
+}
+
+static int stream_args_ok(const void *info, const void *transition, const void *state, size_t state_bytes, int capacity,
+                          const void *indices_out, int out_capacity, const void *counts_out, int B, int S) {
+    if (B < 1 || S < 1 || capacity < 1 || out_capacity < 1) return TORBI_HIP_EINVAL;
+    if (!info || !transition || !state || !indices_out || !counts_out) return TORBI_HIP_EINVAL;
+    if (S > stream::kMaxStates) return TORBI_HIP_ERANGE;
+    if (state_bytes < torbi_hip_stream_state_bytes(B, S, capacity)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
+                          const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
+                          int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
+    int code = stream_args_ok(info, transition, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    if (Tc < 0 || (Tc > 0 && (!observation || !transition_t || !initial))) return TORBI_HIP_EINVAL;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const stream::Info *in = reinterpret_cast<const stream::Info *>(info);
+    float *ring = static_cast<float *>(state);
+    int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
+    int32_t *bp = memo + (size_t)B * capacity;
+    if (Tc > 0) {
+        // streams per workgroup: as many as the double-buffered rows let share one pass over the matrix, but no fewer
+        // workgroups than compute units while there are streams for them
+        int G = 16;
+        while (G > 1 && (size_t)2 * G * S * sizeof(float) > (size_t)stream::kMaxLdsBytes) G >>= 1;
+        const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
+        while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
+        const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(transition_t) & 15) == 0;
+        const dim3 grid((B + G - 1) / G);
+        const size_t lds = (size_t)2 * G * S * sizeof(float);
+#define TORBI_STREAM_FORWARD(g)                                                                                         \
+        if (vec)                                                                                                        \
+            hipLaunchKernelGGL((stream::stream_forward_kernel<g, 4>), grid, dim3(stream::kThreads), lds, st, observation, \
+                               Tc, in, transition_t, initial, ring, memo, capacity, B, S);                              \
+        else                                                                                                            \
+            hipLaunchKernelGGL((stream::stream_forward_kernel<g, 1>), grid, dim3(stream::kThreads), lds, st, observation, \
+                               Tc, in, transition_t, initial, ring, memo, capacity, B, S)
+        switch (G) {
+            case 16: TORBI_STREAM_FORWARD(16); break;
+            case 8: TORBI_STREAM_FORWARD(8); break;
+            case 4: TORBI_STREAM_FORWARD(4); break;
+            case 2: TORBI_STREAM_FORWARD(2); break;
+            default: TORBI_STREAM_FORWARD(1); break;
+        }
+#undef TORBI_STREAM_FORWARD
+        if ((code = (int)hipGetLastError()) != hipSuccess) return code;
+        if (S > 1) {
+            hipLaunchKernelGGL(stream::stream_first_step_kernel, dim3((S + 3) / 4, B), dim3(stream::kThreads), 0, st, in,
+                               transition, ring, bp, capacity, S);
+            if ((code = (int)hipGetLastError()) != hipSuccess) return code;
+        }
+    }
+    hipLaunchKernelGGL(stream::stream_walk_kernel<false>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t), st,
+                       in, transition, ring, memo, bp, capacity, indices_out, out_capacity, counts_out, S);
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *state, size_t state_bytes, int capacity,
+                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
+    const int code = stream_args_ok(info, transition, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    float *ring = static_cast<float *>(state);
+    int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
+    hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ring, memo,
+                       memo + (size_t)B * capacity, capacity, indices_out, out_capacity, counts_out, S);
     return (int)hipGetLastError();
 }
 

@@ -1,0 +1,307 @@
+"""Exact streaming Viterbi decoding: frames pushed in pieces, indices returned as soon as they are final.
+
+Frame c of a stream is DECIDED once the survivor paths of every state at the newest frame pass through one single state at
+c: no later observation can change the path up to c any more.  `push` returns, per stream, the frames that became decided,
+`flush` the rest; concatenated they are bit-identical to `from_probabilities` on the whole sequence (NaN and +/-inf
+included).  The HIP route is csrc/stream.hpp behind torbi_hip_stream_* (include/torbi_hip.h); `gpu=None` runs the same
+decoder on the host with torch CPU ops.  STREAM.md has the layout and the kernels.
+"""
+import ctypes
+import math
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .core import _compute_device, _host_log, _prepared_transition
+from .viterbi import epsilon_clamp_, log_epsilon_clamp
+
+# ring slots of a new decoder; the ring doubles when a push needs more
+INITIAL_CAPACITY = 16
+
+
+class StreamDecoder:
+    """Viterbi decoding of `batch` independent streams whose frames arrive in pieces.
+
+    `transition` (states, states) [next, prev], `initial` (states,) and `log_probs` mean what they mean to
+    `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform transition log(1/S)); observations go
+    through the same log() and epsilon round trip.  `gpu` is a HIP device index; None decodes on the host.
+
+    Device memory per stream: (4 * states + 4) bytes per pending frame (a posterior row and a word of the frontier walk) plus
+    4 * states; the ring grows by doubling, so a stream whose frames never become decided (an identity transition matrix)
+    holds all of them until `flush`.
+
+        dec = StreamDecoder(batch, states, transition, initial)
+        out = dec.push(observation)       # (batch, Tc, states) -> `batch` int32 tensors, the frames decided by this push
+        rest = dec.flush()                # the remaining frames of every stream; the streams start afresh
+    """
+
+    def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
+                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0):
+        if batch < 1 or states < 1:
+            raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
+        self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
+        S = self.states
+        self.device = torch.device('cpu') if gpu is None else _compute_device(gpu)
+        tiny = torch.finfo(torch.float32).tiny
+        # the steps of from_probabilities (core.py), element by element: chunking cannot change a bit
+        if initial is None:
+            initial = torch.full((S,), math.log((1. / S) + tiny), dtype=torch.float32, device=self.device)
+        elif not log_probs:
+            initial = torch.log(initial)
+        if transition is None:
+            transition = torch.full((S, S), math.log(1. / S), dtype=torch.float32, device=self.device)
+        elif gpu is None:
+            transition = transition if log_probs else torch.log(transition)
+        else:
+            transition = _prepared_transition(transition, log_probs, self.device)
+        self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
+        self.transition = transition.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(self.transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
+            raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
+        self._frames = np.zeros(self.batch, dtype=np.int64)        # frames pushed
+        self._base = np.zeros(self.batch, dtype=np.int64)          # first frame not yet returned
+        if gpu is None:
+            self._rows = [[] for _ in range(self.batch)]            # posterior rows of frames base-1 .. n-1 (host)
+            self._memo = [{} for _ in range(self.batch)]            # frame -> survivor-set size of an earlier walk
+        else:
+            self._lib = _lib.load()
+            self._transposed = self.transition.t().contiguous()
+            self._capacity = 0
+            self._state = None
+            self._grow(INITIAL_CAPACITY)
+
+    # ------------------------------------------------------------------ public
+    @property
+    def frames(self) -> torch.Tensor:
+        """(batch,) int64: frames pushed to each stream since it started."""
+        return torch.from_numpy(self._frames.copy())
+
+    @property
+    def pending(self) -> torch.Tensor:
+        """(batch,) int64: frames pushed and not yet returned."""
+        return torch.from_numpy(self._frames - self._base)
+
+    def push(self, observation: torch.Tensor, frames: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """Append frames to the streams and return what became decided.
+
+        observation (batch, Tc, states); frames (batch,) valid frames per stream, 0 .. Tc (None = all Tc).  Returns `batch`
+        1-D int32 tensors on the compute device: the indices of the frames this push decided, oldest first.  On the GPU this
+        reads one small per-stream count array back, so every call synchronises the host with the current stream once.
+        """
+        if observation.dim() != 3 or observation.shape[0] != self.batch or observation.shape[2] != self.states:
+            raise ValueError(f'observation must be ({self.batch}, Tc, {self.states}), got {tuple(observation.shape)}')
+        Tc = int(observation.shape[1])
+        if frames is None:
+            f = np.full(self.batch, Tc, dtype=np.int64)
+        else:
+            f = torch.as_tensor(frames).detach().to('cpu', torch.int64).reshape(-1).numpy().copy()
+            if f.shape[0] != self.batch or (f < 0).any() or (f > Tc).any():
+                raise ValueError(f'frames must hold {self.batch} counts in 0 .. {Tc}')
+        obs = self._prepare(observation)
+        if self.gpu is None:
+            return self._push_host(obs, f)
+        return self._push_device(obs, f)
+
+    def flush(self, items: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """End streams `items` (default: all): return their remaining indices (one 1-D int32 tensor per item, in the
+        order given) and reset them, so that their next push starts a new sequence from `initial`.  The final state is the
+        first NaN of the newest posterior row, otherwise its first maximum (the reference's argmax)."""
+        items = list(range(self.batch)) if items is None else [int(k) for k in items]
+        if any(k < 0 or k >= self.batch for k in items):
+            raise IndexError(f'stream index out of range 0 .. {self.batch - 1}')
+        if self.gpu is None:
+            rest = {k: self._flush_host(k) for k in items}
+        else:
+            rest = self._flush_device(sorted(set(items)))
+        for k in set(items):
+            self._frames[k] = self._base[k] = 0
+        return [rest[k] for k in items]
+
+    # ------------------------------------------------------------------ inputs
+    def _prepare(self, observation: torch.Tensor) -> torch.Tensor:
+        """from_probabilities' log() and epsilon round trip (core.py), on a copy: the caller's tensor is not written."""
+        tiny = torch.finfo(torch.float32).tiny
+        if self.gpu is None:
+            x = observation if self.log_probs else torch.log(observation)
+            x = x.to(device=self.device, dtype=torch.float32)
+            if x.data_ptr() == observation.data_ptr():
+                x = x.clone()
+            torch.exp_(x)
+            x += tiny
+            torch.log_(x)
+            return x.contiguous()
+        clamped = None
+        if not self.log_probs:
+            if observation.device == self.device:
+                clamped = log_epsilon_clamp(observation.contiguous())
+            if clamped is None:
+                observation = _host_log(observation)
+        if clamped is not None:
+            return clamped
+        on_host = observation
+        x = observation.to(device=self.device, dtype=torch.float32).contiguous()
+        if getattr(on_host, 'torbi_slab', None) is not None:        # (_host_log's pooled buffer: free once the copy has left)
+            from . import slabs
+            left = torch.cuda.Event()
+            left.record(torch.cuda.current_stream(self.device))
+            slabs.pool(None).give(on_host.torbi_slab, left)
+        if x.data_ptr() == observation.data_ptr():
+            x = x.clone()
+        return epsilon_clamp_(x)
+
+    # ------------------------------------------------------------------ host route
+    def _row(self, prev: torch.Tensor, obs_row: torch.Tensor) -> torch.Tensor:
+        cand = prev[None, :] + self.transition                    # [next, prev]
+        nan = torch.isnan(cand)
+        best = cand.masked_fill(nan, -math.inf).amax(dim=1)
+        # the reference's scan keeps a NaN candidate of prev-state 0 and never takes one elsewhere
+        best = torch.where(nan[:, 0], torch.full_like(best, math.nan), best)
+        return obs_row + best
+
+    def _backpointers(self, prev: torch.Tensor, states: torch.Tensor) -> torch.Tensor:
+        cand = prev[None, :] + self.transition[states]
+        nan = torch.isnan(cand)
+        arg = cand.masked_fill(nan, -math.inf).argmax(dim=1)     # first maximum of the non-NaN candidates
+        return torch.where(nan[:, 0], torch.zeros_like(arg), arg)
+
+    @staticmethod
+    def _final_state(row: torch.Tensor) -> int:
+        nan = torch.isnan(row)
+        if bool(nan.any()):
+            return int(nan.to(torch.uint8).argmax())
+        return int(row.argmax())
+
+    def _backtrace_host(self, b: int, c: int, state: int) -> torch.Tensor:
+        """Indices of frames base .. c of stream b, the path through `state` at frame c."""
+        base, rows = int(self._base[b]), self._rows[b]
+        first = int(self._frames[b]) - len(rows)                  # frame of rows[0]
+        out = [state]
+        for t in range(c, base, -1):
+            state = int(self._backpointers(rows[t - 1 - first], torch.tensor([state]))[0])
+            out.append(state)
+        return torch.tensor(out[::-1], dtype=torch.int32)
+
+    def _push_host(self, obs: torch.Tensor, f: np.ndarray) -> List[torch.Tensor]:
+        S, result = self.states, []
+        for b in range(self.batch):
+            rows = self._rows[b]
+            for t in range(int(f[b])):
+                rows.append(obs[b, t] + self.initial if self._frames[b] == 0 else self._row(rows[-1], obs[b, t]))
+                self._frames[b] += 1
+            n, base = int(self._frames[b]), int(self._base[b])
+            c, state = -1, 0
+            if f[b] > 0 and S == 1:
+                c = n - 1
+            elif f[b] > 0 and n - base >= 2:
+                first = n - len(rows)
+                memo = self._memo[b]
+                alive = torch.arange(S)
+                for t in range(n - 1, base, -1):                      # alive: the set at frame t
+                    alive = torch.unique(self._backpointers(rows[t - 1 - first], alive))
+                    k = int(alive.numel())
+                    if k == 1:
+                        c, state = t - 1, int(alive[0])
+                        break
+                    # same size as an earlier walk's set here: the same set, and that walk found no single state below
+                    same = memo.get(t - 1) == k
+                    memo[t - 1] = k
+                    if same:
+                        break
+            if c >= 0:
+                result.append(self._backtrace_host(b, c, state))
+                self._base[b] = c + 1
+                keep = n - (c + 1) + 1                                # pending rows and the one before them
+                del rows[:max(0, len(rows) - keep)]
+                for t in [t for t in self._memo[b] if t <= c]:
+                    del self._memo[b][t]
+            else:
+                result.append(torch.empty(0, dtype=torch.int32))
+        return result
+
+    def _flush_host(self, b: int) -> torch.Tensor:
+        n, base = int(self._frames[b]), int(self._base[b])
+        out = torch.empty(0, dtype=torch.int32)
+        if n > base:
+            out = self._backtrace_host(b, n - 1, self._final_state(self._rows[b][-1]))
+        self._rows[b], self._memo[b] = [], {}
+        return out
+
+    # ------------------------------------------------------------------ HIP route
+    def _grow(self, capacity: int) -> None:
+        """Ring of `capacity` slots (at least double the old one); pending rows and the newest row move to their new
+        slots by one device copy, the walk memo starts empty."""
+        B, S = self.batch, self.states
+        capacity = max(int(capacity), 2 * self._capacity)
+        capacity = 1 << (capacity - 1).bit_length()
+        nbytes = self._lib.torbi_hip_stream_state_bytes(B, S, capacity)
+        if nbytes == 0:
+            raise ValueError('torbi_hip_stream_state_bytes rejected the shape')
+        state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ring = state[:B * capacity * S * 4].view(torch.float32).view(B, capacity, S)
+        state[B * capacity * S * 4:B * capacity * (S + 1) * 4].zero_()
+        if self._state is not None:
+            items, frames = [], []
+            for b in range(B):
+                n = int(self._frames[b])
+                if n == 0:
+                    continue
+                lo = min(int(self._base[b]), n - 1)
+                frames.append(np.arange(lo, n, dtype=np.int64))
+                items.append(np.full(n - lo, b, dtype=np.int64))
+            if items:
+                bi = torch.from_numpy(np.concatenate(items)).to(self.device)
+                fr = torch.from_numpy(np.concatenate(frames)).to(self.device)
+                ring[bi, fr % capacity] = self._ring()[bi, fr % self._capacity]
+        self._state, self._capacity, self._state_bytes = state, capacity, nbytes
+
+    def _ring(self) -> torch.Tensor:
+        B, S, cap = self.batch, self.states, self._capacity
+        return self._state[:B * cap * S * 4].view(torch.float32).view(B, cap, S)
+
+    def _info(self, pending: np.ndarray, third: np.ndarray) -> torch.Tensor:
+        info = np.stack([pending, self._base % self._capacity, third, (self._frames == 0).astype(np.int64)], axis=1)
+        return torch.from_numpy(info.astype(np.int32)).to(self.device)
+
+    def _results(self, out: torch.Tensor, counts: torch.Tensor, what: str) -> np.ndarray:
+        got = counts.cpu().numpy().astype(np.int64)           # (the one host synchronisation of the call)
+        if (got < 0).any():
+            raise _lib.TorbiHipError(f'{what}: stream state does not match the call (counts {got.tolist()})')
+        return got
+
+    def _push_device(self, obs: torch.Tensor, f: np.ndarray) -> List[torch.Tensor]:
+        B, S = self.batch, self.states
+        pending = self._frames - self._base
+        need = int((pending + f).max())
+        if need > self._capacity:
+            self._grow(need)
+        info = self._info(pending, f)
+        out = torch.empty((B, max(1, need)), dtype=torch.int32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        Tc = int(obs.shape[1])
+        _lib.check(self._lib.torbi_hip_stream_push(
+            obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
+            self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+            counts.data_ptr(), B, S, self.device.index or 0, ctypes.c_void_p(stream)), 'torbi_hip_stream_push')
+        got = self._results(out, counts, 'torbi_hip_stream_push')
+        self._frames += f
+        self._base += got
+        return [out[b, :got[b]] for b in range(B)]
+
+    def _flush_device(self, items: List[int]) -> dict:
+        B, S = self.batch, self.states
+        pending = self._frames - self._base
+        marks = np.zeros(B, dtype=np.int64)
+        marks[items] = 1
+        info = self._info(pending, marks)
+        out = torch.empty((B, max(1, int(pending.max()))), dtype=torch.int32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.torbi_hip_stream_flush(
+            info.data_ptr(), self.transition.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity,
+            out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, self.device.index or 0, ctypes.c_void_p(stream)),
+            'torbi_hip_stream_flush')
+        got = self._results(out, counts, 'torbi_hip_stream_flush')
+        return {k: out[k, :got[k]] for k in items}

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define TORBI_HIP_ABI_VERSION 16
+#define TORBI_HIP_ABI_VERSION 17
 
 #define TORBI_HIP_OK 0
 #define TORBI_HIP_EINVAL (-1)      /* null pointer / non-positive dimension            */
@@ -436,6 +436,31 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
 int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *state, size_t state_bytes, int capacity,
                            int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+
+/*
+ * (ABI 17) Forward-backward: per-frame state posteriors and the sequence log-likelihood of the HMM that
+ * torbi_hip_viterbi_decode decodes (torbi_amd/posterior.py, POSTERIOR.md).  Inputs as there: observation (B, T, S) log
+ * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.  For t < F_b:
+ *     log alpha_0[j] = initial[j] + obs_0[j],  log alpha_t[j] = obs_t[j] + logsumexp_i (transition[j][i] + log alpha_{t-1}[i])
+ *     log beta_{F-1}[j] = 0,                   log beta_t[i]  = logsumexp_j (transition[j][i] + obs_{t+1}[j] + log beta_{t+1}[j])
+ *     L_b = logsumexp_j log alpha_{F-1}[j],    gamma_t[j]     = exp(log alpha_t[j] + log beta_t[j] - L_b)
+ * posterior_out (B, T, S) fp32 receives gamma (rows t >= F_b are 0), loglik_out (B,) fp32 receives L (summed in fp64).
+ * -inf entries are zero probabilities.  An item of total probability 0 gets L = -inf and NaN rows t < F_b; a NaN or +inf in
+ * anything an item reads gives it L = NaN and NaN rows; an item's bits never depend on other items' data.
+ *
+ * workspace: device scratch of torbi_hip_forward_backward_workspace_bytes(B, T, S) bytes (no initialisation; both entry
+ * points).  One launch per timestep and pass, no host synchronisation: a call can be captured into a graph.
+ * The uniform entry point takes a matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))) and computes
+ * the same quantities in closed form (beta is constant over states): one elementwise pass and a per-item fp64 sum.
+ * TORBI_HIP_ERANGE for S > 16384, more than 65535 * 32 items or more than 2^32 item frames (B * T).
+ */
+size_t torbi_hip_forward_backward_workspace_bytes(int B, int T, int S);
+int torbi_hip_forward_backward(const float *observation, const int32_t *batch_frames, const float *transition,
+                               const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                               size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                       const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                                       size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ SOURCE = os.path.join(_HERE, 'csrc', 'torbi_hip.hip')
 INCLUDE = os.path.join(ROOT, 'include')
 # TORBI_HIP_LIBRARY: an alternative build of the library (tools/variants_probe.py: -D experiments)
 LIBRARY = os.environ.get('TORBI_HIP_LIBRARY') or os.path.join(_HERE, 'libtorbi_hip.so')
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 # every symbol include/torbi_hip.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -81,6 +81,13 @@ SYMBOLS = {
     'torbi_hip_stream_flush': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
         _c.c_int, _c.c_void_p]),
+    'torbi_hip_forward_backward_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_forward_backward': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_forward_backward_uniform': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
 }
 
 MAX_BATCHES = 16        # TORBI_HIP_MAX_BATCHES

@@ -37,6 +37,7 @@
 #include "band_forward.hpp"
 #include "band_tile_forward.hpp"
 #include "stream.hpp"
+#include "forward_backward.hpp"
 
 namespace {
 
@@ -2463,6 +2464,130 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
     hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
                        static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ring, memo,
                        memo + (size_t)B * capacity, capacity, indices_out, out_capacity, counts_out, S);
+    return (int)hipGetLastError();
+}
+
+// ---- forward-backward: state posteriors and log-likelihood (forward_backward.hpp) ----
+
+size_t torbi_hip_forward_backward_workspace_bytes(int B, int T, int S) {
+    if (B < 1 || T < 1 || S < 1 || S > fb::kMaxStates) return 256;
+    return fb::layout(B, T, S).total;
+}
+
+static int fb_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *post,
+                      const void *loglik, const void *ws, size_t ws_bytes, int B, int T, int S) {
+    if (B < 0 || T < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!obs || !frames || !matrix || !initial || !post || !loglik || !ws) return TORBI_HIP_EINVAL;
+    // (grid limits: 32-item tiles on grid y of the step kernels; rows / 4 workgroups on grid x of the row kernels)
+    if (S > fb::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32)
+        return TORBI_HIP_ERANGE;
+    if (ws_bytes < torbi_hip_forward_backward_workspace_bytes(B, T, S)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+static char *fb_base(void *workspace) {
+    return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+}
+
+// One step launch: 32 x 32 tiles (states x items).  With at least two tiles per compute unit, four waves per tile stage the
+// operands through LDS; with fewer, K is split over as many waves as bring the launch to two per SIMD (at most 16 per
+// workgroup), each reading its chunks from global memory.
+extern "C++" template <bool BACKWARD>
+static hipError_t fb_step(const float *obs, const int32_t *frames, const float *mat, const float *m, const float *cbuf,
+                          float *partial, const float *loglik, float *post, const float *x_in, float *w_out, int t, int B,
+                          int T, int S, bool vec, int cus, hipStream_t st) {
+    const unsigned tiles = (unsigned)((S + 31) / 32) * (unsigned)((B + 31) / 32);
+    const dim3 grid((S + 31) / 32, (B + 31) / 32);
+#define TORBI_FB_STEP(staged, ks)                                                                                         \
+    do {                                                                                                                  \
+        if (vec)                                                                                                          \
+            hipLaunchKernelGGL((fb::fb_step_kernel<staged, BACKWARD, true>), grid, dim3(64 * (ks)), 0, st, obs, frames, mat, \
+                               m, cbuf, partial, loglik, post, x_in, w_out, t, B, T, S, ks);                               \
+        else                                                                                                              \
+            hipLaunchKernelGGL((fb::fb_step_kernel<staged, BACKWARD, false>), grid, dim3(64 * (ks)), 0, st, obs, frames,   \
+                               mat, m, cbuf, partial, loglik, post, x_in, w_out, t, B, T, S, ks);                          \
+    } while (0)
+    if (tiles >= 2u * cus) {
+        TORBI_FB_STEP(true, 4);
+    } else {
+        int KS = 1;
+        while (KS * 2 <= fb::kMaxWaves && (long long)tiles * KS < 8LL * cus && 8 * KS * 2 <= S) KS *= 2;
+        TORBI_FB_STEP(false, KS);
+    }
+#undef TORBI_FB_STEP
+    return hipGetLastError();
+}
+
+int torbi_hip_forward_backward(const float *observation, const int32_t *batch_frames, const float *transition,
+                               const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                               size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = fb_args_ok(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace,
+                              workspace_bytes, B, T, S);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fb::Layout l = fb::layout(B, T, S);
+    char *base = fb_base(workspace);
+    float *E = reinterpret_cast<float *>(base + l.E), *Et = reinterpret_cast<float *>(base + l.Et);
+    float *m = reinterpret_cast<float *>(base + l.m), *cbuf = reinterpret_cast<float *>(base + l.c);
+    float *partial = reinterpret_cast<float *>(base + l.partial), *w = reinterpret_cast<float *>(base + l.w);
+    const size_t wrow = (size_t)B * fb::padded_states(S);
+    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
+    hipError_t e;
+    {
+        const size_t n = (size_t)fb::padded_rows(S) * fb::padded_states(S);
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(fb::fb_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, E, Et, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_forward_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, m,
+                       posterior_out, partial, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(posterior_out) & 15) == 0;
+    for (int t = 1; t < T; ++t)
+        if ((e = fb_step<false>(observation, batch_frames, E, m, cbuf, partial, loglik_out, posterior_out, posterior_out,
+                                nullptr, t, B, T, S, vec, cus, st)) != hipSuccess)
+            return (int)e;
+    hipLaunchKernelGGL(fb::fb_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, m, partial, cbuf, loglik_out, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_backward_last_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, batch_frames, m,
+                       cbuf, loglik_out, posterior_out, w, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    for (int t = T - 2; t >= 0; --t)
+        if ((e = fb_step<true>(observation, batch_frames, Et, m, cbuf, partial, loglik_out, posterior_out,
+                               w + ((t + 1) & 1) * wrow, w + (t & 1) * wrow, t, B, T, S, true, cus, st)) != hipSuccess)
+            return (int)e;
+    return TORBI_HIP_OK;
+}
+
+int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                       const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                                       size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = fb_args_ok(observation, batch_frames, initial /* (no matrix) */, initial, posterior_out, loglik_out,
+                              workspace, workspace_bytes, B, T, S);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    double *lse = reinterpret_cast<double *>(fb_base(workspace));
+    const size_t rows = (size_t)B * T;
+    const bool vec = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(observation) | reinterpret_cast<uintptr_t>(posterior_out)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(fb::fb_uniform_rows_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation,
+                           batch_frames, initial, posterior_out, lse, B, T, S);
+    else
+        hipLaunchKernelGGL(fb::fb_uniform_rows_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation,
+                           batch_frames, initial, posterior_out, lse, B, T, S);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
+                       posterior_out, loglik_out, T, S);
     return (int)hipGetLastError();
 }
 

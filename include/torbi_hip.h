@@ -462,6 +462,24 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
                                        const float *initial, float *posterior_out, float *loglik_out, void *workspace,
                                        size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
+/*
+ * Expected counts (added within ABI 17): torbi_hip_forward_backward on the same inputs, which writes posterior_out and
+ * loglik_out bit for bit as that call does, and in addition, with a per-item weight g_b (item_weights (B,) fp32; null:
+ * all ones) and xi_t(j, i) = P(s_{t-1} = i, s_t = j | obs_b):
+ *     counts_out[j][i]      = sum_b g_b sum_{1 <= t < F_b} xi_t(j, i)      (S, S) fp32, [next][prev] like `transition`
+ *     initial_counts_out[j] = sum_b g_b gamma_0^b[j]                        (S,) fp32
+ * An item with g_b == 0 or a non-finite L_b is skipped, not multiplied: a NaN item adds nothing.  The summation order is
+ * fixed (over t from F - 1 down to 1, over items in order), so the bits of both outputs depend on the inputs only; no
+ * float atomics.  workspace: torbi_hip_forward_backward_counts_workspace_bytes(B, T, S) bytes.  No host synchronisation:
+ * with a caller-owned workspace a call can be captured into a graph.  Errors as torbi_hip_forward_backward, and
+ * TORBI_HIP_EINVAL for a null counts_out or initial_counts_out.
+ */
+size_t torbi_hip_forward_backward_counts_workspace_bytes(int B, int T, int S);
+int torbi_hip_forward_backward_counts(const float *observation, const int32_t *batch_frames, const float *transition,
+                                      const float *initial, const float *item_weights, float *posterior_out,
+                                      float *loglik_out, float *counts_out, float *initial_counts_out, void *workspace,
+                                      size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,8 +19,11 @@ from .state import reset as reset_path_state
 from .core import release_job_memory
 from .stream import StreamDecoder
 from .posterior import forward_backward, forward_backward_workspace_bytes, state_posteriors
+from .training import (expected_counts, expected_counts_workspace_bytes, forward_backward_counts,
+                       log_likelihood)
 
 __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 'workspace_bytes', 'set_forward_path', 'forward_path', 'from_probabilities', 'from_file', 'from_file_to_file',
            'from_files_to_files', 'from_dataloader', 'save', 'save_masked', 'data', 'synth',
            'distributed', 'DecodePipeline', 'BATCH_SIZE', 'NUM_WORKERS', 'reset_path_state', 'release_job_memory', 'timer',
-           'StreamDecoder', 'state_posteriors', 'forward_backward', 'forward_backward_workspace_bytes']
+           'StreamDecoder', 'state_posteriors', 'forward_backward', 'forward_backward_workspace_bytes',
+           'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood']

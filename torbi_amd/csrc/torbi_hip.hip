@@ -38,6 +38,7 @@
 #include "band_tile_forward.hpp"
 #include "stream.hpp"
 #include "forward_backward.hpp"
+#include "counts.hpp"
 
 namespace {
 
@@ -2519,12 +2520,17 @@ static hipError_t fb_step(const float *obs, const int32_t *frames, const float *
     return hipGetLastError();
 }
 
-int torbi_hip_forward_backward(const float *observation, const int32_t *batch_frames, const float *transition,
-                               const float *initial, float *posterior_out, float *loglik_out, void *workspace,
-                               size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
-    const int rc = fb_args_ok(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace,
-                              workspace_bytes, B, T, S);
-    if (rc != TORBI_HIP_OK || B == 0) return rc;
+// Expected-count outputs of torbi_hip_forward_backward_counts; null for the plain call.
+struct FbCounts {
+    const float *weights;
+    float *counts, *initial_counts;
+};
+
+// The dense route.  With `counts`, one fb_counts_kernel launch for pair t + 1 goes in front of backward step t (the
+// kernels that produce posterior and log-likelihood are the same launches with the same arguments either way).
+static int fb_dense(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                    float *posterior_out, float *loglik_out, void *workspace, int B, int T, int S, int device,
+                    void *stream, const FbCounts *counts) {
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2559,11 +2565,60 @@ int torbi_hip_forward_backward(const float *observation, const int32_t *batch_fr
     hipLaunchKernelGGL(fb::fb_backward_last_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, batch_frames, m,
                        cbuf, loglik_out, posterior_out, w, B, T, S);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    for (int t = T - 2; t >= 0; --t)
+    const dim3 cgrid((S + fb::kCountsTile - 1) / fb::kCountsTile, (S + fb::kCountsTile - 1) / fb::kCountsTile);
+    for (int t = T - 2; t >= 0; --t) {
+        if (counts) {
+            const float *wt = w + ((t + 1) & 1) * wrow;
+            const int first = t == T - 2;
+            if (vec)
+                hipLaunchKernelGGL(fb::fb_counts_kernel<true>, cgrid, dim3(256), 0, st, batch_frames, counts->weights,
+                                   loglik_out, cbuf, posterior_out, wt, counts->counts, t + 1, B, T, S, first);
+            else
+                hipLaunchKernelGGL(fb::fb_counts_kernel<false>, cgrid, dim3(256), 0, st, batch_frames, counts->weights,
+                                   loglik_out, cbuf, posterior_out, wt, counts->counts, t + 1, B, T, S, first);
+            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        }
         if ((e = fb_step<true>(observation, batch_frames, Et, m, cbuf, partial, loglik_out, posterior_out,
                                w + ((t + 1) & 1) * wrow, w + (t & 1) * wrow, t, B, T, S, true, cus, st)) != hipSuccess)
             return (int)e;
+    }
+    if (counts) {
+        const size_t n = (size_t)S * S;
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(fb::fb_counts_finalize_kernel, dim3(grid), dim3(256), 0, st, E, counts->counts, S, T > 1 ? 1 : 0);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(fb::fb_initial_counts_kernel, dim3((S + 255) / 256), dim3(256), 0, st, counts->weights,
+                           loglik_out, posterior_out, counts->initial_counts, B, T, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
     return TORBI_HIP_OK;
+}
+
+int torbi_hip_forward_backward(const float *observation, const int32_t *batch_frames, const float *transition,
+                               const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                               size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = fb_args_ok(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace,
+                              workspace_bytes, B, T, S);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    return fb_dense(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace, B, T, S, device,
+                    stream, nullptr);
+}
+
+size_t torbi_hip_forward_backward_counts_workspace_bytes(int B, int T, int S) {
+    return torbi_hip_forward_backward_workspace_bytes(B, T, S);
+}
+
+int torbi_hip_forward_backward_counts(const float *observation, const int32_t *batch_frames, const float *transition,
+                                      const float *initial, const float *item_weights, float *posterior_out,
+                                      float *loglik_out, float *counts_out, float *initial_counts_out, void *workspace,
+                                      size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    if (B > 0 && (!counts_out || !initial_counts_out)) return TORBI_HIP_EINVAL;
+    const int rc = fb_args_ok(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace,
+                              workspace_bytes, B, T, S);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const FbCounts counts{item_weights, counts_out, initial_counts_out};
+    return fb_dense(observation, batch_frames, transition, initial, posterior_out, loglik_out, workspace, B, T, S, device,
+                    stream, &counts);
 }
 
 int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,

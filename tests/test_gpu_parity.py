@@ -1522,6 +1522,10 @@ def test_a_large_host_batch_of_probabilities_is_logged_like_upstream(monkeypatch
     again = torbi_amd.from_probabilities(probs, frames, trans, gpu=0).cpu()
     torch.cuda.synchronize()
     assert torch.equal(again, want) and slabs.pool(None).held_bytes() == grown    # ... and was used again
+    for _ in range(2):                                  # state_posteriors takes its log the same way and gives it back
+        torbi_amd.state_posteriors(probs, frames, trans, gpu=0)
+        torch.cuda.synchronize()
+        assert slabs.pool(None).held_bytes() == grown and torch.equal(probs, keep)
     monkeypatch.setattr(core, 'HOST_LOG_POOL_BYTES', 1 << 40)
     assert torch.equal(torbi_amd.from_probabilities(probs, frames, trans, gpu=0).cpu(), want)
     assert torch.equal(torbi_amd.from_probabilities(probs[:, ::2], frames.clamp(max=15), trans, gpu=0).cpu(),

@@ -146,6 +146,47 @@ def test_defaults_and_probabilities_match_from_probabilities_preprocessing():
     close((g2.numpy().astype(np.float64), L2.numpy().astype(np.float64)), want2, [T] * B)
 
 
+def _model_entry(entry, obs, trans, init, log_probs):
+    """One call of an entry point that prepares its inputs like from_probabilities (gpu=None); its outputs as a list."""
+    B, _, S = obs.shape
+    if entry == 'from_probabilities':
+        return [torbi_amd.from_probabilities(obs, None, trans, init, log_probs=log_probs)]
+    if entry == 'StreamDecoder':
+        dec = torbi_amd.StreamDecoder(B, S, trans, init, log_probs=log_probs, gpu=None)
+        return dec.push(obs) + dec.flush()
+    return list(getattr(torbi_amd, entry)(obs, None, trans, init, log_probs=log_probs))
+
+
+@pytest.mark.parametrize('entry,log_probs,written', [('from_probabilities', True, True),
+                                                     ('from_probabilities', False, False),
+                                                     ('StreamDecoder', True, False), ('state_posteriors', True, False),
+                                                     ('expected_counts', True, False)])
+def test_only_from_probabilities_writes_the_callers_observation(entry, log_probs, written):
+    """from_probabilities takes a float32 log observation on the compute device through the epsilon round trip in place,
+    like upstream; the other entry points work on a copy."""
+    obs, trans, init = (torch.from_numpy(x) for x in synth.problem(2, 6, 5, seed=21))
+    obs[0, 0, 0] = -math.inf                          # log(exp(x) + tiny) != x here
+    if not log_probs:
+        obs, trans, init = obs.exp(), trans.exp(), init.exp()
+    kept = obs.clone()
+    _model_entry(entry, obs, trans, init, log_probs)
+    assert torch.equal(obs, kept) != written
+
+
+@pytest.mark.parametrize('entry', ['from_probabilities', 'StreamDecoder', 'state_posteriors', 'expected_counts'])
+def test_a_float64_initial_is_cast_except_by_from_probabilities(entry):
+    """from_probabilities hands a float64 initial to the operator, which rejects it (like upstream); the other entry
+    points cast it to float32."""
+    obs, trans, init = (torch.from_numpy(x) for x in synth.problem(3, 8, 6, seed=22))
+    if entry == 'from_probabilities':
+        with pytest.raises(RuntimeError, match='initial'):
+            _model_entry(entry, obs, trans, init.double(), True)
+        return
+    got = _model_entry(entry, obs, trans, init.double(), True)
+    want = _model_entry(entry, obs, trans, init, True)
+    assert len(got) == len(want) and all(torch.equal(g, w) for g, w in zip(got, want))
+
+
 def test_ragged_and_out_of_range_frames():
     B, T, S = 4, 9, 6
     obs, trans, init = synth.problem(B, T, S, seed=9)

@@ -10,6 +10,8 @@ import os
 import shutil
 import subprocess
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 SOURCE = os.path.join(_HERE, 'csrc', 'torbi_hip.hip')
@@ -169,6 +171,20 @@ def check(code, what='torbi_hip call'):
     if code != 0:
         msg = load().torbi_hip_error_string(code)
         raise TorbiHipError(f'{what} failed with code {code}: {msg.decode() if msg else "?"}')
+
+
+def launch(device, need=None, workspace=None):
+    """What a C entry that runs on HIP `device` takes besides its tensors: (workspace, device index, current stream as
+    c_void_p).  With `need` bytes the workspace is the caller's, checked, or a fresh uint8 tensor; without, None."""
+    import torch
+    if need is not None:
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+        elif (workspace.device != device or workspace.dtype != torch.uint8 or workspace.numel() < need
+              or not workspace.is_contiguous()):
+            raise RuntimeError(f'workspace must be a contiguous uint8 tensor of >= {need} bytes on {device}')
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    return workspace, index, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def build_cpu(force=False, verbose=False):

@@ -4,15 +4,15 @@ Same function names, argument order, defaults and return conventions as the refe
 decode itself runs on an MI355X through `torbi_amd.decode` (C ABI, include/torbi_hip.h).
 Differences that follow from "GPU only" are stated in each docstring and in INTEGRATION.md.
 """
-import math
 import os
 from typing import Dict, List, Optional, Union
 
 import torch
 
 from . import data as _data
-from . import timer
-from .viterbi import decode, decode_uniform, epsilon_clamp_, log_epsilon_clamp, uniform_supported
+from . import inputs, timer
+from .inputs import _prepared_transition
+from .viterbi import decode, decode_cpu, decode_uniform, uniform_supported
 
 # reference torbi/config/defaults.py:80,83
 BATCH_SIZE = 512
@@ -41,85 +41,8 @@ RING_CHUNKS = int(os.environ.get('TORBI_RING_CHUNKS', '4'))
 # pass in place in the device slab; False = pinned batch -> from_probabilities' own device move, log and clamp (rounds 2-5)
 STAGE_PROBABILITIES = os.environ.get('TORBI_STAGE_PROBABILITIES', '1') != '0'
 RING_CHUNK_BYTES = int(os.environ.get('TORBI_RING_CHUNK_MB', '256')) << 20
-
-
-def _compute_device(gpu):
-    if gpu == 'mps':
-        raise RuntimeError('the MPS backend of the reference is out of scope on MI355X')
-    if not torch.cuda.is_available():
-        raise RuntimeError(
-            f'from_probabilities(gpu={gpu!r}) needs a HIP device and PyTorch-ROCm reports none; there is no CPU '
-            'fallback for a GPU request (gpu=None selects the CPU operator, like upstream)')
-    return torch.device(f'cuda:{gpu}')
-
-
-def _from_probabilities_cpu(observation, batch_frames, transition, initial, log_probs, num_threads):
-    """`gpu=None`: the reference's CPU route (torbi/core.py:145-201 with device = 'cpu'), decoded by the host twin of
-    the operator (include/torbi_cpu.h).  Same steps in the same order, materialised uniform defaults included."""
-    from .viterbi import decode_cpu
-    batch, frames, states = observation.shape
-    device = torch.device('cpu')
-    tiny = torch.finfo(torch.float32).tiny
-    if batch_frames is None:
-        batch_frames = torch.full((batch,), frames, dtype=torch.int32, device=device)
-    batch_frames = batch_frames.to(dtype=torch.int32, device=device)
-    if initial is None:
-        initial = torch.full((states,), math.log((1. / states) + tiny), dtype=torch.float32, device=device)
-    else:
-        if not log_probs:
-            initial = torch.log(initial)
-        initial = initial.to(device)
-    if transition is None:
-        transition = torch.full((states, states), math.log(1. / states), dtype=torch.float32, device=device)
-    else:
-        if not log_probs:
-            transition = torch.log(transition)
-        transition = transition.to(device)
-    if not log_probs:
-        observation = torch.log(observation)
-    observation = observation.to(device=device, dtype=torch.float32)
-    torch.exp_(observation)
-    observation += tiny
-    torch.log_(observation)
-    with timer.context('torbi'):
-        return decode_cpu(observation, batch_frames, transition, initial, num_threads=num_threads)
-
-
-def _prepared_transition(transition: torch.Tensor, log_probs: bool, device) -> torch.Tensor:
-    """log() (unless `log_probs`) and device move of the transition matrix (core.py:181-187), remembered with the
-    caller's tensor (object and version, torbi_amd/state.py): repeated calls with one matrix then hand torbi_amd.decode
-    the SAME device tensor, which is what its structure look and path measurements hang off."""
-    from . import state
-    kept = state.notes(transition)             # None under torch.inference_mode(): nothing to remember it by
-    key = ('prepared', bool(log_probs), str(device))
-    if kept is not None and key in kept:
-        return kept[key]
-    prepared = (transition if log_probs else torch.log(transition)).to(device)
-    if kept is not None:
-        kept[key] = prepared
-    return prepared
-
-
-# batches of host probabilities from this size on take their log() into a pooled pinned buffer (_host_log)
+# batches of host probabilities from this size on take their log() into a pooled pinned buffer (inputs._host_log)
 HOST_LOG_POOL_BYTES = 32 << 20
-
-
-def _host_log(observation: torch.Tensor) -> torch.Tensor:
-    """`torch.log(observation)` where the observation lives, like upstream (core.py:189-191: the log is taken BEFORE the device
-    move, so a host batch is logged by the host and the operator sees the host's roundings).  A large float32 host batch is
-    logged into a pinned buffer of the process-wide pool (torbi_amd/slabs.py; `release_job_memory()` frees it): the same
-    kernel, the same bits, but no fresh 1.5 GB of first-touched pages per call and an asynchronous copy at the host link's rate
-    behind it -- 512 x 500 x 1440: 398 -> ~65 ms per call."""
-    nbytes = observation.numel() * 4
-    if (observation.device.type != 'cpu' or observation.dtype != torch.float32 or nbytes < HOST_LOG_POOL_BYTES
-            or observation.requires_grad or not torch.cuda.is_available()):          # (`out=` is not for tensors in a graph)
-        return torch.log(observation)
-    from . import slabs
-    slab = slabs.pool(None).take(nbytes, limit=2)
-    out = slab[:nbytes].view(torch.float32).view(observation.shape)
-    torch.log(observation, out=out)
-    out.torbi_slab = slab
-    return out
 
 
 def from_probabilities(
@@ -157,40 +80,30 @@ def from_probabilities(
     Returns:
         (batch, frames) int32 indices of the most likely state sequence of every item
     """
-    if gpu is None:
-        return _from_probabilities_cpu(observation, batch_frames, transition, initial, log_probs, num_threads)
     batch, frames, states = observation.shape
-    device = _compute_device(gpu)
-    tiny = torch.finfo(torch.float32).tiny
-
-    if batch_frames is None:
-        batch_frames = torch.full((batch,), frames, dtype=torch.int32, device=device)
-    batch_frames = batch_frames.to(dtype=torch.int32, device=device)
+    device = inputs._compute_device(gpu)
+    batch_frames = inputs.frames(batch_frames, batch, frames, device)
 
     # `_model` (from_dataloader): initial/transition are the same objects for every batch, so their
     # log(), device move and (in torbi_amd.decode) structure look are done once, not per batch
     if _model is not None and 'initial' in _model:
         initial, transition, uniform = _model['initial'], _model['transition'], _model['uniform']
     else:
-        # Default to uniform initial probabilities (core.py:161-166)
-        if initial is None:
-            initial = torch.full(
-                (states,), math.log((1. / states) + tiny), dtype=torch.float32, device=device)
-        else:
-            if not log_probs:
-                initial = torch.log(initial)
-            initial = initial.to(device)
-
-        # Default to uniform transition probabilities (core.py:175-180).  The reference
-        # materialises torch.full((S, S), log(1/S)); a matrix of identical entries is decoded by the
-        # O(S)-per-timestep entry point instead, with identical results (decode_uniform).
-        uniform = None
-        if transition is None:
-            uniform = float(torch.tensor(math.log(1. / states), dtype=torch.float32))
-        else:
-            transition = _prepared_transition(transition, log_probs, device)
+        # The reference materialises torch.full((S, S), log(1/S)) for a missing transition (core.py:175-180); on the GPU
+        # a matrix of identical entries is decoded by the O(S)-per-timestep entry point instead, with identical results
+        # (decode_uniform)
+        transition, uniform, initial = inputs.model(transition, initial, log_probs, states, device)
         if _model is not None:
             _model.update(initial=initial, transition=transition, uniform=uniform)
+
+    if gpu is None:
+        # the reference's CPU route (core.py:145-201 with device = 'cpu') on the host twin of the operator
+        # (include/torbi_cpu.h), the uniform matrix materialised like upstream
+        observation = inputs.observation(observation, log_probs, device, in_place=True)
+        if transition is None:
+            transition = torch.full((states, states), uniform, dtype=torch.float32)
+        with timer.context('torbi'):
+            return decode_cpu(observation, batch_frames, transition, initial, num_threads=num_threads)
 
     # The whole default call -- probabilities in, no transition given -- as ONE pass over the observations: log(), the
     # epsilon round trip and the O(S)-per-frame decode in one kernel (same values, same indices; csrc/uniform_decode.hpp)
@@ -199,32 +112,12 @@ def from_probabilities(
         with timer.context('torbi'):
             return decode_uniform(observation, batch_frames, uniform, initial, probabilities=True)
 
-    # Ensure observation probabilities are in log space (core.py:189-191).  Probabilities that already live on the
-    # compute device go through log() and the epsilon round trip below in one pass (same values, tested bitwise)
-    # (`_prepared`, the many-file driver: the batch is on the device, float32, and has been through both steps already --
-    # in place in its staging slab, _Staging.decode)
-    clamped = observation if _prepared else None
-    if not log_probs and not _prepared:
-        if observation.device == device:
-            clamped = log_epsilon_clamp(observation)
-        if clamped is None:
-            observation = _host_log(observation)
-    # non_blocking: a pinned host batch (data.loader) is copied asynchronously, so the copy of batch k+1
-    # runs under the decode of batch k; pageable sources fall back to the synchronous path by themselves
-    on_host = observation
-    observation = observation.to(device=device, dtype=torch.float32, non_blocking=True)
-    if getattr(on_host, 'torbi_slab', None) is not None:        # (_host_log's pooled buffer: free again once the copy has left)
-        from . import slabs
-        left = torch.cuda.Event()
-        left.record(torch.cuda.current_stream(device))
-        slabs.pool(None).give(on_host.torbi_slab, left)
-
-    # Add epsilon for stability (core.py:193-197; in place, like the reference): exp_, += tiny,
-    # log_ as ONE elementwise pass on the device
-    if clamped is not None:
-        observation = clamped
-    else:
-        epsilon_clamp_(observation)
+    # log() and the epsilon round trip, in place like the reference (core.py:189-197).  non_blocking: a pinned host batch
+    # (data.loader) is copied asynchronously, so the copy of batch k+1 runs under the decode of batch k; pageable sources
+    # fall back to the synchronous path by themselves.  (`_prepared`, the many-file driver: the batch is on the device,
+    # float32, and has been through both steps already -- in place in its staging slab, _Staging.decode)
+    if not _prepared:
+        observation = inputs.observation(observation, log_probs, device, in_place=True, non_blocking=True)
 
     # Decode, inside the same timing scope as upstream's (core.py:200-206; torbi_amd/timer.py)
     with timer.context('torbi'):

@@ -16,9 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
-from .core import _compute_device, _host_log, _prepared_transition
-from .viterbi import epsilon_clamp_, log_epsilon_clamp
+from . import _lib, inputs
 
 
 def forward_backward_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -26,59 +24,56 @@ def forward_backward_workspace_bytes(B: int, T: int, S: int) -> int:
     return int(_lib.load().torbi_hip_forward_backward_workspace_bytes(B, T, S))
 
 
-def _check_shapes(observation, batch_frames, transition, initial):
-    """(B, T, S) of a call; raises before anything is launched or computed unless batch_frames is (B,), transition (S, S)
-    and initial (S,) (None: the default of that argument).  The kernels read exactly those extents."""
-    if observation.dim() != 3:
-        raise RuntimeError(f'observation must have shape (batch, frames, states); got {tuple(observation.shape)}')
-    B, T, S = observation.shape
-    if T < 1 or S < 1:
-        raise RuntimeError('observation needs at least one frame and one state')
-    if batch_frames is not None and tuple(batch_frames.shape) != (B,):
-        raise RuntimeError(f'batch_frames must have shape ({B},); got {tuple(batch_frames.shape)}')
-    if transition is not None and tuple(transition.shape) != (S, S):
-        raise RuntimeError(f'transition must have shape ({S}, {S}); got {tuple(transition.shape)}')
-    if initial is not None and tuple(initial.shape) != (S,):
-        raise RuntimeError(f'initial must have shape ({S},); got {tuple(initial.shape)}')
-    return B, T, S
+def _operands(what, observation, batch_frames, transition, initial, item_weights=None):
+    """The front of the operator level (`forward_backward`, `forward_backward_counts`): every check before anything runs,
+    then the observation as contiguous float32 on its HIP device (the current one for a host tensor) and the frames."""
+    if transition is None or initial is None:
+        raise RuntimeError(f'{what} needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    if item_weights is not None and tuple(item_weights.shape) != (B,):
+        raise RuntimeError(f'item_weights must have shape ({B},); got {tuple(item_weights.shape)}')
+    if not torch.cuda.is_available():
+        raise RuntimeError(f'torbi_amd.{what} needs a HIP device (state_posteriors / expected_counts with gpu=None run on '
+                           'the CPU)')
+    device = observation.device if observation.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    return observation.to(device=device, dtype=torch.float32).contiguous(), inputs.frames(batch_frames, B, T, device)
 
 
-def _frames(batch_frames, B, T, device):
-    if batch_frames is None:
-        return torch.full((B,), T, dtype=torch.int32, device=device)
-    return batch_frames.to(device=device, dtype=torch.int32).contiguous()
-
-
-def _run(observation, batch_frames, transition, uniform, initial, workspace):
-    """One call of the HIP route on the device of `observation` (float32, contiguous, log space)."""
-    B, T, S = _check_shapes(observation, batch_frames, transition, initial)
+def _run(observation, frames, transition, uniform, initial, workspace=None, counts=False, item_weights=None):
+    """One call of the HIP route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
+    there: (posterior, log_likelihood), and with `counts` (torbi_hip_forward_backward_counts, dense route only) also
+    (transition_counts, initial_counts) weighted by `item_weights` (None = all ones)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
     device = observation.device
     lib = _lib.load()
-    posterior = torch.empty((B, T, S), dtype=torch.float32, device=device)
-    loglik = torch.empty((B,), dtype=torch.float32, device=device)
+    out = [torch.empty((B, T, S), dtype=torch.float32, device=device),
+           torch.empty((B,), dtype=torch.float32, device=device)]
+    if counts:
+        out += [torch.zeros((S, S), dtype=torch.float32, device=device),
+                torch.zeros((S,), dtype=torch.float32, device=device)]
     if B == 0:
-        return posterior, loglik
-    need = lib.torbi_hip_forward_backward_workspace_bytes(B, T, S)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-    elif (workspace.device != device or workspace.dtype != torch.uint8 or workspace.numel() < need
-          or not workspace.is_contiguous()):
-        raise RuntimeError(f'workspace must be a contiguous uint8 tensor of >= {need} bytes on {device}')
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    frames = batch_frames.to(device=device, dtype=torch.int32).contiguous()
+        return tuple(out)
+    need = (lib.torbi_hip_forward_backward_counts_workspace_bytes if counts
+            else lib.torbi_hip_forward_backward_workspace_bytes)(B, T, S)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
     init = initial.to(device=device, dtype=torch.float32).contiguous()
-    if uniform is None:
+    head = (observation.data_ptr(), frames.data_ptr())
+    tail = tuple(t.data_ptr() for t in out) + (workspace.data_ptr(), workspace.numel(), B, T, S, index, stream)
+    if uniform is not None:
+        _lib.check(lib.torbi_hip_forward_backward_uniform(*head, ctypes.c_float(uniform), init.data_ptr(), *tail),
+                   'torbi_hip_forward_backward_uniform')
+    elif not counts:
         trans = transition.to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(lib.torbi_hip_forward_backward(
-            observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(), posterior.data_ptr(),
-            loglik.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index, stream), 'torbi_hip_forward_backward')
+        _lib.check(lib.torbi_hip_forward_backward(*head, trans.data_ptr(), init.data_ptr(), *tail),
+                   'torbi_hip_forward_backward')
     else:
-        _lib.check(lib.torbi_hip_forward_backward_uniform(
-            observation.data_ptr(), frames.data_ptr(), ctypes.c_float(uniform), init.data_ptr(), posterior.data_ptr(),
-            loglik.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index, stream),
-            'torbi_hip_forward_backward_uniform')
-    return posterior, loglik
+        trans = transition.to(device=device, dtype=torch.float32).contiguous()
+        weights = None if item_weights is None else item_weights.to(device=device, dtype=torch.float32).contiguous()
+        _lib.check(lib.torbi_hip_forward_backward_counts(*head, trans.data_ptr(), init.data_ptr(),
+                                                         None if weights is None else weights.data_ptr(), *tail),
+                   'torbi_hip_forward_backward_counts')
+    return tuple(out)
 
 
 def forward_backward(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -96,14 +91,8 @@ def forward_backward(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     Returns:
         (posterior (B, T, S) float32, log_likelihood (B,) float32) on the device; rows t >= F_b are 0
     """
-    if transition is None or initial is None:
-        raise RuntimeError('forward_backward needs a transition matrix and an initial distribution')
-    B, T, S = _check_shapes(observation, batch_frames, transition, initial)
-    if not torch.cuda.is_available():
-        raise RuntimeError('torbi_amd.forward_backward needs a HIP device (state_posteriors(gpu=None) runs on the CPU)')
-    device = observation.device if observation.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    obs = observation.to(device=device, dtype=torch.float32).contiguous()
-    return _run(obs, _frames(batch_frames, B, T, device), transition, None, initial, workspace)
+    obs, frames = _operands('forward_backward', observation, batch_frames, transition, initial)
+    return _run(obs, frames, transition, None, initial, workspace)
 
 
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -112,70 +101,32 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     """P(state_t = j | all frames) of every frame, and log P(observations) of every item.
 
     Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
-    transition log(1/S)), and the inputs go through the same log() and epsilon round trip, so the model is bit for bit the
-    one `from_probabilities` decodes.  `transition=None` takes the closed form of a uniform matrix (beta is constant over
-    states).  `gpu` is a HIP device index; None computes in float64 on the CPU.  The caller's tensors are not written.
+    transition log(1/S)), and the inputs go through the same log() and epsilon round trip (torbi_amd/inputs.py), so the
+    model is bit for bit the one `from_probabilities` decodes.  `transition=None` takes the closed form of a uniform matrix
+    (beta is constant over states).  `gpu` is a HIP device index; None computes in float64 on the CPU.  The caller's
+    tensors are not written.
 
     Returns:
         (posterior (batch, frames, states) float32, log_likelihood (batch,) float32) on the compute device.  Rows
         t >= batch_frames[b] are 0; an item of total probability 0 has log-likelihood -inf and NaN rows, an item that reads
         a NaN or +inf has NaN for both.
     """
-    B, T, S = _check_shapes(observation, batch_frames, transition, initial)
-    device = torch.device('cpu') if gpu is None else _compute_device(gpu)
-    tiny = torch.finfo(torch.float32).tiny
-    frames = _frames(batch_frames, B, T, device)
-    # from_probabilities' defaults and preprocessing (core.py), element by element
-    if initial is None:
-        initial = torch.full((S,), math.log((1. / S) + tiny), dtype=torch.float32, device=device)
-    else:
-        if not log_probs:
-            initial = torch.log(initial)
-        initial = initial.to(device)
-    uniform = None
-    if transition is None:
-        uniform = float(torch.tensor(math.log(1. / S), dtype=torch.float32))
-    elif gpu is None:
-        transition = (transition if log_probs else torch.log(transition)).to(device)
-    else:
-        transition = _prepared_transition(transition, log_probs, device)
-    obs = _observation(observation, log_probs, device, gpu is None)
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    device = inputs._compute_device(gpu)
+    frames = inputs.frames(batch_frames, B, T, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
-        return _host(obs, frames, transition, uniform, initial.to(torch.float32))
-    return _run(obs, frames, transition, uniform, initial, None)
+        gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
+        return gamma.to(torch.float32), L.to(torch.float32)
+    return _run(obs, frames, transition, uniform, initial)
 
 
-def _observation(observation, log_probs, device, host):
-    """log() unless `log_probs`, the move to `device` as float32 and the epsilon round trip, on a copy."""
-    tiny = torch.finfo(torch.float32).tiny
-    if host:
-        x = observation if log_probs else torch.log(observation)
-        x = x.to(device=device, dtype=torch.float32)
-        if x.data_ptr() == observation.data_ptr():
-            x = x.clone()
-        torch.exp_(x)
-        x += tiny
-        torch.log_(x)
-        return x.contiguous()
-    clamped = None
-    if not log_probs:
-        if observation.device == device:
-            clamped = log_epsilon_clamp(observation.contiguous())
-        if clamped is None:
-            observation = _host_log(observation)
-    if clamped is not None:
-        return clamped
-    x = observation.to(device=device, dtype=torch.float32)
-    if x.data_ptr() == observation.data_ptr():
-        x = x.clone()
-    x = x.contiguous()
-    epsilon_clamp_(x)
-    return x
-
-
-def _host(obs, frames, transition, uniform, initial):
-    """gpu=None: the scaled recurrence of the HIP route in float64 (torch CPU ops), returned as float32."""
-    B, T, S = _check_shapes(obs, frames, transition, initial)
+def _host(obs, frames, transition, uniform, initial, weights=None, counts=False):
+    """The scaled recurrence of the HIP route in float64 with torch CPU ops: (gamma, L, X, I), float64.  `uniform` (not
+    None) takes the closed form of a uniform transition matrix.  X (S, S) [next, prev] and I (S,), the expected counts
+    weighted by `weights` (None = all ones), are computed only with `counts` (dense route), else None."""
+    B, T, S = inputs.check_shapes(obs, frames, transition, initial)
     o = obs.to(torch.float64)
     pi = initial.to(torch.float64)
     F = frames.to(torch.int64).clamp(1, T)
@@ -205,6 +156,7 @@ def _host(obs, frames, transition, uniform, initial):
             c[:, t] = alpha[:, t].sum(dim=1)
         L = torch.where(valid, torch.log(c) + m, torch.zeros_like(m)).sum(dim=1)
         gamma = torch.zeros((B, T, S), dtype=torch.float64)
+        W = torch.zeros((B, T, S), dtype=torch.float64) if counts else None        # every w_t, for the counts
         w = torch.zeros((B, S), dtype=torch.float64)
         for t in range(T - 1, -1, -1):
             last = (F - 1 == t)[:, None]
@@ -212,8 +164,20 @@ def _host(obs, frames, transition, uniform, initial):
             ct = c[:, t, None]
             gamma[:, t] = alpha[:, t] * beta / ct
             w = torch.where((t <= F - 1)[:, None], e[:, t] * beta / ct, w)
+            if counts:
+                W[:, t] = w
     L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
     bad = ~torch.isfinite(L)
     gamma = torch.where(valid[..., None], gamma, torch.zeros_like(gamma))
     gamma = torch.where(bad[:, None, None] & valid[..., None], torch.full_like(gamma, math.nan), gamma)
-    return gamma.to(torch.float32), L.to(torch.float32)
+    if not counts:
+        return gamma, L, None, None
+    g = torch.ones(B, dtype=torch.float64) if weights is None else weights.detach().to('cpu', torch.float64)
+    live = (g != 0) & ~bad                                                          # skipped, not multiplied
+    pair = valid[:, 1:] & live[:, None]                                             # (B, T - 1): pair t = 1 .. F - 1
+    zero = torch.zeros((), dtype=torch.float64)
+    Wp = torch.where(pair[..., None], W[:, 1:], zero)
+    Ap = torch.where(pair[..., None], alpha[:, :-1] / c[:, :-1, None] * g[:, None, None], zero)
+    X = E * torch.einsum('btj,bti->ji', Wp, Ap)
+    I = torch.where(live[:, None], g[:, None] * gamma[:, 0], zero).sum(dim=0)
+    return gamma, L, X, I

@@ -6,16 +6,13 @@ c: no later observation can change the path up to c any more.  `push` returns, p
 included).  The HIP route is csrc/stream.hpp behind torbi_hip_stream_* (include/torbi_hip.h); `gpu=None` runs the same
 decoder on the host with torch CPU ops.  STREAM.md has the layout and the kernels.
 """
-import ctypes
 import math
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
-from .core import _compute_device, _host_log, _prepared_transition
-from .viterbi import epsilon_clamp_, log_epsilon_clamp
+from . import _lib, inputs
 
 # ring slots of a new decoder; the ring doubles when a push needs more
 INITIAL_CAPACITY = 16
@@ -43,19 +40,11 @@ class StreamDecoder:
             raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
         self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
         S = self.states
-        self.device = torch.device('cpu') if gpu is None else _compute_device(gpu)
-        tiny = torch.finfo(torch.float32).tiny
-        # the steps of from_probabilities (core.py), element by element: chunking cannot change a bit
-        if initial is None:
-            initial = torch.full((S,), math.log((1. / S) + tiny), dtype=torch.float32, device=self.device)
-        elif not log_probs:
-            initial = torch.log(initial)
+        self.device = inputs._compute_device(gpu)
+        # the model of from_probabilities (torbi_amd/inputs.py): chunking cannot change a bit
+        transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
         if transition is None:
-            transition = torch.full((S, S), math.log(1. / S), dtype=torch.float32, device=self.device)
-        elif gpu is None:
-            transition = transition if log_probs else torch.log(transition)
-        else:
-            transition = _prepared_transition(transition, log_probs, self.device)
+            transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
         self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
         self.transition = transition.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(self.transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
@@ -99,7 +88,7 @@ class StreamDecoder:
             f = torch.as_tensor(frames).detach().to('cpu', torch.int64).reshape(-1).numpy().copy()
             if f.shape[0] != self.batch or (f < 0).any() or (f > Tc).any():
                 raise ValueError(f'frames must hold {self.batch} counts in 0 .. {Tc}')
-        obs = self._prepare(observation)
+        obs = inputs.observation(observation, self.log_probs, self.device)
         if self.gpu is None:
             return self._push_host(obs, f)
         return self._push_device(obs, f)
@@ -118,38 +107,6 @@ class StreamDecoder:
         for k in set(items):
             self._frames[k] = self._base[k] = 0
         return [rest[k] for k in items]
-
-    # ------------------------------------------------------------------ inputs
-    def _prepare(self, observation: torch.Tensor) -> torch.Tensor:
-        """from_probabilities' log() and epsilon round trip (core.py), on a copy: the caller's tensor is not written."""
-        tiny = torch.finfo(torch.float32).tiny
-        if self.gpu is None:
-            x = observation if self.log_probs else torch.log(observation)
-            x = x.to(device=self.device, dtype=torch.float32)
-            if x.data_ptr() == observation.data_ptr():
-                x = x.clone()
-            torch.exp_(x)
-            x += tiny
-            torch.log_(x)
-            return x.contiguous()
-        clamped = None
-        if not self.log_probs:
-            if observation.device == self.device:
-                clamped = log_epsilon_clamp(observation.contiguous())
-            if clamped is None:
-                observation = _host_log(observation)
-        if clamped is not None:
-            return clamped
-        on_host = observation
-        x = observation.to(device=self.device, dtype=torch.float32).contiguous()
-        if getattr(on_host, 'torbi_slab', None) is not None:        # (_host_log's pooled buffer: free once the copy has left)
-            from . import slabs
-            left = torch.cuda.Event()
-            left.record(torch.cuda.current_stream(self.device))
-            slabs.pool(None).give(on_host.torbi_slab, left)
-        if x.data_ptr() == observation.data_ptr():
-            x = x.clone()
-        return epsilon_clamp_(x)
 
     # ------------------------------------------------------------------ host route
     def _row(self, prev: torch.Tensor, obs_row: torch.Tensor) -> torch.Tensor:
@@ -279,12 +236,12 @@ class StreamDecoder:
         info = self._info(pending, f)
         out = torch.empty((B, max(1, need)), dtype=torch.int32, device=self.device)
         counts = torch.empty(B, dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _, index, stream = _lib.launch(self.device)
         Tc = int(obs.shape[1])
         _lib.check(self._lib.torbi_hip_stream_push(
             obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
             self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
-            counts.data_ptr(), B, S, self.device.index or 0, ctypes.c_void_p(stream)), 'torbi_hip_stream_push')
+            counts.data_ptr(), B, S, index, stream), 'torbi_hip_stream_push')
         got = self._results(out, counts, 'torbi_hip_stream_push')
         self._frames += f
         self._base += got
@@ -298,10 +255,10 @@ class StreamDecoder:
         info = self._info(pending, marks)
         out = torch.empty((B, max(1, int(pending.max()))), dtype=torch.int32, device=self.device)
         counts = torch.empty(B, dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _, index, stream = _lib.launch(self.device)
         _lib.check(self._lib.torbi_hip_stream_flush(
             info.data_ptr(), self.transition.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity,
-            out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, self.device.index or 0, ctypes.c_void_p(stream)),
+            out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, index, stream),
             'torbi_hip_stream_flush')
         got = self._results(out, counts, 'torbi_hip_stream_flush')
         return {k: out[k, :got[k]] for k in items}

@@ -11,15 +11,13 @@ states of one previous state).  The HIP route is csrc/counts.hpp behind torbi_hi
 (include/torbi_hip.h), fed by the passes of `forward_backward`; `gpu=None` and CPU tensors run the same scaled recurrence in
 float64 with torch CPU ops.  POSTERIOR.md ("Expected counts") has the contract, the kernels and the numbers.
 """
-import ctypes
 import math
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
-from .core import _compute_device, _prepared_transition
-from .posterior import _check_shapes, _frames, _observation
+from . import _lib, inputs
+from .posterior import _host, _operands, _run
 
 
 def expected_counts_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -45,45 +43,8 @@ def forward_backward_counts(observation: torch.Tensor, batch_frames: Optional[to
         (posterior (B, T, S), log_likelihood (B,), transition_counts (S, S) [next, prev], initial_counts (S,)), float32 on
         the device; posterior and log_likelihood are bit for bit those of `forward_backward`
     """
-    if transition is None or initial is None:
-        raise RuntimeError('forward_backward_counts needs a transition matrix and an initial distribution')
-    B, T, S = _check_shapes(observation, batch_frames, transition, initial)
-    if item_weights is not None and tuple(item_weights.shape) != (B,):
-        raise RuntimeError(f'item_weights must have shape ({B},); got {tuple(item_weights.shape)}')
-    if not torch.cuda.is_available():
-        raise RuntimeError('torbi_amd.forward_backward_counts needs a HIP device (expected_counts(gpu=None) runs on the CPU)')
-    device = observation.device if observation.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    obs = observation.to(device=device, dtype=torch.float32).contiguous()
-    return _run_counts(obs, _frames(batch_frames, B, T, device), transition, initial, item_weights, workspace)
-
-
-def _run_counts(observation, frames, transition, initial, item_weights, workspace):
-    B, T, S = observation.shape
-    device = observation.device
-    lib = _lib.load()
-    posterior = torch.empty((B, T, S), dtype=torch.float32, device=device)
-    loglik = torch.empty((B,), dtype=torch.float32, device=device)
-    counts = torch.zeros((S, S), dtype=torch.float32, device=device)
-    initial_counts = torch.zeros((S,), dtype=torch.float32, device=device)
-    if B == 0:
-        return posterior, loglik, counts, initial_counts
-    need = lib.torbi_hip_forward_backward_counts_workspace_bytes(B, T, S)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-    elif (workspace.device != device or workspace.dtype != torch.uint8 or workspace.numel() < need
-          or not workspace.is_contiguous()):
-        raise RuntimeError(f'workspace must be a contiguous uint8 tensor of >= {need} bytes on {device}')
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    weights = None if item_weights is None else item_weights.to(device=device, dtype=torch.float32).contiguous()
-    _lib.check(lib.torbi_hip_forward_backward_counts(
-        observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
-        None if weights is None else weights.data_ptr(), posterior.data_ptr(), loglik.data_ptr(), counts.data_ptr(),
-        initial_counts.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index, stream),
-        'torbi_hip_forward_backward_counts')
-    return posterior, loglik, counts, initial_counts
+    obs, frames = _operands('forward_backward_counts', observation, batch_frames, transition, initial, item_weights)
+    return _run(obs, frames, transition, None, initial, workspace, counts=True, item_weights=item_weights)
 
 
 def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -100,101 +61,42 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
         transition_counts[j, i] is the expected number of steps from state i to state j; one M-step divides each column by
         its sum.
     """
-    B, T, S = _check_shapes(observation, batch_frames, transition, initial)
-    device = torch.device('cpu') if gpu is None else _compute_device(gpu)
-    tiny = torch.finfo(torch.float32).tiny
-    frames = _frames(batch_frames, B, T, device)
-    # state_posteriors' defaults and preprocessing (posterior.py), element by element
-    if initial is None:
-        initial = torch.full((S,), math.log((1. / S) + tiny), dtype=torch.float32, device=device)
-    else:
-        if not log_probs:
-            initial = torch.log(initial)
-        initial = initial.to(device)
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    device = inputs._compute_device(gpu)
+    frames = inputs.frames(batch_frames, B, T, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
     if transition is None:
-        uniform = float(torch.tensor(math.log(1. / S), dtype=torch.float32))
         transition = torch.full((S, S), uniform, dtype=torch.float32, device=device)
-    elif gpu is None:
-        transition = (transition if log_probs else torch.log(transition)).to(device)
-    else:
-        transition = _prepared_transition(transition, log_probs, device)
-    obs = _observation(observation, log_probs, device, gpu is None)
+    obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         _, L, X, I = _host_counts(obs, frames, transition.to(torch.float32), initial.to(torch.float32), None)
         return X.to(torch.float32), I.to(torch.float32), L.to(torch.float32)
-    _, L, X, I = _run_counts(obs, frames, transition, initial, None, None)
+    _, L, X, I = _run(obs, frames, transition, None, initial, counts=True)
     return X, I, L
 
 
 def _host_counts(obs, frames, transition, initial, weights, counts=True):
-    """The scaled recurrence of `posterior._host` in float64, keeping every w_t: (gamma, L, X, I) in float64 (X and I None
-    unless `counts`).  The forward pass and L are those of `_host`, operation for operation."""
-    B, T, S = _check_shapes(obs, frames, transition, initial)
-    o = obs.to(torch.float64)
-    pi = initial.to(torch.float64)
-    F = frames.to(torch.int64).clamp(1, T)
-    t_index = torch.arange(T)
-    valid = t_index[None, :] < F[:, None]                                          # (B, T)
-    x = o.clone()
-    x[:, 0] += pi
-    m = torch.amax(x, dim=2)                                                        # NaN propagates
-    m = torch.where(m == -math.inf, torch.zeros_like(m), m)
-    e = torch.exp(x - m[..., None])
-    E = torch.exp(transition.to(torch.float64))                                     # [next, prev]
-    alpha = torch.zeros((B, T, S), dtype=torch.float64)
-    c = torch.zeros((B, T), dtype=torch.float64)
-    alpha[:, 0] = e[:, 0]
-    c[:, 0] = alpha[:, 0].sum(dim=1)
-    for t in range(1, T):
-        u = e[:, t] * (alpha[:, t - 1] @ E.T)
-        prev = c[:, t - 1, None]
-        alpha[:, t] = torch.where(prev == 0, u * 0., u / prev)
-        c[:, t] = alpha[:, t].sum(dim=1)
-    L = torch.where(valid, torch.log(c) + m, torch.zeros_like(m)).sum(dim=1)
-    gamma = torch.zeros((B, T, S), dtype=torch.float64)
-    W = torch.zeros((B, T, S), dtype=torch.float64)
-    w = torch.zeros((B, S), dtype=torch.float64)
-    for t in range(T - 1, -1, -1):
-        last = (F - 1 == t)[:, None]
-        beta = torch.where(last, torch.ones((B, S), dtype=torch.float64), w @ E)
-        ct = c[:, t, None]
-        gamma[:, t] = alpha[:, t] * beta / ct
-        w = torch.where((t <= F - 1)[:, None], e[:, t] * beta / ct, w)
-        W[:, t] = w
-    L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
-    bad = ~torch.isfinite(L)
-    gamma = torch.where(valid[..., None], gamma, torch.zeros_like(gamma))
-    gamma = torch.where(bad[:, None, None] & valid[..., None], torch.full_like(gamma, math.nan), gamma)
-    if not counts:
-        return gamma, L, None, None
-    g = torch.ones(B, dtype=torch.float64) if weights is None else weights.detach().to('cpu', torch.float64)
-    live = (g != 0) & ~bad                                                          # skipped, not multiplied
-    pair = valid[:, 1:] & live[:, None]                                             # (B, T - 1): pair t = 1 .. F - 1
-    zero = torch.zeros((), dtype=torch.float64)
-    Wp = torch.where(pair[..., None], W[:, 1:], zero)
-    Ap = torch.where(pair[..., None], alpha[:, :-1] / c[:, :-1, None] * g[:, None, None], zero)
-    X = E * torch.einsum('btj,bti->ji', Wp, Ap)
-    I = torch.where(live[:, None], g[:, None] * gamma[:, 0], zero).sum(dim=0)
-    return gamma, L, X, I
+    """The dense float64 route of `posterior._host` with the counts weighted by `weights` (None = all ones): (gamma, L, X,
+    I) in float64 (X and I None unless `counts`)."""
+    return _host(obs, frames, transition, None, initial, weights, counts)
 
 
 class _LogLikelihood(torch.autograd.Function):
     @staticmethod
     def forward(ctx, observation, batch_frames, transition, initial):
-        B, T, S = _check_shapes(observation, batch_frames, transition, initial)
+        B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
         ctx.dtypes = (observation.dtype, transition.dtype, initial.dtype)
         ctx.devices = (observation.device, transition.device, initial.device)
         if observation.is_cuda:
             device = observation.device
-            frames = _frames(batch_frames, B, T, device)
+            frames = inputs.frames(batch_frames, B, T, device)
             obs = observation.detach().to(dtype=torch.float32).contiguous()
             trans = transition.detach().to(device=device, dtype=torch.float32).contiguous()
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
-            from .posterior import _run
-            gamma, L = _run(obs, frames, trans, None, init, None)
+            gamma, L = _run(obs, frames, trans, None, init)
             ctx.save_for_backward(obs, frames, trans, init, gamma, L)
             return L
-        frames = _frames(batch_frames, B, T, torch.device('cpu'))
+        frames = inputs.frames(batch_frames, B, T, torch.device('cpu'))
         obs, trans, init = (v.detach().to(torch.float64) for v in (observation, transition, initial))
         gamma, L, _, _ = _host_counts(obs, frames, trans, init, None, counts=False)
         ctx.save_for_backward(obs, frames, trans, init, gamma, L)
@@ -212,7 +114,7 @@ class _LogLikelihood(torch.autograd.Function):
         if need_t or need_i:
             if need_t:
                 if obs.is_cuda:
-                    _, _, X, I = _run_counts(obs, frames, trans, init, g.contiguous(), None)
+                    _, _, X, I = _run(obs, frames, trans, None, init, counts=True, item_weights=g.contiguous())
                 else:
                     _, _, X, I = _host_counts(obs, frames, trans, init, g)
             else:

@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, state
+from . import _lib, inputs, state
 from .state import _version_of
 
 
@@ -24,28 +24,18 @@ def _require_gpu():
 
 
 def _check_inputs(observation, batch_frames, transition, initial):
-    if observation.dim() != 3:
-        raise RuntimeError(
-            f'observation must have shape (batch, frames, states); got {tuple(observation.shape)}')
-    B, T, S = observation.shape
-    if T < 1 or S < 1:
-        raise RuntimeError('observation needs at least one frame and one state')
+    """`inputs.check_shapes` and the operator's dtypes (transition None: a uniform matrix)."""
+    shape = inputs.check_shapes(observation, batch_frames, transition, initial)
     # dtype errors mirror what ATen's data_ptr<T>() raises in the reference operator
     # (torbi/csrc/cuda/viterbi.cu:203-215): fp32 scores, int32 lengths
     for name, tensor, dtype in (('observation', observation, torch.float32),
                                 ('transition', transition, torch.float32),
                                 ('initial', initial, torch.float32),
                                 ('batch_frames', batch_frames, torch.int32)):
-        if tensor.dtype != dtype:
+        if tensor is not None and tensor.dtype != dtype:
             raise RuntimeError(
                 f'expected scalar type {dtype} for {name} but found {tensor.dtype}')
-    if tuple(batch_frames.shape) != (B,):
-        raise RuntimeError(f'batch_frames must have shape ({B},); got {tuple(batch_frames.shape)}')
-    if tuple(transition.shape) != (S, S):
-        raise RuntimeError(f'transition must have shape ({S}, {S}); got {tuple(transition.shape)}')
-    if tuple(initial.shape) != (S,):
-        raise RuntimeError(f'initial must have shape ({S},); got {tuple(initial.shape)}')
-    return B, T, S
+    return shape
 
 
 def workspace_bytes(batch: int, frames: int, states: int) -> int:
@@ -379,22 +369,13 @@ def decode(
     indices = torch.empty((B, T), dtype=torch.int32, device=device)
     if B == 0:
         return indices.to(home)
-    need = lib.torbi_hip_workspace_bytes(B, T, S)
     own_scratch = workspace is None
-    if own_scratch:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
-    elif (workspace.device != device or workspace.dtype != torch.uint8
-          or workspace.numel() < need or not workspace.is_contiguous()):
-        raise RuntimeError(f'workspace must be a contiguous uint8 tensor of >= {need} bytes on {device}')
-
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(device).cuda_stream
+    workspace, index, stream = _lib.launch(device, lib.torbi_hip_workspace_bytes(B, T, S), workspace)
     chosen = _resolve_path(trans, transition, B, S, device, path, tiles_of(B, S))
     args = (obs.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
-            indices.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index,
-            ctypes.c_void_p(stream))
+            indices.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index, stream)
     flags = _path_flag(chosen)
-    if _reusable(workspace, transition, (B, T, S, chosen, stream), reuse_preparation):
+    if _reusable(workspace, transition, (B, T, S, chosen, stream.value), reuse_preparation):
         flags |= 1                                  # TORBI_HIP_REUSE_TRANSITION
     if chosen in TIME_RESIDENT:
         flags |= _seed_flag(transition, S)          # TORBI_HIP_FEW_SEEDS / _MANY_SEEDS once the scan depth is known
@@ -405,7 +386,7 @@ def decode(
         left, right, background = _band_of(trans, transition, S, B, index)
         phases = (ctypes.c_float * 6)() if _profile is not None else None
         _lib.check(lib.torbi_hip_viterbi_decode_banded_over(one, 1, trans.data_ptr(), init.data_ptr(), S, left, right,
-                                                            ctypes.c_float(background), index, ctypes.c_void_p(stream), flags, phases),
+                                                            ctypes.c_float(background), index, stream, flags, phases),
                    'torbi_hip_viterbi_decode_banded_over')
         if _profile is not None:
             _profile[:] = list(phases)
@@ -414,7 +395,7 @@ def decode(
                                           workspace.numel(), B, T))
         phases = (ctypes.c_float * 6)() if _profile is not None else None
         _lib.check(kept.call(device, lambda pointer, size, reuse, filled: lib.torbi_hip_viterbi_decode_batches_prepared(
-            one, 1, trans.data_ptr(), init.data_ptr(), S, index, ctypes.c_void_p(stream), flags | reuse, phases,
+            one, 1, trans.data_ptr(), init.data_ptr(), S, index, stream, flags | reuse, phases,
             pointer, size, filled)), 'torbi_hip_viterbi_decode_batches_prepared')
         if _profile is not None:
             _profile[:] = list(phases)
@@ -587,9 +568,7 @@ def decode_batches(
     trans = transition.to(device).contiguous()
     init = initial.to(device).contiguous()
     own_scratch = workspaces is None
-    if own_scratch:
-        workspaces = [torch.empty((lib.torbi_hip_workspace_bytes(B, T, S),), dtype=torch.uint8, device=device)
-                      for B, T, _ in shapes]
+    workspaces = [None] * count if own_scratch else list(workspaces)
     if len(workspaces) != count:
         raise RuntimeError('decode_batches needs one workspace per batch')
     if out is None:
@@ -602,21 +581,17 @@ def decode_batches(
             raise RuntimeError('out tensors must be contiguous int32 (N_k, T_k) tensors on the compute device')
     table = (_lib.Batch * count)()
     for k, (B, T, _) in enumerate(shapes):
-        ws = workspaces[k]
-        need = lib.torbi_hip_workspace_bytes(B, T, S)
-        if ws.device != device or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
-            raise RuntimeError(f'workspace {k} must be a contiguous uint8 tensor of >= {need} bytes on {device}')
+        ws, index, stream = _lib.launch(device, lib.torbi_hip_workspace_bytes(B, T, S), workspaces[k])
+        workspaces[k] = ws
         table[k] = _lib.Batch(observations[k].data_ptr(), batch_frames[k].data_ptr(), indices[k].data_ptr(),
                               ws.data_ptr(), ws.numel(), B, T)
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(device).cuda_stream
     largest = max(B for B, _, _ in shapes)
     tiles = sum(tiles_of(B, S) for B, _, _ in shapes)
     chosen = _resolve_path(trans, transition, largest, S, device, path, tiles, count=count,
                            items=sum(B for B, _, _ in shapes))
     flags = _path_flag(chosen)
     first = next((k for k, (B, _, _) in enumerate(shapes) if B > 0), 0)
-    if _reusable(workspaces[first], transition, (tuple(shapes), chosen, stream), reuse_preparation) \
+    if _reusable(workspaces[first], transition, (tuple(shapes), chosen, stream.value), reuse_preparation) \
             and (chosen in TIME_RESIDENT or count == 1):
         flags |= 1
     if shortest_first:
@@ -628,15 +603,15 @@ def decode_batches(
     if chosen == 'band':
         left, right, background = _band_of(trans, transition, S, sum(B for B, _, _ in shapes), index)
         _lib.check(lib.torbi_hip_viterbi_decode_banded_over(table, count, trans.data_ptr(), init.data_ptr(), S, left, right,
-                                                            ctypes.c_float(background), index, ctypes.c_void_p(stream), flags, phases),
+                                                            ctypes.c_float(background), index, stream, flags, phases),
                    'torbi_hip_viterbi_decode_banded_over')
     elif kept is not None:
         _lib.check(kept.call(device, lambda pointer, size, reuse, filled: lib.torbi_hip_viterbi_decode_batches_prepared(
-            table, count, trans.data_ptr(), init.data_ptr(), S, index, ctypes.c_void_p(stream), flags | reuse, phases,
+            table, count, trans.data_ptr(), init.data_ptr(), S, index, stream, flags | reuse, phases,
             pointer, size, filled)), 'torbi_hip_viterbi_decode_batches_prepared')
     else:
         _lib.check(lib.torbi_hip_viterbi_decode_batches(table, count, trans.data_ptr(), init.data_ptr(), S, index,
-                                                        ctypes.c_void_p(stream), flags, phases),
+                                                        stream, flags, phases),
                    'torbi_hip_viterbi_decode_batches')
     if _profile is not None:
         _profile[:] = list(phases)
@@ -786,18 +761,14 @@ def decode_uniform(
     """
     B, T, S = observation.shape
     if probabilities and not (uniform_supported(S) and observation.dtype == torch.float32):
-        tiny = torch.finfo(torch.float32).tiny             # (the steps of torbi/core.py:189-197, one by one)
-        scores = torch.log(observation).to(dtype=torch.float32)
-        scores.exp_()
-        scores += tiny
-        scores.log_()
+        # (the steps of torbi/core.py:189-197, one by one)
+        scores = epsilon_clamp_(torch.log(observation).to(dtype=torch.float32))
         return decode_uniform(scores, batch_frames, log_transition, initial)
     if not uniform_supported(S):
         transition = torch.full((S, S), float(log_transition), dtype=torch.float32,
                                 device=observation.device)
         return decode(observation, batch_frames, transition, initial)
-    _check_inputs(observation, batch_frames, torch.empty((S, S), dtype=torch.float32, device='meta'),
-                  initial)
+    _check_inputs(observation, batch_frames, None, initial)
     _require_gpu()
     lib = _lib.load()
     home = observation.device
@@ -808,18 +779,13 @@ def decode_uniform(
     indices = torch.empty((B, T), dtype=torch.int32, device=device)
     if B == 0:
         return indices.to(home)
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(device).cuda_stream
+    _, index, stream = _lib.launch(device)
     entry = lib.torbi_hip_viterbi_decode_uniform_probabilities if probabilities else lib.torbi_hip_viterbi_decode_uniform
     code = entry(obs.data_ptr(), frames.data_ptr(), float(log_transition), init.data_ptr(),
-                 indices.data_ptr(), B, T, S, index, ctypes.c_void_p(stream))
+                 indices.data_ptr(), B, T, S, index, stream)
     if code == -5:     # TORBI_HIP_EUNSUPPORTED (e.g. a misaligned view): materialise
         if probabilities:
-            tiny = torch.finfo(torch.float32).tiny
-            obs = torch.log(obs)
-            obs.exp_()
-            obs += tiny
-            obs.log_()
+            obs = epsilon_clamp_(torch.log(obs))
         transition = torch.full((S, S), float(log_transition), dtype=torch.float32, device=device)
         return decode(obs, batch_frames, transition, initial).to(home)      # (like every other return of this function)
     _lib.check(code, 'torbi_hip_viterbi_decode_uniform')

@@ -480,6 +480,37 @@ int torbi_hip_forward_backward_counts(const float *observation, const int32_t *b
                                       float *loglik_out, float *counts_out, float *initial_counts_out, void *workspace,
                                       size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
+/*
+ * k-best Viterbi decoding (added within ABI 17): the k best state sequences of every item with their exact scores, on the
+ * model torbi_hip_viterbi_decode decodes (torbi_amd/k_best.py, KBEST.md).  Inputs as there: observation (B, T, S) log
+ * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log; 1 <= k <= 32.
+ * Every state j of frame t keeps a list L_t(j) of (value, back-pointer) entries, all sums in float32:
+ *     L_0(j) = [ fl(obs_0[j] + initial[j]) ]
+ *     t >= 1: candidates c = fl(L_{t-1}(i)[r] + transition[j][i]) over every prev-state i and rank r of L_{t-1}(i);
+ *             L_t(j) = the first min(k, count) in the order (c descending, i ascending, r ascending), each stored as
+ *             fl(obs_t[j] + c) with back-pointer (i, r)
+ *     result: the first min(k, S^F) entries (L_{F-1}(j)[r], j, r) in the order (value descending, j ascending, r ascending)
+ * Rank 0 is torbi_hip_viterbi_decode's path for inputs without NaN or +inf.  indices_out (B, k, T) int32: rank q's path in
+ * columns t < F_b, its last state repeated after; scores_out (B, k) fp32: the path's value.  Ranks beyond S^F get score
+ * -inf and index -1 in every column.  A NaN or +inf in anything an item reads (initial, the matrix when F_b >= 2, its
+ * observation rows t < F_b) gives that item NaN scores and -1 indices.  An item's bits never depend on other items' data.
+ *
+ * workspace: device scratch (no initialisation) of torbi_hip_k_best_workspace_bytes(B, T, S, k) bytes for
+ * torbi_hip_k_best (back-pointers: 4 * B * (T - 1) * k * S bytes) and of torbi_hip_k_best_workspace_bytes(B, T, 1, k)
+ * bytes for torbi_hip_k_best_uniform.  One launch per frame (general route) or one per call (uniform route), no host
+ * synchronisation: with a caller-owned workspace a call can be captured into a graph.
+ * The uniform entry point takes a matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))); it
+ * returns the bits of torbi_hip_k_best on that matrix.
+ * TORBI_HIP_EINVAL for k outside [1, 32]; TORBI_HIP_ERANGE for S > 16384, B * T > 2^32 or B * T * S > 2^40.
+ */
+size_t torbi_hip_k_best_workspace_bytes(int B, int T, int S, int k);
+int torbi_hip_k_best(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                     int32_t *indices_out, float *scores_out, void *workspace, size_t workspace_bytes, int B, int T, int S,
+                     int k, int device, void *stream);
+int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                             const float *initial, int32_t *indices_out, float *scores_out, void *workspace,
+                             size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

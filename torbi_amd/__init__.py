@@ -21,9 +21,11 @@ from .stream import StreamDecoder
 from .posterior import forward_backward, forward_backward_workspace_bytes, state_posteriors
 from .training import (expected_counts, expected_counts_workspace_bytes, forward_backward_counts,
                        log_likelihood)
+from .k_best import best_paths, decode_k_best, decode_k_best_workspace_bytes
 
 __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 'workspace_bytes', 'set_forward_path', 'forward_path', 'from_probabilities', 'from_file', 'from_file_to_file',
            'from_files_to_files', 'from_dataloader', 'save', 'save_masked', 'data', 'synth',
            'distributed', 'DecodePipeline', 'BATCH_SIZE', 'NUM_WORKERS', 'reset_path_state', 'release_job_memory', 'timer',
            'StreamDecoder', 'state_posteriors', 'forward_backward', 'forward_backward_workspace_bytes',
-           'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood']
+           'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood',
+           'best_paths', 'decode_k_best', 'decode_k_best_workspace_bytes']

@@ -39,6 +39,7 @@
 #include "stream.hpp"
 #include "forward_backward.hpp"
 #include "counts.hpp"
+#include "k_best.hpp"
 
 namespace {
 
@@ -2643,6 +2644,130 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
                        posterior_out, loglik_out, T, S);
+    return (int)hipGetLastError();
+}
+
+// ---- k-best Viterbi decoding (k_best.hpp) ----
+
+size_t torbi_hip_k_best_workspace_bytes(int B, int T, int S, int k) {
+    if (B < 1 || T < 1 || S < 1 || S > kb::kMaxStates || k < 1 || k > kb::kMaxK) return 256;
+    return kb::layout(B, T, S, k).total;
+}
+
+static int kb_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *indices,
+                      const void *scores, const void *ws, size_t ws_bytes, int B, int T, int S, int k, int wS) {
+    if (B < 0 || T < 1 || S < 1 || k < 1 || k > kb::kMaxK) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!obs || !frames || !matrix || !initial || !indices || !scores || !ws) return TORBI_HIP_EINVAL;
+    if (S > kb::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (size_t)B * T > (size_t)1 << 32)
+        return TORBI_HIP_ERANGE;
+    if (ws_bytes < torbi_hip_k_best_workspace_bytes(B, T, wS, k)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+// One frame of the general route: KMAX = k rounded up to a power of two, G items per workgroup (G * KMAX <= 16 list
+// entries per thread, at most 8 items, G rank-0 rows of LDS <= 64 KB: at most 129 VGPRs), but no fewer than
+// kb::kStepWorkgroups workgroups while G > 1.  The rule depends on the shape and k only, not on the device.
+static hipError_t kb_step(const float *obs, const int32_t *frames, const float *tt, const float *prev, float *cur,
+                          int32_t *ptrs, int t, int B, int T, int S, int k, hipStream_t st) {
+    int KMAX = 1;
+    while (KMAX < k) KMAX *= 2;
+    int G = std::min(8, std::max(1, 16 / KMAX));
+    while (G > 1 && (size_t)G * S * sizeof(float) > (size_t)kb::kRowLdsBytes) G >>= 1;
+    const int jblocks = (S + kb::kThreads - 1) / kb::kThreads;
+    while (G > 1 && (long long)((B + G - 1) / G) * jblocks < kb::kStepWorkgroups) G >>= 1;
+    const int n = kb::list_length(k, S, t - 1), m = kb::list_length(k, S, t);
+    const dim3 grid((B + G - 1) / G, jblocks);
+    const size_t lds = (size_t)G * S * sizeof(float);
+#define TORBI_KB_STEP(km, g)                                                                                              \
+    hipLaunchKernelGGL((kb::kb_step_kernel<km, g>), grid, dim3(kb::kThreads), lds, st, obs, frames, tt, prev, cur, ptrs, t, \
+                       B, T, S, k, n, m)
+#define TORBI_KB_G(km)                                                                                                    \
+    switch (G) {                                                                                                          \
+        case 8: TORBI_KB_STEP(km, (km <= 2 ? 8 : 1)); break;                                                              \
+        case 4: TORBI_KB_STEP(km, (km <= 4 ? 4 : 1)); break;                                                              \
+        case 2: TORBI_KB_STEP(km, (km <= 8 ? 2 : 1)); break;                                                              \
+        default: TORBI_KB_STEP(km, 1); break;                                                                             \
+    }
+    switch (KMAX) {
+        case 1: TORBI_KB_G(1); break;
+        case 2: TORBI_KB_G(2); break;
+        case 4: TORBI_KB_G(4); break;
+        case 8: TORBI_KB_G(8); break;
+        case 16: TORBI_KB_G(16); break;
+        default: TORBI_KB_G(32); break;
+    }
+#undef TORBI_KB_G
+#undef TORBI_KB_STEP
+    return hipGetLastError();
+}
+
+int torbi_hip_k_best(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                     int32_t *indices_out, float *scores_out, void *workspace, size_t workspace_bytes, int B, int T, int S,
+                     int k, int device, void *stream) {
+    const int rc = kb_args_ok(observation, batch_frames, transition, initial, indices_out, scores_out, workspace,
+                              workspace_bytes, B, T, S, k, S);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const kb::Layout l = kb::layout(B, T, S, k);
+    char *base = fb_base(workspace);
+    float *vals = reinterpret_cast<float *>(base + l.vals), *tt = reinterpret_cast<float *>(base + l.tt);
+    int32_t *ptrs = reinterpret_cast<int32_t *>(base + l.ptrs), *count = reinterpret_cast<int32_t *>(base + l.count);
+    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
+    kb::Final *fin = reinterpret_cast<kb::Final *>(base + l.final_);
+    const size_t plane = (size_t)B * k * S;
+    hipError_t e;
+    if ((e = hipMemsetAsync(flag, 0, sizeof(int32_t), st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_prepare_kernel, dim3((S + 31) / 32, (S + 31) / 32), dim3(256), 0, st, transition, tt, flag, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, vals, T, S, k);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    for (int t = 1; t < T; ++t)
+        if ((e = kb_step(observation, batch_frames, tt, vals + ((t - 1) & 1) * plane, vals + (t & 1) * plane, ptrs, t, B,
+                         T, S, k, st)) != hipSuccess)
+            return (int)e;
+    hipLaunchKernelGGL(kb::kb_final_kernel, dim3(B), dim3(kb::kThreads), 0, st, observation, batch_frames, initial, vals, fin,
+                       count, flag, B, T, S, k);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_walk_kernel<false>, dim3(B), dim3(64), 0, st, batch_frames, ptrs, fin, count, flag, indices_out,
+                       scores_out, T, S, k);
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                             const float *initial, int32_t *indices_out, float *scores_out, void *workspace,
+                             size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream) {
+    const int rc = kb_args_ok(observation, batch_frames, initial /* (no matrix) */, initial, indices_out, scores_out,
+                              workspace, workspace_bytes, B, T, S, k, 1);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const kb::Layout l = kb::layout(B, T, 1, k);
+    char *base = fb_base(workspace);
+    int32_t *ptrs = reinterpret_cast<int32_t *>(base + l.ptrs), *count = reinterpret_cast<int32_t *>(base + l.count);
+    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
+    kb::Final *fin = reinterpret_cast<kb::Final *>(base + l.final_);
+    int KMAX = 1;
+    while (KMAX < k) KMAX *= 2;
+#define TORBI_KB_UNIFORM(km)                                                                                              \
+    hipLaunchKernelGGL(kb::kb_uniform_kernel<km>, dim3(B), dim3(64), 0, st, observation, batch_frames, uniform_value, initial, \
+                       ptrs, fin, count, flag, B, T, S, k)
+    switch (KMAX) {
+        case 1: TORBI_KB_UNIFORM(1); break;
+        case 2: TORBI_KB_UNIFORM(2); break;
+        case 4: TORBI_KB_UNIFORM(4); break;
+        case 8: TORBI_KB_UNIFORM(8); break;
+        case 16: TORBI_KB_UNIFORM(16); break;
+        default: TORBI_KB_UNIFORM(32); break;
+    }
+#undef TORBI_KB_UNIFORM
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_walk_kernel<true>, dim3(B), dim3(64), 0, st, batch_frames, ptrs, fin, count, flag, indices_out,
+                       scores_out, T, S, k);
     return (int)hipGetLastError();
 }
 

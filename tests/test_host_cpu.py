@@ -66,6 +66,54 @@ def test_argument_errors_without_touching_a_device():
     assert lib.torbi_hip_viterbi_decode(null, null, null, null, null, null, 0, 0, 1, 1, 0, null) == 0
 
 
+def test_every_decode_entry_point_keeps_its_own_answer_to_bad_arguments():
+    """The decode entry points share one dispatcher; what each of them answered to a missing table, model or buffer before
+    it did is its own: an empty batch of decode_ex needs no model, the table entry points and decode_profiled turn a
+    missing model down before they look at a batch, decode_batches_prepared looks at its buffer first.  No device needed."""
+    lib = _lib.load()
+    null = ctypes.c_void_p(0)
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    aligned = ctypes.c_void_p((p.value + 255) // 256 * 256)
+
+    def one(B, T=4):
+        return (_lib.Batch * 1)(_lib.Batch(p, p, p, p, 64, B, T))
+    phases = (ctypes.c_float * 6)()
+    filled = ctypes.c_int(7)
+    EINVAL, EWORKSPACE = -1, -2
+    ex, profiled = lib.torbi_hip_viterbi_decode_ex, lib.torbi_hip_viterbi_decode_profiled
+    assert ex(null, null, null, null, null, null, 0, 0, 1, 1, 0, null, 0) == 0
+    assert ex(null, null, null, null, null, null, 0, 0, 0, 1, 0, null, 0) == EINVAL             # no frames
+    assert ex(null, null, null, null, null, null, 0, 0, 1, 1, 0, null, 1 << 20) == EINVAL       # unknown flag
+    assert ex(p, p, p, p, p, p, 64, 4, 4, 4, 0, null, 256) == EWORKSPACE
+    assert profiled(null, null, null, null, null, null, 0, 0, 1, 1, 0, null, 0, phases) == EINVAL
+    assert profiled(null, null, p, p, null, null, 0, 0, 1, 1, 0, null, 0, phases) == 0
+    assert profiled(null, null, p, p, null, null, 0, 0, 1, 1, 0, null, 0, None) == EINVAL
+    assert profiled(p, p, p, p, p, p, 64, 4, 4, 4, 0, null, 0, phases) == EWORKSPACE
+    batches = lib.torbi_hip_viterbi_decode_batches
+    assert batches(null, 0, null, null, 4, 0, null, 0, None) == 0
+    assert batches(null, 0, null, null, 0, 0, null, 0, None) == EINVAL                          # no states
+    assert batches(one(0), 1, null, p, 4, 0, null, 0, None) == EINVAL                           # no model, an empty batch
+    assert batches(one(0), 1, p, p, 4, 0, null, 0, None) == 0
+    assert batches(null, 1, p, p, 4, 0, null, 0, None) == EINVAL
+    assert batches(one(0), _lib.MAX_BATCHES + 1, p, p, 4, 0, null, 0, None) == EINVAL
+    assert batches(one(4), 1, p, p, 4, 0, null, 0, None) == EWORKSPACE
+    assert batches(one(0, 0), 1, p, p, 4, 0, null, 0, None) == EINVAL
+    banded, over = lib.torbi_hip_viterbi_decode_banded, lib.torbi_hip_viterbi_decode_banded_over
+    assert banded(null, 0, null, null, 4, -1, 0, 0, null, 0, None) == EINVAL                    # a negative reach, no batch
+    assert banded(null, 0, null, null, 4, 1, 1, 0, null, 0, None) == 0
+    assert banded(one(0), 1, null, p, 4, 1, 1, 0, null, 0, None) == EINVAL
+    assert banded(one(0), 1, p, p, 4, 1, 1, 0, null, 0, None) == 0
+    assert over(one(4), 1, p, p, 4, 1, 1, ctypes.c_float(-3.0), 0, null, 0, None) == EWORKSPACE
+    prepared = lib.torbi_hip_viterbi_decode_batches_prepared
+    assert prepared(null, 0, null, null, 4, 0, null, 0, None, ctypes.c_void_p(aligned.value + 1), 1 << 30,
+                    ctypes.byref(filled)) == EWORKSPACE and filled.value == 0                   # misaligned, no batch
+    assert prepared(null, 0, null, null, 4, 0, null, 0, None, aligned, 16, ctypes.byref(filled)) == EWORKSPACE    # short
+    filled.value = 7
+    assert prepared(one(0), 1, p, p, 4, 0, null, 0, None, null, 0, ctypes.byref(filled)) == 0 and filled.value == 0
+    assert prepared(one(0), 1, null, p, 4, 0, null, 1, None, null, 0, ctypes.byref(filled)) == EINVAL
+
+
 def test_decode_validates_like_the_reference_operator():
     obs = torch.zeros(1, 3, 3)
     trans = torch.zeros(3, 3)

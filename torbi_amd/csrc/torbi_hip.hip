@@ -693,10 +693,12 @@ struct ResidentWorkspace {
 // The per-transition preparation of the time-resident routes (sorted + arranged rows, transposed matrix, row ranges)
 // may live OUTSIDE the workspace (torbi_hip_viterbi_decode_batches_prepared): a caller that allocates a workspace per call
 // -- the reference's own calling pattern, torbi/core.py:200-206 -- keeps 25 MB per matrix instead of rebuilding it
-// (0.25 ms per call at 1440 states).  Set for the duration of one call on the calling thread.
-thread_local void *g_preparation = nullptr;
-thread_local size_t g_preparation_bytes = 0;
-thread_local bool g_preparation_valid = false;      // holds this matrix's preparation (the caller's promise, or filled by this call)
+// (0.25 ms per call at 1440 states).  Travels as an argument from the entry point to the one layout that reads it.
+struct Preparation {
+    void *pointer;
+    size_t bytes;
+    bool valid;      // holds this matrix's preparation (the caller's promise, or filled by this call)
+};
 
 // the serial number of the decode this host thread is launching: what its kernels raise their NaN / +inf alarms with
 // (nonfinite.hpp; never 0, never repeated within a process: no alarm word has to be cleared between decodes)
@@ -714,7 +716,8 @@ inline size_t preparation_bytes(int S) {
            align_up(sizeof(int32_t) * 2 * (size_t)S, 256);
 }
 
-inline ResidentWorkspace carve_resident(void *base, int B, int T, int S, int cus) {
+// `kept`: the caller's preparation buffer (run_resident only; every other layout of a workspace is the plain one)
+inline ResidentWorkspace carve_resident(void *base, int B, int T, int S, int cus, const Preparation *kept = nullptr) {
     ResidentWorkspace w;
     char *p = static_cast<char *>(base);
     const int Sp = (S + 15) / 16 * 16;
@@ -744,8 +747,8 @@ inline ResidentWorkspace carve_resident(void *base, int B, int T, int S, int cus
     w.sorted = reinterpret_cast<float2 *>(p);
     w.tt = reinterpret_cast<float *>(p + sorted_bytes);
     w.row_range = reinterpret_cast<int32_t *>(p + sorted_bytes + tt_bytes);
-    if (base && g_preparation && g_preparation_bytes >= preparation_bytes(S)) {      // (the caller keeps it: see above)
-        char *q = static_cast<char *>(g_preparation);
+    if (base && kept && kept->bytes >= preparation_bytes(S)) {      // (the caller keeps it: see above)
+        char *q = static_cast<char *>(kept->pointer);
         w.sorted = reinterpret_cast<float2 *>(q);
         w.tt = reinterpret_cast<float *>(q + sorted_bytes);
         w.row_range = reinterpret_cast<int32_t *>(q + sorted_bytes + tt_bytes);
@@ -771,10 +774,7 @@ struct BandWorkspace {
 constexpr size_t kBandWords = 16 + 2 * (size_t)kMaxGroupTiles + 64;
 inline BandWorkspace carve_band(void *base, int B, int T, int S, int cus) {
     BandWorkspace w;
-    void *const kept = g_preparation;
-    g_preparation = nullptr;                     // (the band route keeps nothing in a caller's preparation buffer)
-    w.base = carve_resident(base, B, T, S, cus);
-    g_preparation = kept;
+    w.base = carve_resident(base, B, T, S, cus);     // (the band route keeps nothing in a caller's preparation buffer)
     char *p = static_cast<char *>(base) + w.base.bytes;
     w.xchg_bytes = align_up(band::xchg_bytes(B, S), 256);
     w.xchg = p;
@@ -1427,10 +1427,11 @@ inline hipError_t nonfinite_end(const HostBatch *hb, int n, const float *trans, 
     return hipGetLastError();
 }
 
-// batches with B > 0 only; the preparation lives in the first batch's workspace
+// batches with B > 0 only; the preparation lives in the first batch's workspace, or in `kept` (marked valid once this call
+// has enqueued its filling)
 hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const float *init, int S, int cus, hipStream_t s,
-                        hipEvent_t *ev, int *launches, bool reuse, bool ascending = false, bool clusters = false,
-                        bool few = false) {
+                        hipEvent_t *ev, int *launches, bool reuse, bool ascending, bool clusters, bool few,
+                        Preparation *kept) {
     resident::Group grp{};
     resident::OrderJobs jobs{};
     jobs.ascending = ascending ? 1 : 0;
@@ -1460,7 +1461,7 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
         tiles += tiles_of(hb[k].B, S);
         items += hb[k].B;
     }
-    const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus);
+    const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus, kept);
     if (tiles > kMaxGroupTiles) return hipErrorInvalidValue;
     grp.tile_map = w.tile_map;
     grp.stats = w.stats;
@@ -1487,9 +1488,9 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
         jobs.job[k].route_record = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
         jobs.job[k].route = (int)(R > 1 ? ROUTE_CLUSTER : ROUTE_RESIDENT);
     }
-    if (g_preparation) reuse = g_preparation_valid;       // the caller's buffer: the promise is about IT, whichever batch
+    if (kept) reuse = kept->valid;       // the caller's buffer: the promise is about IT, whichever batch
     if (!reuse) launch_list_preparation(trans, w.sorted, w.row_range, w.tt, S, w.SpP, w.NPOW, resident::tile_items(S), s);
-    if (g_preparation) g_preparation_valid = true;
+    if (kept) kept->valid = true;
     hipLaunchKernelGGL(resident::order_items_kernel, dim3((widest + 255) / 256, n), dim3(256), 0, s, jobs);
     for (int k = 0; k < n; ++k) {            // batches too large for the all-pairs ranking: counting sort over the lengths
         const resident::OrderJob &jb = jobs.job[k];
@@ -1830,11 +1831,16 @@ inline bool band_plan_for(const HostBatch *hb, int n, int S, int hl, int hr, int
     return choose_band(S, hl, hr, tiles, cus, pl, background);
 }
 
-// one decode on `s`; optional events bracket the forward and backtrace phases (ev[3]: end of the preparation)
-hipError_t run_decode(const float *obs, const int32_t *frames, const float *trans, const float *init,
-                      int32_t *out, void *workspace, int B, int T, int S, int device, hipStream_t s,
-                      hipEvent_t *ev, int *launches, bool reuse, bool collect, int path, unsigned seed_flags = 0u,
-                      Route *taken = nullptr) {
+// one decode on `s`; optional events bracket the forward and backtrace phases (ev[3]: end of the preparation).
+// `kept`: the caller's preparation buffer, which only the time-resident routes use
+hipError_t run_decode(const HostBatch &hb, const float *trans, const float *init, int S, int device, hipStream_t s,
+                      hipEvent_t *ev, int *launches, bool reuse, int path, unsigned seed_flags, Route *taken,
+                      Preparation *kept) {
+    const float *const obs = hb.obs;
+    const int32_t *const frames = hb.frames;
+    int32_t *const out = hb.out;
+    void *const workspace = hb.workspace;
+    const int B = hb.B, T = hb.T;
     hipError_t e;
     const int cus = cu_count(device);
     Route route = route_for(path, B, S, cus);
@@ -1845,18 +1851,15 @@ hipError_t run_decode(const float *obs, const int32_t *frames, const float *tran
     if (route == ROUTE_HELD && !held_resident(S, device, cus))
         route = route_for(path == TORBI_HIP_FORWARD_HELD ? TORBI_HIP_FORWARD_AUTO : path, B, S, cus, false);
     if (taken) *taken = route;
-    if (route == ROUTE_RESIDENT || route == ROUTE_CLUSTER) {
-        const HostBatch hb{obs, frames, out, workspace, B, T};
+    if (route == ROUTE_RESIDENT || route == ROUTE_CLUSTER)
         return run_resident(&hb, 1, trans, init, S, cus, s, ev, launches, reuse, false, route == ROUTE_CLUSTER,
-                            few_seeds(seed_flags, route == ROUTE_CLUSTER));
-    }
-    if (g_preparation) reuse = false;       // (the promise was about the caller's buffer; this route prepares in the workspace)
+                            few_seeds(seed_flags, route == ROUTE_CLUSTER), kept);
+    if (kept) reuse = false;       // (the promise was about the caller's buffer; this route prepares in the workspace)
     if (ev) (void)hipEventRecord(ev[0], s);
     if (ev) (void)hipEventRecord(ev[3], s);
     // NaN / +inf inputs (nonfinite.hpp): the small-state kernels look at the values they produce; the routes below get
     // their observations looked at by a launch of its own (they launch a kernel per timestep anyway)
-    const HostBatch alone{obs, frames, out, workspace, B, T};
-    e = nonfinite_begin(&alone, 1, trans, init, S, cus, s, route != ROUTE_SMALL, -1, -1, route != ROUTE_SMALL);
+    e = nonfinite_begin(&hb, 1, trans, init, S, cus, s, route != ROUTE_SMALL, -1, -1, route != ROUTE_SMALL);
     if (e != hipSuccess) return e;
     if (route == ROUTE_SMALL) {             // one launch: recurrence, backtrace and the route record
         // (the byte plane lies where the generic path's trellis does and is never larger: small_states.hpp)
@@ -1866,7 +1869,7 @@ hipError_t run_decode(const float *obs, const int32_t *frames, const float *tran
         e = small::supported(S) ? launch_small(obs, frames, trans, init, w, out, record, B, T, S, s, launches, cus)
                                 : launch_block(obs, frames, trans, init, w, out, record, B, T, S, s, launches, cus);
         if (ev) (void)hipEventRecord(ev[1], s);
-        if (e == hipSuccess) e = nonfinite_end(&alone, 1, trans, init, S, cus, s);
+        if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, cus, s);
         if (ev) (void)hipEventRecord(ev[2], s);
         return e;
     }
@@ -1909,22 +1912,25 @@ hipError_t run_decode(const float *obs, const int32_t *frames, const float *tran
         if (ev) (void)hipEventRecord(ev[1], s);
         if (e == hipSuccess) e = launch_finalize(frames, w, out, B, T, S, s);
     }
-    if (e == hipSuccess) e = nonfinite_end(&alone, 1, trans, init, S, cus, s);
+    if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, cus, s);
     if (ev) (void)hipEventRecord(ev[2], s);
     return e;
 }
 
+// the four events of a profiled call; of a call that asks for no phases none is created and nothing synchronises
 struct PhaseEvents {
     hipEvent_t ev[4] = {};
     hipError_t err = hipSuccess;
-    PhaseEvents() {
+    const bool wanted;
+    explicit PhaseEvents(bool wanted_) : wanted(wanted_) {
         for (auto &x : ev)
-            if (err == hipSuccess) err = hipEventCreate(&x);
+            if (wanted && err == hipSuccess) err = hipEventCreate(&x);
     }
     ~PhaseEvents() {
         for (auto &x : ev)
             if (x) (void)hipEventDestroy(x);
     }
+    hipEvent_t *events() { return wanted ? ev : nullptr; }
     // forward (incl. preparation), argmax + backtrace, preparation alone -- after synchronising on the last event
     hipError_t read(float *phase_ms) {
         hipError_t e = hipEventSynchronize(ev[2]);
@@ -1935,6 +1941,104 @@ struct PhaseEvents {
         return hipSuccess;
     }
 };
+
+// ---- the ONE way from a Viterbi decode entry point with a transition matrix to the kernels ---------------------------
+struct BandPromise { int reach_left, reach_right; float background; };
+struct DecodeCall {             // everything of a call that is not a batch
+    const float *transition, *initial;
+    int S, device;
+    void *stream;
+    unsigned flags;
+    float *phase_ms;            // null: no events are created, nothing synchronises
+    const BandPromise *band;    // null, or what the caller promises about the matrix (torbi_hip_viterbi_decode_banded_over)
+    Preparation *preparation;   // null, or the caller-kept buffer (torbi_hip_viterbi_decode_batches_prepared)
+};
+
+// the entry points that take a batch table turn a missing table or model down before they look at any batch (an empty
+// batch of torbi_hip_viterbi_decode_ex needs neither)
+inline bool table_given(const torbi_hip_batch *batches, int count, const float *transition, const float *initial) {
+    return count == 0 || (batches && transition && initial);
+}
+
+int decode_group(const torbi_hip_batch *batches, int count, const DecodeCall &call) {
+    const float *const transition = call.transition, *const initial = call.initial;
+    const int S = call.S, device = call.device;
+    const unsigned flags = call.flags;
+    float *const phase_ms = call.phase_ms;
+    if (!flags_ok(flags) || count < 0 || count > TORBI_HIP_MAX_BATCHES || S < 1) return TORBI_HIP_EINVAL;
+    if (count == 0) return TORBI_HIP_OK;
+    if (!batches) return TORBI_HIP_EINVAL;
+    if (phase_ms)
+        for (int i = 0; i < 6; ++i) phase_ms[i] = 0.0f;
+    const int cus = cu_count(device);
+    HostBatch hb[TORBI_HIP_MAX_BATCHES];
+    int n = 0, tiles = 0;
+    for (int k = 0; k < count; ++k) {
+        const torbi_hip_batch &b = batches[k];
+        const int rc = check_args(b.observation, b.batch_frames, transition, initial, b.indices_out, b.workspace,
+                                  b.workspace_bytes, b.B, b.T, S, device);
+        if (rc != TORBI_HIP_OK) return rc;
+        if (b.B == 0) continue;
+        hb[n++] = HostBatch{b.observation, b.batch_frames, b.indices_out, b.workspace, b.B, b.T};
+        tiles += tiles_of(b.B, S);
+    }
+    if (n == 0) return TORBI_HIP_OK;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    hipStream_t s = static_cast<hipStream_t>(call.stream);
+    int path = requested_path(flags);
+    // a promised band: the band kernel when its plan covers the group, else whatever the call does without the promise
+    // (BAND named: as AUTO)
+    BandChoice band_choice;
+    bool banded = false;
+    if (call.band) {
+        bool vec = (reinterpret_cast<uintptr_t>(transition) & 15) == 0;       // (16-byte reads of matrix rows and observation rows)
+        for (int k = 0; k < n; ++k) vec = vec && (reinterpret_cast<uintptr_t>(hb[k].obs) & 15) == 0;
+        banded = vec && band_plan_for(hb, n, S, call.band->reach_left, call.band->reach_right, cus, path, band_choice,
+                                      call.band->background);
+        if (!banded && path == TORBI_HIP_FORWARD_BAND) path = TORBI_HIP_FORWARD_AUTO;
+    }
+    const bool reuse = (flags & TORBI_HIP_REUSE_TRANSITION) != 0;
+    // ONE time-resident launch for the whole group: named (whole tiles per workgroup, or clusters), or AUTO with enough
+    // items -- half the compute units' worth of tiles, or fewer tiles split over clusters (batches of >= 17 items)
+    int largest = 0;
+    long long items = 0;
+    for (int k = 0; k < n; ++k) largest = std::max(largest, hb[k].B), items += hb[k].B;
+    const bool split = cluster_members(tiles, S, cus) > 1;
+    const bool together = resident_fits(S, tiles) &&
+                          (path == TORBI_HIP_FORWARD_RESIDENT || path == TORBI_HIP_FORWARD_CLUSTER ||
+                           (path == TORBI_HIP_FORWARD_AUTO && !small::supported(S) && !small_block_auto((int)std::min(items, 1ll << 30), S, cus) &&      // (a wavefront / workgroup per sequence)
+                            (2 * tiles > cus || (split && largest > 16))));
+    const bool clusters = together && split && path != TORBI_HIP_FORWARD_RESIDENT;
+    const bool ascending = (flags & TORBI_HIP_SHORTEST_FIRST) != 0;
+    PhaseEvents pe(phase_ms != nullptr);
+    if (pe.err != hipSuccess) return (int)pe.err;
+    int launches = 0, covered = n;
+    Route taken = ROUTE_BAND;
+    hipError_t e = hipSuccess;
+    if (banded) {
+        e = run_band(hb, n, transition, initial, S, band_choice, cus, s, pe.events(), &launches, ascending);
+    } else if (together) {
+        e = run_resident(hb, n, transition, initial, S, cus, s, pe.events(), &launches, reuse, ascending, clusters,
+                         few_seeds(flags, clusters), call.preparation);
+        taken = clusters ? ROUTE_CLUSTER : ROUTE_RESIDENT;
+    } else {
+        // one batch after the other, each on the path it would take alone (route_for); phases and route of the LAST batch
+        // only; the reuse promise covers the first batch's workspace only
+        for (int k = 0; k < n && e == hipSuccess; ++k)
+            e = run_decode(hb[k], transition, initial, S, device, s, k == n - 1 ? pe.events() : nullptr, &launches,
+                           reuse && k == 0, path, flags, &taken, call.preparation);
+        covered = 1;
+    }
+    mark_decode_end(device, s);
+    if (phase_ms) {
+        if (e == hipSuccess) e = pe.read(phase_ms);
+        phase_ms[2] = (float)launches;
+        phase_ms[3] = (float)taken;
+        phase_ms[5] = (float)covered;
+    }
+    return (int)e;
+}
 
 }  // namespace
 
@@ -2008,93 +2112,17 @@ int torbi_hip_viterbi_decode_ex(const float *observation, const int32_t *batch_f
                                 int32_t *indices_out, void *workspace, size_t workspace_bytes,
                                 int B, int T, int S, int device, void *stream, unsigned flags) {
     if (!flags_ok(flags)) return TORBI_HIP_EINVAL;
-    const int rc = check_args(observation, batch_frames, transition, initial, indices_out,
-                              workspace, workspace_bytes, B, T, S, device);
-    if (rc != TORBI_HIP_OK || B == 0) return rc;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    const hipError_t e = run_decode(observation, batch_frames, transition, initial, indices_out, workspace,
-                                    B, T, S, device, static_cast<hipStream_t>(stream), nullptr, nullptr,
-                                    (flags & TORBI_HIP_REUSE_TRANSITION) != 0, (flags & TORBI_HIP_COLLECT_STATS) != 0,
-                                    requested_path(flags), flags);
-    mark_decode_end(device, static_cast<hipStream_t>(stream));
-    return (int)e;
+    const torbi_hip_batch one{observation, batch_frames, indices_out, workspace, workspace_bytes, B, T};
+    // (a batch on its own has no order among batches to choose: TORBI_HIP_SHORTEST_FIRST belongs to the table entry points)
+    return decode_group(&one, 1, DecodeCall{transition, initial, S, device, stream, flags & ~(unsigned)TORBI_HIP_SHORTEST_FIRST,
+                                            nullptr, nullptr, nullptr});
 }
 
 int torbi_hip_viterbi_decode_batches(const torbi_hip_batch *batches, int count, const float *transition,
                                      const float *initial, int S, int device, void *stream, unsigned flags,
                                      float *phase_ms) {
-    if (!flags_ok(flags) || count < 0 || count > TORBI_HIP_MAX_BATCHES || S < 1) return TORBI_HIP_EINVAL;
-    if (count == 0) return TORBI_HIP_OK;
-    if (!batches || !transition || !initial) return TORBI_HIP_EINVAL;
-    if (phase_ms)
-        for (int i = 0; i < 6; ++i) phase_ms[i] = 0.0f;
-    const int cus = cu_count(device);
-    HostBatch hb[TORBI_HIP_MAX_BATCHES];
-    int n = 0, tiles = 0;
-    for (int k = 0; k < count; ++k) {
-        const torbi_hip_batch &b = batches[k];
-        const int rc = check_args(b.observation, b.batch_frames, transition, initial, b.indices_out, b.workspace,
-                                  b.workspace_bytes, b.B, b.T, S, device);
-        if (rc != TORBI_HIP_OK) return rc;
-        if (b.B == 0) continue;
-        hb[n++] = HostBatch{b.observation, b.batch_frames, b.indices_out, b.workspace, b.B, b.T};
-        tiles += tiles_of(b.B, S);
-    }
-    if (n == 0) return TORBI_HIP_OK;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int path = requested_path(flags);
-    const bool reuse = (flags & TORBI_HIP_REUSE_TRANSITION) != 0;
-    // ONE time-resident launch for the whole group: named (whole tiles per workgroup, or clusters), or AUTO with enough
-    // items -- half the compute units' worth of tiles, or fewer tiles split over clusters (batches of >= 17 items)
-    int largest = 0;
-    long long items = 0;
-    for (int k = 0; k < n; ++k) largest = std::max(largest, hb[k].B), items += hb[k].B;
-    const bool split = cluster_members(tiles, S, cus) > 1;
-    const bool together = resident_fits(S, tiles) &&
-                          (path == TORBI_HIP_FORWARD_RESIDENT || path == TORBI_HIP_FORWARD_CLUSTER ||
-                           (path == TORBI_HIP_FORWARD_AUTO && !small::supported(S) && !small_block_auto((int)std::min(items, 1ll << 30), S, cus) &&      // (a wavefront / workgroup per sequence)
-                            (2 * tiles > cus || (split && largest > 16))));
-    const bool clusters = together && split && path != TORBI_HIP_FORWARD_RESIDENT;
-    const bool ascending = (flags & TORBI_HIP_SHORTEST_FIRST) != 0;
-    if (phase_ms) {
-        PhaseEvents pe;
-        if (pe.err != hipSuccess) return (int)pe.err;
-        int launches = 0;
-        hipError_t e;
-        if (together) {
-            e = run_resident(hb, n, transition, initial, S, cus, s, pe.ev, &launches, reuse, ascending, clusters,
-                             few_seeds(flags, clusters));
-            phase_ms[3] = (float)(clusters ? ROUTE_CLUSTER : ROUTE_RESIDENT);
-        } else {
-            // one batch after the other, each on the path it would take alone; phases of the LAST batch only
-            e = hipSuccess;
-            // (the reuse promise covers the first batch's workspace only)
-            Route taken = route_for(path, hb[n - 1].B, S, cus);
-            for (int k = 0; k < n && e == hipSuccess; ++k)
-                e = run_decode(hb[k].obs, hb[k].frames, transition, initial, hb[k].out, hb[k].workspace, hb[k].B,
-                               hb[k].T, S, device, s, k == n - 1 ? pe.ev : nullptr, &launches, reuse && k == 0, false, path, flags,
-                               &taken);
-            phase_ms[3] = (float)taken;
-        }
-        mark_decode_end(device, s);
-        if (e == hipSuccess) e = pe.read(phase_ms);
-        phase_ms[2] = (float)launches;
-        phase_ms[5] = (float)(together ? n : 1);
-        return (int)e;
-    }
-    hipError_t e = hipSuccess;
-    if (together)
-        e = run_resident(hb, n, transition, initial, S, cus, s, nullptr, nullptr, reuse, ascending, clusters,
-                         few_seeds(flags, clusters));
-    else
-        for (int k = 0; k < n && e == hipSuccess; ++k)
-            e = run_decode(hb[k].obs, hb[k].frames, transition, initial, hb[k].out, hb[k].workspace, hb[k].B, hb[k].T, S,
-                           device, s, nullptr, nullptr, reuse && k == 0, (flags & TORBI_HIP_COLLECT_STATS) != 0, path, flags);
-    mark_decode_end(device, s);
-    return (int)e;
+    if (!table_given(batches, count, transition, initial)) return TORBI_HIP_EINVAL;
+    return decode_group(batches, count, DecodeCall{transition, initial, S, device, stream, flags, phase_ms, nullptr, nullptr});
 }
 
 
@@ -2170,53 +2198,9 @@ int torbi_hip_viterbi_decode_banded(const torbi_hip_batch *batches, int count, c
 int torbi_hip_viterbi_decode_banded_over(const torbi_hip_batch *batches, int count, const float *transition, const float *initial,
                                          int S, int reach_left, int reach_right, float background, int device, void *stream,
                                          unsigned flags, float *phase_ms) {
-    if (!flags_ok(flags) || count < 0 || count > TORBI_HIP_MAX_BATCHES || S < 1 || reach_left < 0 || reach_right < 0)
-        return TORBI_HIP_EINVAL;
-    if (count == 0) return TORBI_HIP_OK;
-    if (!batches || !transition || !initial) return TORBI_HIP_EINVAL;
-    const int cus = cu_count(device);
-    HostBatch hb[TORBI_HIP_MAX_BATCHES];
-    int n = 0;
-    for (int k = 0; k < count; ++k) {
-        const torbi_hip_batch &b = batches[k];
-        const int rc = check_args(b.observation, b.batch_frames, transition, initial, b.indices_out, b.workspace,
-                                  b.workspace_bytes, b.B, b.T, S, device);
-        if (rc != TORBI_HIP_OK) return rc;
-        if (b.B == 0) continue;
-        hb[n++] = HostBatch{b.observation, b.batch_frames, b.indices_out, b.workspace, b.B, b.T};
-    }
-    BandChoice pl;
-    const int path = requested_path(flags);
-    bool vec = (reinterpret_cast<uintptr_t>(transition) & 15) == 0;       // (16-byte reads of matrix rows and observation rows)
-    for (int k = 0; k < n; ++k) vec = vec && (reinterpret_cast<uintptr_t>(hb[k].obs) & 15) == 0;
-    if (n == 0 || !vec || !band_plan_for(hb, n, S, reach_left, reach_right, cus, path, pl, background)) {
-        // not a shape of the band kernel: whatever the plain entry point does with it (BAND named: as AUTO)
-        unsigned f = flags;
-        if (path == TORBI_HIP_FORWARD_BAND) f = (flags & ~(7u << 4)) | TORBI_HIP_PATH_FLAG(TORBI_HIP_FORWARD_AUTO);
-        return torbi_hip_viterbi_decode_batches(batches, count, transition, initial, S, device, stream, f, phase_ms);
-    }
-    if (phase_ms)
-        for (int i = 0; i < 6; ++i) phase_ms[i] = 0.0f;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool ascending = (flags & TORBI_HIP_SHORTEST_FIRST) != 0;
-    hipError_t e;
-    if (phase_ms) {
-        PhaseEvents pe;
-        if (pe.err != hipSuccess) return (int)pe.err;
-        int launches = 0;
-        e = run_band(hb, n, transition, initial, S, pl, cus, s, pe.ev, &launches, ascending);
-        mark_decode_end(device, s);
-        if (e == hipSuccess) e = pe.read(phase_ms);
-        phase_ms[2] = (float)launches;
-        phase_ms[3] = (float)ROUTE_BAND;
-        phase_ms[5] = (float)n;
-        return (int)e;
-    }
-    e = run_band(hb, n, transition, initial, S, pl, cus, s, nullptr, nullptr, ascending);
-    mark_decode_end(device, s);
-    return (int)e;
+    if (reach_left < 0 || reach_right < 0 || !table_given(batches, count, transition, initial)) return TORBI_HIP_EINVAL;
+    const BandPromise band{reach_left, reach_right, background};
+    return decode_group(batches, count, DecodeCall{transition, initial, S, device, stream, flags, phase_ms, &band, nullptr});
 }
 
 size_t torbi_hip_preparation_bytes(int S) { return S > 0 ? preparation_bytes(S) : 256; }
@@ -2228,12 +2212,11 @@ int torbi_hip_viterbi_decode_batches_prepared(const torbi_hip_batch *batches, in
     if (filled) *filled = 0;
     if (preparation && (S < 1 || preparation_bytes_given < preparation_bytes(S) || (reinterpret_cast<uintptr_t>(preparation) & 255)))
         return TORBI_HIP_EWORKSPACE;
-    struct Scope {
-        Scope(void *p, size_t n, bool valid) { g_preparation = p; g_preparation_bytes = n; g_preparation_valid = valid; }
-        ~Scope() { g_preparation = nullptr; g_preparation_bytes = 0; g_preparation_valid = false; }
-    } scope(preparation, preparation_bytes_given, preparation && (flags & TORBI_HIP_REUSE_TRANSITION));
-    const int rc = torbi_hip_viterbi_decode_batches(batches, count, transition, initial, S, device, stream, flags, phase_ms);
-    if (filled && rc == TORBI_HIP_OK) *filled = g_preparation_valid ? 1 : 0;
+    if (!table_given(batches, count, transition, initial)) return TORBI_HIP_EINVAL;
+    Preparation kept{preparation, preparation_bytes_given, preparation && (flags & TORBI_HIP_REUSE_TRANSITION)};
+    const int rc = decode_group(batches, count, DecodeCall{transition, initial, S, device, stream, flags, phase_ms, nullptr,
+                                                           preparation ? &kept : nullptr});
+    if (filled && rc == TORBI_HIP_OK) *filled = kept.valid ? 1 : 0;
     return rc;
 }
 
@@ -2320,13 +2303,13 @@ int torbi_hip_viterbi_decode_profiled(const float *observation, const int32_t *b
                                       int32_t *indices_out, void *workspace,
                                       size_t workspace_bytes, int B, int T, int S, int device,
                                       void *stream, unsigned flags, float *phase_ms) {
-    if (!phase_ms || !flags_ok(flags)) return TORBI_HIP_EINVAL;
+    if (!phase_ms || !flags_ok(flags) || !transition || !initial) return TORBI_HIP_EINVAL;
     const torbi_hip_batch one{observation, batch_frames, indices_out, workspace, workspace_bytes, B, T};
-    // a single batch through the batches entry: same routing as torbi_hip_viterbi_decode_ex for this shape (AUTO
-    // there counts the 16-item tiles of the group, which for one batch is what route_for() does)
+    // a table of one: the group decision of decode_group() counts the 16-item tiles of the group, which for one batch is what
+    // route_for() does, so the routing is that of torbi_hip_viterbi_decode_ex for this shape
     unsigned f = flags;
     if (((flags >> 4) & 7u) == 0) f |= TORBI_HIP_PATH_FLAG(default_path());
-    return torbi_hip_viterbi_decode_batches(&one, 1, transition, initial, S, device, stream, f, phase_ms);
+    return decode_group(&one, 1, DecodeCall{transition, initial, S, device, stream, f, phase_ms, nullptr, nullptr});
 }
 
 int torbi_hip_read_posterior(const void *workspace, size_t workspace_bytes,

@@ -7,6 +7,7 @@ implementation through the C ABI (include/torbi_hip.h) instead of
 import threading
 import ctypes
 import os
+import weakref
 from typing import Optional
 
 import torch
@@ -50,23 +51,29 @@ def _path_flag(path: str) -> int:
 
 def _resolve_path(trans, transition, B, S, device, path, tiles, count=1, items=None):
     """The path name this call passes to the library."""
+    return _resolve(trans, transition, B, S, torch.device(device), path, tiles, count, items)[0]
+
+
+def _resolve(trans, transition, B, S, device, path, tiles, count=1, items=None):
+    """(`_resolve_path`'s answer, what `_band_of` says about the matrix when that answer is 'band' else None); `device`: a
+    torch.device."""
     forced = _forced_path if path is None else path
     if forced not in FORWARD_PATHS:
         raise ValueError(f'forward path must be one of {sorted(FORWARD_PATHS)}; got {forced!r}')
     if forced not in ('auto', 'band'):
-        return forced
-    index = torch.device(device).index or 0
+        return forced, None
+    index = device.index or 0
     total = B if items is None else items
     small = 2 <= S <= SMALL_STATES and forward_path(total, S, 'auto', index) == 'small'
     if not (small and forced == 'auto'):
         # a banded matrix (the reference's pitch model, torbi/evaluate/core.py:24-33) whose band the band kernel covers
         # (csrc/band_forward.hpp): every finite cell and no other, the time loop inside one launch.  AUTO leaves the
         # handful of sequences the held-matrix kernel decodes to it.
-        if _band_of(trans, transition, S, total, index) is not None \
-                and (forced == 'band' or not (count == 1 and forward_path(B, S, 'auto', index) == 'held')):
-            return 'band'
+        band = _band_of(trans, transition, S, total, index)
+        if band is not None and (forced == 'band' or not (count == 1 and forward_path(B, S, 'auto', index) == 'held')):
+            return 'band', band
     if small or forced == 'band':
-        return 'auto'               # one wavefront / workgroup per sequence, whatever the matrix looks like (csrc/small_states.hpp)
+        return 'auto', None         # one wavefront / workgroup per sequence, whatever the matrix looks like (csrc/small_states.hpp)
     chosen = _choose_path(trans, transition, B, S)
     banded = chosen == 'dense'
     cus = compute_units(device)
@@ -91,7 +98,7 @@ def _resolve_path(trans, transition, B, S, device, path, tiles, count=1, items=N
         if banded or chosen in ('pruned', 'dense'):
             losing = not banded and _resident_is_losing(transition, S, single=not group_like)
             chosen = 'dense' if losing else 'cluster'
-    return chosen
+    return chosen, None
 
 
 # fraction of a row's S/16 list blocks per scan above which the dense kernel wins (tools/peaked_group_probe.py at 1440
@@ -357,8 +364,6 @@ def decode(
     """
     B, T, S = _check_inputs(observation, batch_frames, transition, initial)
     _require_gpu()
-    lib = _lib.load()
-
     home = observation.device
     device = home if home.type == 'cuda' else torch.device('cuda', torch.cuda.current_device())
     obs = observation.to(device).contiguous()
@@ -369,45 +374,9 @@ def decode(
     indices = torch.empty((B, T), dtype=torch.int32, device=device)
     if B == 0:
         return indices.to(home)
-    own_scratch = workspace is None
-    workspace, index, stream = _lib.launch(device, lib.torbi_hip_workspace_bytes(B, T, S), workspace)
-    chosen = _resolve_path(trans, transition, B, S, device, path, tiles_of(B, S))
-    args = (obs.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
-            indices.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, index, stream)
-    flags = _path_flag(chosen)
-    if _reusable(workspace, transition, (B, T, S, chosen, stream.value), reuse_preparation):
-        flags |= 1                                  # TORBI_HIP_REUSE_TRANSITION
-    if chosen in TIME_RESIDENT:
-        flags |= _seed_flag(transition, S)          # TORBI_HIP_FEW_SEEDS / _MANY_SEEDS once the scan depth is known
-    kept = _kept_preparation(transition, B, S, chosen, device, index) if own_scratch and chosen != 'band' else None
-    if chosen == 'band':
-        one = (_lib.Batch * 1)(_lib.Batch(obs.data_ptr(), frames.data_ptr(), indices.data_ptr(), workspace.data_ptr(),
-                                          workspace.numel(), B, T))
-        left, right, background = _band_of(trans, transition, S, B, index)
-        phases = (ctypes.c_float * 6)() if _profile is not None else None
-        _lib.check(lib.torbi_hip_viterbi_decode_banded_over(one, 1, trans.data_ptr(), init.data_ptr(), S, left, right,
-                                                            ctypes.c_float(background), index, stream, flags, phases),
-                   'torbi_hip_viterbi_decode_banded_over')
-        if _profile is not None:
-            _profile[:] = list(phases)
-    elif kept is not None:       # the per-call scratch is new every time; the preparation stays with the matrix
-        one = (_lib.Batch * 1)(_lib.Batch(obs.data_ptr(), frames.data_ptr(), indices.data_ptr(), workspace.data_ptr(),
-                                          workspace.numel(), B, T))
-        phases = (ctypes.c_float * 6)() if _profile is not None else None
-        _lib.check(kept.call(device, lambda pointer, size, reuse, filled: lib.torbi_hip_viterbi_decode_batches_prepared(
-            one, 1, trans.data_ptr(), init.data_ptr(), S, index, stream, flags | reuse, phases,
-            pointer, size, filled)), 'torbi_hip_viterbi_decode_batches_prepared')
-        if _profile is not None:
-            _profile[:] = list(phases)
-    elif _profile is None:
-        _lib.check(lib.torbi_hip_viterbi_decode_ex(*args, flags), 'torbi_hip_viterbi_decode_ex')
-    else:
-        phases = (ctypes.c_float * 6)()
-        _lib.check(lib.torbi_hip_viterbi_decode_profiled(*args, flags, phases),
-                   'torbi_hip_viterbi_decode_profiled')
-        _profile[:] = list(phases)
-    if chosen in TIME_RESIDENT and (_forced_path if path is None else path) == 'auto':
-        _watch_resident(transition, workspace, B, T, S, _seeds_kept(flags, chosen, tiles_of(B, S), device))
+    shape = (B, T, S)
+    _issue((obs,), (frames,), (indices,), None if workspace is None else (workspace,), (shape,), transition, trans, init,
+           device, path, shape, reuse_preparation, False, _profile)
     return indices if home == device else indices.to(home)
 
 
@@ -451,7 +420,6 @@ class _Preparation:
     tensor's death drops it; 25.6 MB at 1440 states."""
 
     def __init__(self, nbytes, device):
-        import threading
         self.buffer = torch.empty((nbytes,), dtype=torch.uint8, device=device)
         self.home = torch.cuda.current_stream(device).cuda_stream      # the stream the caching allocator knows the block by
         self.filled = None            # event recorded behind the call that filled the buffer
@@ -480,7 +448,7 @@ class _Preparation:
         return run(self.buffer.data_ptr(), self.buffer.numel(), 1, ctypes.byref(filled))
 
 
-_preparation_lock = __import__('threading').Lock()
+_preparation_lock = threading.Lock()
 
 
 def _kept_preparation(transition, B, S, chosen, device, index):
@@ -503,7 +471,6 @@ def _reusable(workspace, transition, shape_state, wanted) -> bool:
     shape, path and stream) and say whether it already does.  The transition is identified by the tensor OBJECT
     and its version (a new tensor can reuse a freed address); a tensor without a version counter (inference
     mode) is never reused.  Kept with the workspace tensor's notes (torbi_amd/state.py)."""
-    import weakref
     version = _version_of(transition)
     kept = state.notes(workspace)
     if kept is None:
@@ -513,6 +480,69 @@ def _reusable(workspace, transition, shape_state, wanted) -> bool:
     hit = (wanted and version is not None and known is not None and known[0] == holds and known[1]() is transition)
     kept['holds'] = (holds, weakref.ref(transition))
     return bool(hit)
+
+
+def _issue(observations, batch_frames, indices, workspaces, shapes, transition, trans, init, device, path, holds,
+           reuse_preparation, shortest_first=False, _profile=None) -> None:
+    """What `decode` and `decode_batches` end in: one call into the library for batches that are checked, contiguous and on
+    one HIP device (`trans`, `init`: the model there; `transition`: the caller's tensor, which the notes hang off).
+    `workspaces`: the caller's, one per batch, or None.  `holds`: how the calling wrapper names these shapes in what
+    `_reusable` records -- the wrappers spell it differently, so a workspace that moves between them never claims a reuse."""
+    lib = _lib.load()
+    count, S = len(shapes), shapes[0][2]
+    own_scratch = workspaces is None
+    workspaces = [None] * count if own_scratch else list(workspaces)
+    largest = items = tiles = 0
+    first = None                                   # the first batch that is not empty
+    for k, (B, T, _) in enumerate(shapes):         # (one pass, no generators: a 3-state decode takes 0.1 ms, host time shows)
+        workspaces[k], index, stream = _lib.launch(device, lib.torbi_hip_workspace_bytes(B, T, S), workspaces[k])
+        if B > largest:
+            largest = B
+        if first is None and B > 0:
+            first = k
+        items += B
+        tiles += tiles_of(B, S)
+    first = first or 0
+    chosen, band = _resolve(trans, transition, largest, S, device, path, tiles, count, items)
+    flags = _path_flag(chosen)
+    if _reusable(workspaces[first], transition, holds + (chosen, stream.value), reuse_preparation) \
+            and (chosen in TIME_RESIDENT or count == 1):
+        flags |= 1                                 # TORBI_HIP_REUSE_TRANSITION
+    if shortest_first:
+        flags |= 256                               # TORBI_HIP_SHORTEST_FIRST
+    if chosen in TIME_RESIDENT:
+        flags |= _seed_flag(transition, S)         # TORBI_HIP_FEW_SEEDS / _MANY_SEEDS once the scan depth is known
+    phases = (ctypes.c_float * 6)() if _profile is not None else None
+    kept = _kept_preparation(transition, largest, S, chosen, device, index) if own_scratch and chosen != 'band' else None
+    model = (trans.data_ptr(), init.data_ptr(), S)
+    if count == 1 and band is None and kept is None and phases is None and not shortest_first:
+        # ONE batch, nothing to report, no order to choose: the call a latency-bound caller makes (0.09 ms per 3-state
+        # decode) takes no table
+        (B, T, _), ws = shapes[0], workspaces[0]
+        _lib.check(lib.torbi_hip_viterbi_decode_ex(observations[0].data_ptr(), batch_frames[0].data_ptr(), model[0], model[1],
+                                                   indices[0].data_ptr(), ws.data_ptr(), ws.numel(), B, T, S, index, stream,
+                                                   flags), 'torbi_hip_viterbi_decode_ex')
+    else:
+        table = (_lib.Batch * count)(*(
+            _lib.Batch(obs.data_ptr(), frames.data_ptr(), found.data_ptr(), ws.data_ptr(), ws.numel(), B, T)
+            for obs, frames, found, ws, (B, T, _) in zip(observations, batch_frames, indices, workspaces, shapes)))
+        if band is not None:
+            left, right, background = band
+            _lib.check(lib.torbi_hip_viterbi_decode_banded_over(table, count, *model, left, right, ctypes.c_float(background),
+                                                                index, stream, flags, phases),
+                       'torbi_hip_viterbi_decode_banded_over')
+        elif kept is not None:       # the per-call scratch is new every time; the preparation stays with the matrix
+            _lib.check(kept.call(device, lambda pointer, size, reuse, filled: lib.torbi_hip_viterbi_decode_batches_prepared(
+                table, count, *model, index, stream, flags | reuse, phases, pointer, size, filled)),
+                'torbi_hip_viterbi_decode_batches_prepared')
+        else:
+            _lib.check(lib.torbi_hip_viterbi_decode_batches(table, count, *model, index, stream, flags, phases),
+                       'torbi_hip_viterbi_decode_batches')
+    if _profile is not None:
+        _profile[:] = list(phases)
+    if chosen in TIME_RESIDENT and (_forced_path if path is None else path) == 'auto':
+        B0, T0, _ = shapes[first]
+        _watch_resident(transition, workspaces[first], B0, T0, S, _seeds_kept(flags, chosen, tiles, device))
 
 
 def decode_batches(
@@ -555,7 +585,6 @@ def decode_batches(
     if count > _lib.MAX_BATCHES:
         raise RuntimeError(f'at most {_lib.MAX_BATCHES} batches per call; got {count}')
     _require_gpu()
-    lib = _lib.load()
     device = observations[0].device
     if device.type != 'cuda':
         raise RuntimeError('decode_batches takes tensors that are already on a HIP device')
@@ -567,9 +596,7 @@ def decode_batches(
             raise RuntimeError('decode_batches needs contiguous tensors on one device')
     trans = transition.to(device).contiguous()
     init = initial.to(device).contiguous()
-    own_scratch = workspaces is None
-    workspaces = [None] * count if own_scratch else list(workspaces)
-    if len(workspaces) != count:
+    if workspaces is not None and len(workspaces) != count:
         raise RuntimeError('decode_batches needs one workspace per batch')
     if out is None:
         out = [None] * count
@@ -579,45 +606,8 @@ def decode_batches(
         if (tuple(tensor.shape) != (B, T) or tensor.dtype != torch.int32 or tensor.device != device
                 or not tensor.is_contiguous()):
             raise RuntimeError('out tensors must be contiguous int32 (N_k, T_k) tensors on the compute device')
-    table = (_lib.Batch * count)()
-    for k, (B, T, _) in enumerate(shapes):
-        ws, index, stream = _lib.launch(device, lib.torbi_hip_workspace_bytes(B, T, S), workspaces[k])
-        workspaces[k] = ws
-        table[k] = _lib.Batch(observations[k].data_ptr(), batch_frames[k].data_ptr(), indices[k].data_ptr(),
-                              ws.data_ptr(), ws.numel(), B, T)
-    largest = max(B for B, _, _ in shapes)
-    tiles = sum(tiles_of(B, S) for B, _, _ in shapes)
-    chosen = _resolve_path(trans, transition, largest, S, device, path, tiles, count=count,
-                           items=sum(B for B, _, _ in shapes))
-    flags = _path_flag(chosen)
-    first = next((k for k, (B, _, _) in enumerate(shapes) if B > 0), 0)
-    if _reusable(workspaces[first], transition, (tuple(shapes), chosen, stream.value), reuse_preparation) \
-            and (chosen in TIME_RESIDENT or count == 1):
-        flags |= 1
-    if shortest_first:
-        flags |= 256                               # TORBI_HIP_SHORTEST_FIRST
-    if chosen in TIME_RESIDENT:
-        flags |= _seed_flag(transition, S)         # TORBI_HIP_FEW_SEEDS / _MANY_SEEDS once the scan depth is known
-    phases = (ctypes.c_float * 6)() if _profile is not None else None
-    kept = _kept_preparation(transition, largest, S, chosen, device, index) if own_scratch and chosen != 'band' else None
-    if chosen == 'band':
-        left, right, background = _band_of(trans, transition, S, sum(B for B, _, _ in shapes), index)
-        _lib.check(lib.torbi_hip_viterbi_decode_banded_over(table, count, trans.data_ptr(), init.data_ptr(), S, left, right,
-                                                            ctypes.c_float(background), index, stream, flags, phases),
-                   'torbi_hip_viterbi_decode_banded_over')
-    elif kept is not None:
-        _lib.check(kept.call(device, lambda pointer, size, reuse, filled: lib.torbi_hip_viterbi_decode_batches_prepared(
-            table, count, trans.data_ptr(), init.data_ptr(), S, index, stream, flags | reuse, phases,
-            pointer, size, filled)), 'torbi_hip_viterbi_decode_batches_prepared')
-    else:
-        _lib.check(lib.torbi_hip_viterbi_decode_batches(table, count, trans.data_ptr(), init.data_ptr(), S, index,
-                                                        stream, flags, phases),
-                   'torbi_hip_viterbi_decode_batches')
-    if _profile is not None:
-        _profile[:] = list(phases)
-    if chosen in TIME_RESIDENT and (_forced_path if path is None else path) == 'auto':
-        B0, T0, _ = shapes[first]
-        _watch_resident(transition, workspaces[first], B0, T0, S, _seeds_kept(flags, chosen, tiles, device))
+    _issue(observations, batch_frames, indices, workspaces, shapes, transition, trans, init, device, path, (tuple(shapes),),
+           reuse_preparation, shortest_first, _profile)
     return indices
 
 

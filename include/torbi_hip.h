@@ -424,11 +424,20 @@ int torbi_hip_fill_synthetic(float *dst, uint64_t count, uint64_t start, int str
  *
  * push: observation (B, Tc, S) (Tc may be 0); transition (S, S) [next][prev] and transition_t, the same matrix transposed
  * ([prev][next]); initial (S,).  indices_out [B][out_capacity] int32 (out_capacity >= pending + frames): row b receives the
- * stream's newly decided frames, oldest first; counts_out [B] int32 their number (-1: info does not fit capacity or
- * out_capacity; nothing written).  The caller advances base_slot by counts_out[b] and pending by frames - counts_out[b].
+ * stream's newly decided frames, oldest first; counts_out [B] int32 their number.  The caller advances base_slot by
+ * counts_out[b] and pending by frames - counts_out[b].
+ * counts_out[b] = -1 (checked by every kernel of the call, not only the last): the stream's info does not fit --
+ * pending < 0, base_slot outside 0 .. capacity - 1, frames outside 0 .. Tc (push), or pending + frames above capacity or
+ * out_capacity -- and the stream's ring, memo and indices_out row are untouched; the other streams of the call are decoded.
  * flush: the flagged streams' remaining frames (the final state is the first NaN of the newest row, otherwise its first
  * maximum), counts_out as above; the caller then starts those streams afresh.
  * TORBI_HIP_ERANGE for S > 8000.
+ *
+ * torbi_hip_stream_tile (added within ABI 17) reports how many streams share one workgroup of a push's forward kernel for a (B, S) call
+ * on `device`: 1, 2, 4, 8 or 16 (stream_forward_kernel<G, J> of csrc/stream.hpp; J = 4 where S % 4 == 0 and transition_t is
+ * 16-byte aligned, else 1), a function of (B, S, compute units) only and the choice the push itself makes; TORBI_HIP_EINVAL /
+ * TORBI_HIP_ERANGE for a shape the push turns down.  Touches no device memory; without a usable device it answers for 256
+ * compute units.
  */
 size_t torbi_hip_stream_state_bytes(int B, int S, int capacity);
 int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
@@ -436,6 +445,7 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
 int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *state, size_t state_bytes, int capacity,
                            int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+int torbi_hip_stream_tile(int B, int S, int device);
 
 /*
  * (ABI 17) Forward-backward: per-frame state posteriors and the sequence log-likelihood of the HMM that

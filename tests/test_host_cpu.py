@@ -848,3 +848,70 @@ def test_band_plan_covers_the_reference_pitch_band_and_says_so_without_a_gpu():
     import torch
     cpu = torch.zeros((1440, 1440))
     assert viterbi.band_reach(cpu, cpu, 1440) is None           # (asked of device tensors only)
+
+
+def test_stream_entry_points_answer_bad_arguments_before_any_device_work():
+    """torbi_hip_stream_state_bytes / _push / _flush / _tile: the return code of every argument error, in the order the
+    library looks (dimensions, pointers, the state-count bound, the state's size, then the push's own arguments).  The
+    answers of the first three were recorded from the library before torbi_hip_stream_tile was factored out of the push.
+    Every call here is turned down before a device is touched; the pointers are host memory nobody reads."""
+    lib = _lib.load()
+    EINVAL, EWORKSPACE, ERANGE = -1, -2, -3
+    null = ctypes.c_void_p(0)
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    B, S, cap, out_cap = 3, 5, 4, 6
+    need = lib.torbi_hip_stream_state_bytes(B, S, cap)
+    assert need == 4 * (B * cap * S + B * cap + B * S) == 348
+    assert lib.torbi_hip_stream_state_bytes(1, 1, 1) == 12 and lib.torbi_hip_stream_state_bytes(2, 8001, 16) == 1088264
+    for shape in [(0, S, cap), (B, 0, cap), (B, S, 0), (-1, S, cap), (B, -1, cap), (B, S, -1)]:
+        assert lib.torbi_hip_stream_state_bytes(*shape) == 0, shape
+
+    def push(obs=p, Tc=2, info=p, trans=p, tt=p, init=p, state=p, nbytes=need, cap=cap, out=p, out_cap=out_cap, counts=p,
+             B=B, S=S):
+        return lib.torbi_hip_stream_push(obs, Tc, info, trans, tt, init, state, nbytes, cap, out, out_cap, counts, B, S, 0, null)
+
+    def flush(info=p, trans=p, state=p, nbytes=need, cap=cap, out=p, out_cap=out_cap, counts=p, B=B, S=S):
+        return lib.torbi_hip_stream_flush(info, trans, state, nbytes, cap, out, out_cap, counts, B, S, 0, null)
+    for call in (push, flush):
+        for name in ('info', 'trans', 'state', 'out', 'counts'):
+            assert call(**{name: null}) == EINVAL, (call.__name__, name)
+        for name in ('B', 'S', 'cap', 'out_cap'):
+            for value in (0, -1):
+                assert call(**{name: value}) == EINVAL, (call.__name__, name, value)
+        assert call(nbytes=need - 1) == EWORKSPACE and call(nbytes=0) == EWORKSPACE
+        assert call(cap=cap + 1) == EWORKSPACE                                  # the state of a smaller ring
+        assert call(S=8001, nbytes=1 << 40) == ERANGE and call(S=8001) == ERANGE       # the bound before the state's size
+        assert call(S=8001, info=null) == EINVAL and call(S=8001, cap=0) == EINVAL     # ... and after pointers and dimensions
+        assert call(S=8000) == EWORKSPACE                                       # 8000 states pass the bound
+    # the push's own arguments come last: a short state is reported first
+    assert push(Tc=-1) == EINVAL and push(Tc=-1, nbytes=0) == EWORKSPACE
+    for name in ('obs', 'tt', 'init'):
+        assert push(**{name: null}) == EINVAL, name
+        assert push(**{name: null}, nbytes=0) == EWORKSPACE and push(**{name: null}, S=8001) == ERANGE, name
+    # torbi_hip_stream_tile: the push's own answer to a shape
+    for shape in [(0, S), (B, 0), (-1, S), (B, -1), (0, 8001)]:
+        assert lib.torbi_hip_stream_tile(*shape, 0) == EINVAL, shape
+    assert lib.torbi_hip_stream_tile(B, 8001, 0) == ERANGE and lib.torbi_hip_stream_tile(1 << 20, 8001, 0) == ERANGE
+    assert lib.torbi_hip_stream_tile(B, 8000, 0) == 1
+
+
+def test_stream_tile_is_a_power_of_two_that_fits_the_lds_and_follows_the_batch():
+    """torbi_hip_stream_tile(B, S, device): streams per workgroup of a push's forward kernel -- a power of two in 1 .. 16
+    whose 2 * G * S double-buffered floats fit 64 KB, never smaller for a larger batch and never larger for more states,
+    whatever the device's compute-unit count (256 is assumed where there is no device)."""
+    lib = _lib.load()
+    tile = lambda B, S: lib.torbi_hip_stream_tile(B, S, 0)
+    batches = [1, 2, 3, 64, 255, 256, 257, 511, 512, 1021, 1024, 2041, 2048, 4081, 4096, 5000, 1 << 16, 1 << 20]
+    states = [1, 2, 3, 63, 64, 65, 511, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 7999, 8000]
+    table = np.array([[tile(B, S) for S in states] for B in batches])
+    assert np.isin(table, [1, 2, 4, 8, 16]).all()
+    assert (2 * table * np.array(states)[None, :] * 4 <= 65536).all()
+    assert (np.diff(table, axis=0) >= 0).all()                  # non-decreasing in B
+    assert (np.diff(table, axis=1) <= 0).all()                  # non-increasing in S
+    assert (table[0] == 1).all()                                # one stream: nothing to share
+    # a batch large enough for any device: only the LDS decides
+    assert table[-1].tolist() == [16] * 8 + [8] * 2 + [4] * 2 + [2] * 2 + [1] * 3
+    # every G is reached by some batch at 64 states
+    reached = {tile(B, 64) for B in [1] + [1 << k for k in range(1, 21)]}
+    assert reached == {1, 2, 4, 8, 16}

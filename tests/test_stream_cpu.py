@@ -1,7 +1,5 @@
 """torbi_amd.StreamDecoder on the host (gpu=None): exactness against the whole-sequence decode and the oracle, and the
 maximal-commit rule against a brute-force survivor-set computation."""
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -9,46 +7,7 @@ import torch
 import oracle
 import torbi_amd
 from torbi_amd import synth
-
-TINY = np.finfo(np.float32).tiny
-
-
-def plan(B, T, mode, seed=0):
-    """Per push: (Tc, frames per stream) for streams of T frames each (ragged modes: streams end at different times)."""
-    rng = np.random.default_rng(seed)
-    if mode == 'all':
-        return [(T, np.full(B, T))]
-    if mode == 'one':
-        return [(1, np.ones(B, dtype=np.int64))] * T
-    left, pushes = np.full(B, T), []
-    while left.any():
-        Tc = int(rng.integers(1, 9))
-        f = np.minimum(left, rng.integers(0, Tc + 1, size=B)) if mode == 'ragged' else np.minimum(left, Tc)
-        left -= f
-        pushes.append((Tc, f))
-    return pushes
-
-
-def feed(dec, source, pushes, check=None):
-    """Push `source[b]` (frames, S) to stream b piece by piece (invalid positions hold NaN: they must not be read);
-    returns the concatenated outputs (flush included) and the frames pushed per stream."""
-    B, S = len(source), dec.states
-    pos = np.zeros(B, dtype=np.int64)
-    got = [[] for _ in range(B)]
-    for Tc, f in pushes:
-        chunk = torch.full((B, Tc, S), math.nan)
-        for b in range(B):
-            chunk[b, :f[b]] = torch.from_numpy(source[b][pos[b]:pos[b] + f[b]])
-        out = dec.push(chunk, torch.from_numpy(np.asarray(f)))
-        for b in range(B):
-            got[b].append(out[b].cpu())
-        pos += f
-        if check is not None:
-            check(dec, pos)
-    for b, rest in enumerate(dec.flush()):
-        got[b].append(rest.cpu())
-    assert (dec.frames == 0).all() and (dec.pending == 0).all()
-    return [torch.cat(g).numpy() for g in got], pos
+from stream_cases import plan, feed, clamp, commit_checker
 
 
 def whole(obs, trans, init, log_probs=True):
@@ -57,15 +16,6 @@ def whole(obs, trans, init, log_probs=True):
     i = None if init is None else torch.from_numpy(np.asarray(init))
     return torbi_amd.from_probabilities(torch.from_numpy(np.ascontiguousarray(obs))[None], None, t, i, log_probs,
                                         gpu=None)[0].numpy()
-
-
-def clamp(obs):
-    """The epsilon round trip from_probabilities applies to log inputs (what the oracle must be given)."""
-    x = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).clone()
-    torch.exp_(x)
-    x += torch.finfo(torch.float32).tiny
-    torch.log_(x)
-    return x.numpy()
 
 
 def check_exact(source, trans, init, pushes, with_oracle=True, log_probs=True):
@@ -167,47 +117,6 @@ def test_probabilities_in(default):
 
 
 # ---------------------------------------------------------------------------------------------- maximal commit
-def reference_arrays(seq, trans, init):
-    """Posterior rows and backpointers with the reference's rules, numpy float32."""
-    T, S = seq.shape
-    post = np.empty((T, S), np.float32)
-    bp = np.zeros((T, S), np.int64)
-    post[0] = seq[0] + init
-    for t in range(1, T):
-        cand = post[t - 1][None, :] + trans
-        nan = np.isnan(cand)
-        masked = np.where(nan, -np.inf, cand)
-        best = np.where(nan[:, 0], np.nan, masked.max(axis=1))
-        bp[t] = np.where(nan[:, 0], 0, masked.argmax(axis=1))
-        post[t] = seq[t] + best
-    return post, bp
-
-
-def decided(bp, n, S):
-    """Frames 0 .. c are decided after n frames: the largest c whose ancestor set of all S states is one state (-1)."""
-    alive = np.arange(S)
-    if S == 1:
-        return n - 1
-    for t in range(n - 1, 0, -1):
-        alive = np.unique(bp[t][alive])
-        if alive.size == 1:
-            return t - 1
-    return -1
-
-
-def commit_checker(source, trans, init):
-    B, S = len(source), source[0].shape[1]
-    bps = [reference_arrays(clamp(source[b]), trans, init)[1] for b in range(B)]
-
-    def check(dec, pos):
-        for b in range(B):
-            n = int(pos[b])
-            want = n - (decided(bps[b], n, S) + 1) if n else 0
-            assert int(dec.pending[b]) == want, (b, n, int(dec.pending[b]), want)
-        assert dec.frames.tolist() == pos.tolist()
-    return check
-
-
 @pytest.mark.parametrize('S', [1, 3, 17, 64])
 @pytest.mark.parametrize('mode', ['one', 'ragged'])
 def test_maximal_commit(S, mode):

@@ -83,6 +83,7 @@ SYMBOLS = {
     'torbi_hip_stream_flush': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
         _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_tile': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
     'torbi_hip_forward_backward_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     'torbi_hip_forward_backward': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,

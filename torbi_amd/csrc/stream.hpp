@@ -49,6 +49,20 @@ __device__ __forceinline__ int slot_of(int base_slot, int r, int cap) {       //
     return (base_slot + r + cap) % cap;
 }
 
+// info[b] fits a ring of `cap` slots to which the call adds `frames` (0 .. max_frames) rows, `room` = min(cap, out_cap)
+// pending rows at the most afterwards: every slot_of() of the stream stays inside its ring, no pending row is overwritten
+// and the output row holds whatever the call may return.  A stream that fails it is left alone by every kernel of the call
+// (ring, memo and output row untouched) and reported as counts[b] = -1.
+__device__ __forceinline__ bool info_fits(const Info &in, int frames, int max_frames, int cap, int room) {
+    return in.pending >= 0 && in.base_slot >= 0 && in.base_slot < cap && frames >= 0 && frames <= max_frames &&
+           in.pending <= room - frames;
+}
+
+// frames a push appends to a stream: info's count, 0 for a stream whose info does not fit
+__device__ __forceinline__ int push_frames(const Info &in, int Tc, int cap, int room) {
+    return info_fits(in, in.frames, Tc, cap, room) ? in.frames : 0;
+}
+
 // G streams of a tile: forward over `frames` new rows each.  obs (B, Tc, S); tt = transition transposed ([prev][next]);
 // every thread owns J consecutive next-states (J = 4: S % 4 == 0, one 16-byte load of the matrix per prev-state feeds
 // 4 * G cells).  Dynamic LDS: 2 * G * S floats.
@@ -56,20 +70,20 @@ template <int G, int J>
 __global__ __launch_bounds__(kThreads) void stream_forward_kernel(const float *__restrict__ obs, int Tc, const Info *__restrict__ info,
                                                                   const float *__restrict__ tt, const float *__restrict__ initial,
                                                                   float *__restrict__ ring, int32_t *__restrict__ memo, int cap,
-                                                                  int B, int S) {
+                                                                  int room, int B, int S) {
     extern __shared__ float rows[];          // [2][G][S]
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * G;
     int tmax = 0;
 #pragma unroll
     for (int g = 0; g < G; ++g)
-        if (b0 + g < B) tmax = max(tmax, info[b0 + g].frames);
+        if (b0 + g < B) tmax = max(tmax, push_frames(info[b0 + g], Tc, cap, room));
     if (tmax == 0) return;
     // the carried rows
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int b = b0 + g;
-        const bool carry = b < B && info[b].frames > 0 && !info[b].fresh;
+        const bool carry = b < B && push_frames(info[b], Tc, cap, room) > 0 && !info[b].fresh;
         const float *src = carry ? ring + ((size_t)b * cap + slot_of(info[b].base_slot, info[b].pending - 1, cap)) * S : nullptr;
         for (int i = tid; i < S; i += kThreads) rows[(size_t)g * S + i] = carry ? src[i] : 0.f;
     }
@@ -115,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void stream_forward_kernel(const float *_
                 const int b = b0 + g;
                 if (b >= B) continue;
                 const Info in = info[b];
-                if (t >= in.frames) continue;
+                if (t >= push_frames(in, Tc, cap, room)) continue;
                 float *dst = ring + ((size_t)b * cap + slot_of(in.base_slot, in.pending + t, cap)) * S;
 #pragma unroll
                 for (int q = 0; q < J; ++q) {
@@ -129,7 +143,8 @@ __global__ __launch_bounds__(kThreads) void stream_forward_kernel(const float *_
         }
         if (tid < G) {
             const int b = b0 + tid;
-            if (b < B && t < info[b].frames) memo[(size_t)b * cap + slot_of(info[b].base_slot, info[b].pending + t, cap)] = 0;
+            if (b < B && t < push_frames(info[b], Tc, cap, room))
+                memo[(size_t)b * cap + slot_of(info[b].base_slot, info[b].pending + t, cap)] = 0;
         }
         __syncthreads();
     }
@@ -169,11 +184,12 @@ __device__ __forceinline__ int wave_backpointer(const float *__restrict__ prev, 
 // prev-states of its matrix row, coalesced), grid = (ceil(S / 4), B).
 __global__ __launch_bounds__(kThreads) void stream_first_step_kernel(const Info *__restrict__ info, const float *__restrict__ trans,
                                                                      const float *__restrict__ ring, int32_t *__restrict__ bp,
-                                                                     int cap, int S) {
+                                                                     int cap, int room, int Tc, int S) {
     const int b = blockIdx.y;
     const Info in = info[b];
-    const int P = in.pending + in.frames;
-    if (in.frames <= 0 || P < 2 || S < 2) return;
+    const int frames = push_frames(in, Tc, cap, room);
+    const int P = in.pending + frames;
+    if (frames <= 0 || P < 2 || S < 2) return;
     const int j = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= S) return;
     const float *prev = ring + ((size_t)b * cap + slot_of(in.base_slot, P - 2, cap)) * S;
@@ -204,26 +220,28 @@ __device__ __forceinline__ int wave_final_state(const float *__restrict__ row, i
 
 // One workgroup per stream.  FLUSH = false: frontier walk + backtrace of the newly decided frames; FLUSH = true: final state +
 // backtrace of every pending frame.  out[b][0 .. count) = the stream's frames base .. base + count - 1; counts[b] = count
-// (-1: the call's info does not fit the ring or the output, nothing written).  Dynamic LDS: 2 * S int32.
+// (-1: the call's info does not fit the ring (info_fits; Tc = frames a push may add) or the output, nothing written).
+// Dynamic LDS: 2 * S int32.
 template <bool FLUSH>
 __global__ __launch_bounds__(kThreads) void stream_walk_kernel(const Info *__restrict__ info, const float *__restrict__ trans,
                                                                const float *__restrict__ ring, int32_t *__restrict__ memo,
                                                                const int32_t *__restrict__ bp, int cap, int32_t *__restrict__ out,
-                                                               int out_cap, int32_t *__restrict__ counts, int S) {
+                                                               int out_cap, int32_t *__restrict__ counts, int Tc, int S) {
     extern __shared__ int32_t lds_i[];
     int32_t *flag = lds_i, *list = lds_i + S;
     __shared__ int32_t count_s, stop_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const Info in = info[b];
-    const int P = in.pending + (FLUSH ? 0 : in.frames);         // pending frames after the forward of this push
+    const int add = FLUSH ? 0 : in.frames;                      // rows the forward of this push appended
     const float *r0 = ring + (size_t)b * cap * S;
     int32_t *mb = memo + (size_t)b * cap;
     auto row = [&](int r) { return r0 + (size_t)slot_of(in.base_slot, r, cap) * S; };
-    if (FLUSH ? in.frames == 0 : in.frames <= 0) { if (tid == 0) counts[b] = 0; return; }
-    if (P > cap || P > out_cap || in.pending < 0 || in.base_slot < 0 || in.base_slot >= cap) {
+    if (in.frames == 0) { if (tid == 0) counts[b] = 0; return; }          // nothing asked of this stream
+    if (!info_fits(in, add, FLUSH ? 0 : Tc, cap, min(cap, out_cap))) {
         if (tid == 0) counts[b] = -1;
         return;
     }
+    const int P = in.pending + add;                             // pending frames after the forward of this push
     int c = -1, m = 0;                                  // newest decided frame (relative to base) and its state
     if (FLUSH) {
         if (P >= 1) {

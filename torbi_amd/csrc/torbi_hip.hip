@@ -2388,6 +2388,20 @@ static int stream_args_ok(const void *info, const void *transition, const void *
     return TORBI_HIP_OK;
 }
 
+// Streams per workgroup of a push's forward kernel (stream_forward_kernel<G, *>): as many as the double-buffered rows let
+// share one pass over the matrix, but no fewer workgroups than compute units while there are streams for them.
+static int stream_tile(int B, int S, int device) {
+    if (B < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (S > stream::kMaxStates) return TORBI_HIP_ERANGE;
+    int G = 16;
+    while (G > 1 && (size_t)2 * G * S * sizeof(float) > (size_t)stream::kMaxLdsBytes) G >>= 1;
+    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
+    while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
+    return G;
+}
+
+int torbi_hip_stream_tile(int B, int S, int device) { return stream_tile(B, S, device); }
+
 int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
                           const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
@@ -2402,22 +2416,18 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
     int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
     int32_t *bp = memo + (size_t)B * capacity;
     if (Tc > 0) {
-        // streams per workgroup: as many as the double-buffered rows let share one pass over the matrix, but no fewer
-        // workgroups than compute units while there are streams for them
-        int G = 16;
-        while (G > 1 && (size_t)2 * G * S * sizeof(float) > (size_t)stream::kMaxLdsBytes) G >>= 1;
-        const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
-        while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
+        const int G = stream_tile(B, S, device);
+        const int room = capacity < out_capacity ? capacity : out_capacity;
         const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(transition_t) & 15) == 0;
         const dim3 grid((B + G - 1) / G);
         const size_t lds = (size_t)2 * G * S * sizeof(float);
 #define TORBI_STREAM_FORWARD(g)                                                                                         \
         if (vec)                                                                                                        \
             hipLaunchKernelGGL((stream::stream_forward_kernel<g, 4>), grid, dim3(stream::kThreads), lds, st, observation, \
-                               Tc, in, transition_t, initial, ring, memo, capacity, B, S);                              \
+                               Tc, in, transition_t, initial, ring, memo, capacity, room, B, S);                              \
         else                                                                                                            \
             hipLaunchKernelGGL((stream::stream_forward_kernel<g, 1>), grid, dim3(stream::kThreads), lds, st, observation, \
-                               Tc, in, transition_t, initial, ring, memo, capacity, B, S)
+                               Tc, in, transition_t, initial, ring, memo, capacity, room, B, S)
         switch (G) {
             case 16: TORBI_STREAM_FORWARD(16); break;
             case 8: TORBI_STREAM_FORWARD(8); break;
@@ -2429,12 +2439,12 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
         if ((code = (int)hipGetLastError()) != hipSuccess) return code;
         if (S > 1) {
             hipLaunchKernelGGL(stream::stream_first_step_kernel, dim3((S + 3) / 4, B), dim3(stream::kThreads), 0, st, in,
-                               transition, ring, bp, capacity, S);
+                               transition, ring, bp, capacity, room, Tc, S);
             if ((code = (int)hipGetLastError()) != hipSuccess) return code;
         }
     }
     hipLaunchKernelGGL(stream::stream_walk_kernel<false>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t), st,
-                       in, transition, ring, memo, bp, capacity, indices_out, out_capacity, counts_out, S);
+                       in, transition, ring, memo, bp, capacity, indices_out, out_capacity, counts_out, Tc, S);
     return (int)hipGetLastError();
 }
 
@@ -2448,7 +2458,7 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
     int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
     hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
                        static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ring, memo,
-                       memo + (size_t)B * capacity, capacity, indices_out, out_capacity, counts_out, S);
+                       memo + (size_t)B * capacity, capacity, indices_out, out_capacity, counts_out, 0, S);
     return (int)hipGetLastError();
 }
 

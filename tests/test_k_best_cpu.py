@@ -12,40 +12,9 @@ import torch
 import oracle
 import torbi_amd
 from torbi_amd import _lib, synth
+from k_best_cases import brute, same, clamp, model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-f32 = np.float32
-
-
-def brute(obs, frames, trans, init, k):
-    """Every path scored in float32 with the contract's order of additions, ranked by the recursive tie rule: at frame t
-    the paths into state j are ordered by c = fl(v_{t-1} + A[j, i]) descending, then by i, then by the rank of their
-    prefix among the paths into i at t - 1; the result by (value descending, last state, rank)."""
-    B, T, S = obs.shape
-    indices = np.full((B, k, T), -1, dtype=np.int32)
-    scores = np.full((B, k), -np.inf, dtype=np.float32)
-    for b in range(B):
-        F = int(min(max(frames[b], 1), T))
-        # ranked[j] = [(value, path)] in order
-        ranked = [[(f32(obs[b, 0, j]) + f32(init[j]), [j])] for j in range(S)]
-        for t in range(1, F):
-            new = []
-            for j in range(S):
-                cands = []
-                for i in range(S):
-                    for r, (v, path) in enumerate(ranked[i]):
-                        c = f32(v) + f32(trans[j, i])
-                        cands.append((-c, i, r, c, path))
-                cands.sort(key=lambda x: (x[0], x[1], x[2]))
-                new.append([(f32(obs[b, t, j]) + c, path + [j]) for (_, _, _, c, path) in cands])
-            ranked = new
-        final = [(-v, j, r, v, path) for j in range(S) for r, (v, path) in enumerate(ranked[j])]
-        final.sort(key=lambda x: (x[0], x[1], x[2]))
-        for q, (_, _, _, v, path) in enumerate(final[:k]):
-            scores[b, q] = v
-            indices[b, q, :F] = path
-            indices[b, q, F:] = path[-1]
-    return indices, scores
 
 
 def host(obs, frames, trans, init, k):
@@ -54,29 +23,6 @@ def host(obs, frames, trans, init, k):
                                 torch.as_tensor(init), log_probs=True, gpu=None)
     assert i.dtype == torch.int32 and s.dtype == torch.float32 and i.shape == (obs.shape[0], k, obs.shape[1])
     return i.numpy(), s.numpy()
-
-
-def same(got, want):
-    assert np.array_equal(got[0], want[0]), (got[0], want[0])
-    assert np.array_equal(got[1].view(np.int32), want[1].view(np.int32)), (got[1], want[1])
-
-
-def clamp(x):
-    """The epsilon round trip best_paths applies to a log observation (torch's CPU ops, as on the host route)."""
-    return torbi_amd.viterbi.epsilon_clamp_(torch.tensor(x, dtype=torch.float32)).numpy()
-
-
-def model(B, T, S, seed, ties):
-    rng = np.random.default_rng(seed)
-    if ties:        # small integers: ties everywhere
-        obs = -rng.integers(0, 3, (B, T, S)).astype(np.float32)
-        trans = -rng.integers(0, 3, (S, S)).astype(np.float32)
-        init = -rng.integers(0, 2, (S,)).astype(np.float32)
-    else:
-        obs = rng.standard_normal((B, T, S)).astype(np.float32)
-        trans = rng.standard_normal((S, S)).astype(np.float32)
-        init = rng.standard_normal(S).astype(np.float32)
-    return obs, trans, init
 
 
 @pytest.mark.parametrize('S,T,B,seed', [(S, T, B, seed) for (S, T, B, seed) in

@@ -8,6 +8,7 @@ import torch
 
 import torbi_amd
 from torbi_amd import synth
+from k_best_cases import step_items
 
 pytestmark = pytest.mark.gpu
 
@@ -43,20 +44,6 @@ def ragged(B, T, seed):
 
 def banded(S, tiny):
     return synth.banded_transition(S, max(1.5, S / 16.5), tiny=tiny).astype(np.float32)
-
-
-def step_items(B, S, k):
-    """(KMAX, G) of the step launch for this shape (torbi_hip.hip kb_step): the rule depends on B, S and k only."""
-    kmax = 1
-    while kmax < k:
-        kmax *= 2
-    G = min(8, max(1, 16 // kmax))
-    while G > 1 and G * S * 4 > 64 * 1024:
-        G //= 2
-    jblocks = -(-S // 256)
-    while G > 1 and -(-B // G) * jblocks < 512:
-        G //= 2
-    return kmax, G
 
 
 # every step instance with more than one item per workgroup; B is not a multiple of G, so the last group has a tail

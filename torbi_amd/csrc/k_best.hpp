@@ -421,7 +421,9 @@ __global__ __launch_bounds__(64) void kb_walk_kernel(const int32_t *__restrict__
     }
     const Final f = final_[(size_t)b * k + q];
     scores[(size_t)b * k + q] = f.score;
-    int s = f.state, r = f.rank;
+    // (in range by construction, like the pointers below: a selection round that found no entry would leave its start
+    // values here, 0x7fffffff, and the first pointer read would leave the workspace)
+    int s = min(max(f.state, 0), S - 1), r = min(max(f.rank, 0), k - 1);
     for (int t = F; t < T; ++t) row[t] = s;
     for (int t = F - 1; t >= 1; --t) {
         row[t] = s;

@@ -2631,6 +2631,59 @@ def test_backtrace_in_speculative_segments_is_the_whole_path(path, segments, mon
             assert int(stats[123]) <= int(stats[122])
 
 
+LADDER_STATES = (70, 512, 516, 1536, 1540, 2048, 2052)      # on and just above every step; 70: S % 4 != 0
+# route -> (path named, items, state counts): launch_backtrace_on has no instance above 1536 states to tell apart
+LADDER_ROUTES = {'resident': ('resident', 20, LADDER_STATES), 'rows': ('pruned', 8, LADDER_STATES),
+                 'dense': ('dense', 32, tuple(S for S in LADDER_STATES if S <= 1540)), 'band': ('band', 20, LADDER_STATES)}
+
+def _ladder_problem(route, S):
+    """Observations, lengths, matrix and initial vector of one (route, state count); ragged lengths that include 1, 2 and T.
+    Every sequence's last frame, and one frame inside each of three or more, carries 64 on top of one state of the last
+    lane quad, S-4 .. S-1: scores lie in [-16, 0], a path around that state wins at most 48 elsewhere, so the best path
+    passes through it -- through states that only the instance picked for exactly this state count reads."""
+    _, B, _ = LADDER_ROUTES[route]
+    T = 9
+    obs, trans, init = synth.problem(B, T, S, seed=S)
+    if route == 'band':
+        trans = _banded(S, 9, 14, seed=S)
+    frames = np.full((B,), T, np.int32)
+    frames[:6] = [1, 2, T, 5, 3, 8]
+    for b in range(B):
+        for t in {int(frames[b]) - 1, int(frames[b]) // 2}:
+            obs[b, t, S - 1 - b % 4] += np.float32(64.0)
+    return obs, frames, trans, init
+
+
+@pytest.mark.parametrize('segments', ['1', '8'])
+@pytest.mark.parametrize('route', sorted(LADDER_ROUTES))
+def test_backtrace_instances_on_and_above_every_state_count_step(route, segments, monkeypatch):
+    """The backtrace kernels come in instances for up to 512, 1536, 2048 and 4096 states (a lane holds 2, 6, 8 or 16 float4
+    of a posterior row), picked by the host from the state count: the time-resident gather walk (whole paths and speculative
+    segments), the sorted-row scan's gather walk, the dense route's ranged / whole-row kernels (steps at 512 and 1536 only)
+    and the band walk.  Decoded here ON every step and one lane quad above it, and at a state count that is no multiple of
+    4 (whole-row kernels without vector loads), with ragged lengths that include 1, 2 and T: the route the call reports and
+    the oracle's indices.  An instance launched for more states than its lanes hold ignores the states above 256 per float4
+    and reads nothing out of bounds, so the data put every last state and one inner state of each path into the last lane
+    quad (asserted on the oracle's paths first): a threshold that moved up then decodes other indices at these counts."""
+    monkeypatch.setenv('TORBI_HIP_BACKTRACE_SEGMENTS', segments)
+    dev = torch.device('cuda:0')
+    path, B, states = LADDER_ROUTES[route]
+    if route == 'band':         # the state counts the band kernel covers for this reach (S % 4 == 0 among them)
+        states = tuple(S for S in states if torbi_amd._lib.load().torbi_hip_band_members(B, S, 9, 14, 0) > 0)
+        for step in (512, 1536):
+            assert any(S <= step for S in states) and any(S > step for S in states), states
+    for S in states:
+        obs, frames, trans, init = _ladder_problem(route, S)
+        want = oracle.decode(obs, frames, trans, init, num_threads=oracle.max_threads())      # (remembered by content: once per S)
+        last, inner = want[np.arange(B), frames - 1], want[np.arange(B), frames // 2][frames >= 3]
+        assert last.min() >= S - 4 and inner.min() >= S - 4, (S, last, inner)           # the paths do visit the last quad
+        args = [torch.as_tensor(np.ascontiguousarray(x)).to(dev) for x in (obs, frames, trans, init)]
+        prof = []
+        got = torbi_amd.decode(*args, path=path, _profile=prof).cpu().numpy()
+        assert viterbi.ROUTES[int(prof[3])] == route, (S, viterbi.ROUTES[int(prof[3])])
+        np.testing.assert_array_equal(got, want, err_msg=f'{route} {S} states, {segments} segments')
+
+
 def test_cluster_exchange_survives_the_one_nan_it_uses_as_absent(monkeypatch):
     """The cluster form's exchange marks a slice that has not arrived with one NaN bit pattern (resident_forward.hpp,
     kAbsentBits).  NaNs are out of contract -- but an observation that carries exactly that pattern must not hang the

@@ -1,5 +1,5 @@
 """One decode call of one batch in the cluster form (GPU box): forward us per timestep, backtrace, equality with the
-per-timestep path.  Environment: TORBI_HIP_LIBRARY (variant build), TORBI_HIP_CLUSTER_R, TORBI_HIP_CLUSTER_KW6.
+per-timestep path.  Environment: TORBI_HIP_LIBRARY (variant build).
     python tools/single_call_probe.py [T] [S] [B ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

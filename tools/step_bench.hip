@@ -12,8 +12,12 @@
 
 template <int BL, int JL, int NW, int KC, int MSL = 8>
 void run(int B, int T, int S, int reps) {
-    dense::Plan pl = dense::make_plan(B, S, 256, BL, NW);
-    if (pl.NW != NW || pl.KC != KC) { printf("plan NW/KC %d/%d != %d/%d, skip\n", pl.NW, pl.KC, NW, KC); return; }
+    dense::Plan pl = dense::make_plan(B, S, 256);
+    if (pl.BL != BL) { printf("plan BL %d != %d, skip\n", pl.BL, BL); return; }
+    pl.NW = NW;                    // (the library's plan is 8 waves x 12-row chunks; the variants are this probe's own)
+    pl.KC = KC;
+    pl.NCH = (S + KC - 1) / KC;
+    pl.Kp = pl.NCH * KC;
     if (getenv("NJT")) {           // experiment: force the number of state tiles
         pl.n_jt = atoi(getenv("NJT"));
         pl.JT = (S + pl.n_jt - 1) / pl.n_jt;

@@ -44,16 +44,16 @@ __device__ unsigned long long timing_buf[4096 * 8];
 
 
 struct Plan {
-    int BL;     // batch items per lane (8 or 4); batch tile width BT = 8*BL
+    int BL;     // batch items per lane (8; the kernel also takes 4); batch tile width BT = 8*BL
     int BT;
     int JL;     // next-states per lane (2, 4 or 6); state panel row width W = 8*JL
     int W;
     int n_bt;   // batch tiles
     int n_jt;   // state tiles
     int JT;     // next-states per tile (<= W)
-    int NW;     // waves per workgroup = contraction slices (8 or 16)
+    int NW;     // waves per workgroup = contraction slices (8; the kernel also takes 16)
     int MSL;    // partial tiles merged through LDS at once (8; 4 = small-footprint variant)
-    int KC;     // prev-state rows staged per chunk (12 with 8 waves, 6 with 16)
+    int KC;     // prev-state rows staged per chunk (12 with 8 waves; 6 with 16)
     int Kp;     // padded contraction length (multiple of KC) >= S
     int NCH;    // chunks of KC prev-state rows per panel = Kp / KC
     int RB;     // XCD region: RB batch tiles x RJ state tiles per XCD (L2 locality only)
@@ -63,21 +63,20 @@ struct Plan {
 //  * BT = 32 doubles the number of workgroups (two co-resident per CU, 4 waves per SIMD): a
 //    wave can issue one VALU instruction per ~4 cycles but a SIMD retires two, so stalls of
 //    one wave are only hidden when >= 3-4 waves share the SIMD.  BT = 64 halves the L2->LDS
-//    operand traffic instead.  `bl_override` (0 = heuristic) exists for experiments.
+//    operand traffic instead, and measured faster: 40.6 us/step (BL=8) vs 43.2 (BL=4) at B=512,S=1440.
 //  * JL is chosen to minimise rounds * W (every workgroup computes all W state slots).
-inline Plan make_plan(int B, int S, int num_cus, int bl_override = 0, int nw_override = 0) {
+inline Plan make_plan(int B, int S, int num_cus) {
     Plan best{};
     const int cus = num_cus > 0 ? num_cus : 256;
-    const int BL = bl_override ? bl_override : 8;   // measured: 40.6 us/step (BL=8) vs 43.2 (BL=4) at B=512,S=1440
+    const int BL = 8;
     const int BT = 8 * BL;
-    const int per_cu = BL == 4 ? 2 : 1;         // co-resident workgroups per CU
     const int n_bt = (B + BT - 1) / BT;
     long best_cost = -1;
     for (int JL = 6; JL >= 2; JL -= 2) {
         const int W = 8 * JL;
         const int min_jt = (S + W - 1) / W;
         const long tiles = (long)n_bt * min_jt;
-        const long slots = (long)cus * per_cu;
+        const long slots = (long)cus;           // one workgroup per CU
         const long rounds = (tiles + slots - 1) / slots;
         const long cost = rounds * W;
         if (best_cost < 0 || cost < best_cost) {
@@ -97,9 +96,9 @@ inline Plan make_plan(int B, int S, int num_cus, int bl_override = 0, int nw_ove
     // 8 waves x 12-row chunks.  A 16-wave / 6-row variant (4 waves per SIMD, two-round merge) was
     // measured: its waves finish the contraction staggered (mean 48.7K ticks instead of 66.5K) but
     // the workgroup ends no earlier (42.1 vs 40.4 us/step) -- the SIMD's VALU throughput for this
-    // instruction mix does not improve with occupancy.  `nw_override` = 16 still selects it.
-    best.NW = (nw_override == 16 && BL == 8 && best.JL == 6) ? 16 : 8;
-    best.KC = best.NW == 16 ? 6 : 12;
+    // instruction mix does not improve with occupancy.  (tools/step_bench.hip still times it.)
+    best.NW = 8;
+    best.KC = 12;
     // (a small-footprint variant -- 8-row chunks, 4 merge slices, 57 KB LDS, 128 VGPRs, two
     // workgroups of two in-flight decodes per CU -- was measured at 44.1 vs 37.3 us per step: the
     // SIMDs are VALU-bound, extra resident waves only add staging overhead)

@@ -207,85 +207,22 @@ __global__ __launch_bounds__(64) void backtrace_prefetch_kernel(const float *__r
 // ---------------------------------------------------------------------------------------
 // The same backtrace where the forward pass left SORTED transition rows (pruned / time-resident paths): per path
 // step the argmax_i fl(hist[t-1][i] + trans[j][i]) is found by walking row j in descending transition order, 64
-// entries per wave step, against the posterior row held in the LDS:
+// entries per wave step:
 //     every entry not yet examined has trans <= t_next (the next chunk's first entry) and hist <= hmax, so its
 //     candidate is <= fl(t_next + hmax); once that is < the best candidate seen, no unexamined entry can reach --
 //     or TIE -- the maximum, and the lowest prev-state among the examined maxima is the reference's backpointer
 //     (viterbi.cpp:94-100).
-// A step then moves the 4S-byte posterior row (prefetched one step ahead, coalesced) plus 0.5-1 KB of list instead
-// of the posterior row plus a 4S-byte transition row: with 4096 items in flight (a launch group of 8 batches) the
-// backtrace is bound by exactly that traffic.  List entries are {t, prev-state << shift}; (-inf) entries and the
-// row padding carry a stand-in prev-state, which matters only when EVERY candidate is -inf: the reference's scan
-// then keeps prev-state 0, and so does this.
-// One wave per item; dynamic LDS = 4 * ceil4(S) bytes per wave; S % 4 == 0, S <= 256 * NQ.
+// List entries are {t, prev-state << shift}; (-inf) entries and the row padding carry a stand-in prev-state, which
+// matters only when EVERY candidate is -inf: the reference's scan then keeps prev-state 0, and so does this.
+// One wave per item; S % 4 == 0, S <= 256 * NQ.
+//
+// The posteriors the list chunk points at are gathered straight from the history (64 four-byte reads touch ~46 of a
+// 1440-state row's 90 sectors), and the row maximum the bound needs comes from `rowmax`, which the forward kernel leaves
+// behind for every row.  A step moves 0.5-1 KB of list and those sectors instead of a posterior row plus a 4S-byte
+// transition row.  (The form that staged every posterior row in the LDS -- one dependent load a step instead of two, all
+// 90 sectors -- lost from one 512-item batch, 0.80 against 0.58 ms, to a launch group of eight, 3.11 against 1.86 ms: 4096
+// paths moved 11.8 GB through row staging.  profiles/r03_backtrace_gather.txt; removed.)
 // ---------------------------------------------------------------------------------------
-template <int NQ>
-__device__ __forceinline__ void backtrace_sorted_item(const float *__restrict__ h, const float2 *__restrict__ sorted,
-                                                      int SpP, int shift, int f, int32_t *__restrict__ o, int T, int S,
-                                                      int lane, float *__restrict__ hrow) {
-    f = f < 1 ? 1 : (f > T ? T : f);
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 nxt[NQ];
-    auto load_row = [&](float4 (&dst)[NQ], int r) {
-        const float *row = h + (size_t)r * S;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = 4 * lane + 256 * q;
-            dst[q] = i < S ? *reinterpret_cast<const float4 *>(row + i) : zero;
-        }
-    };
-    load_row(nxt, f - 1);
-    // final state = first argmax of the last posterior row (viterbi.cpp:218)
-    int j = wave_first_argmax4<NQ>(nxt, lane, S);
-    asm volatile("" : "+v"(j));                              // (the row below is requested behind the argmax: one row live)
-    load_row(nxt, f >= 2 ? f - 2 : 0);
-    // every position t >= frames-1 holds the final state (viterbi.cpp:219-221)
-    for (int tt = f - 1 + lane; tt < T; tt += 64) o[tt] = j;
-    const int Sp = (S + 15) / 16 * 16;
-
-    for (int tt = f - 1; tt >= 1; --tt) {
-        // the list of the state just resolved (depends on j): first chunk on its way ...
-        const float2 *row = sorted + (size_t)j * SpP;
-        float2 ent = row[lane];
-        // ... while posterior row tt-1 (already in registers) goes to the LDS; row tt-2 is requested behind it, into the
-        // same registers (one row live, not two: 42 registers instead of 61, so the kernel fits beside the three
-        // 152-register forward waves per SIMD of the next launch group; DESIGN.md 4.12 for what that is worth)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = 4 * lane + 256 * q;
-            if (i < S) *reinterpret_cast<float4 *>(hrow + i) = nxt[q];
-        }
-        const float hmax = wavered::wave_reduce_f32(lane_max<NQ>(nxt, lane, S), wavered::MaxOp());
-        load_row(nxt, tt >= 2 ? tt - 2 : 0);
-        float bv = -INFINITY;
-        int bi = kSentinel;
-        float best = -INFINITY;
-        for (int k0 = 0; k0 < Sp; k0 += 64) {
-            const int kn = k0 + 64 + lane;
-            const float2 ahead = row[kn < SpP ? kn : SpP - 1];       // next chunk (its first entry bounds the rest)
-            if (k0 + lane < Sp) {
-                const int i = __float_as_int(ent.y) >> shift;
-                const float c = hrow[i] + ent.x;
-                if (c > bv || (c == bv && i < bi)) { bv = c; bi = i; }
-            }
-            best = wavered::wave_reduce_f32(bv, wavered::MaxOp());
-            const float tn = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__float_as_int(ahead.x)));
-            ent = ahead;
-            if (k0 + 64 >= Sp || tn + hmax < best) break;
-        }
-        // lowest prev-state among the lanes that hold the maximum; all candidates -inf: prev-state 0
-        const int cand = (bv == best && bi != kSentinel) ? bi : kSentinel;
-        const int win = wavered::wave_min_i32(cand);
-        j = best == -INFINITY ? 0 : win;
-        if (lane == 0) o[tt - 1] = j;
-    }
-}
-
-// The same walk without staging posterior rows: the posteriors the list chunk points at are gathered straight from the
-// history (64 four-byte reads touch ~46 of a 1440-state row's 90 sectors; staging reads all of them), and the row maximum
-// the bound needs comes from `rowmax`, which the time-resident forward kernel leaves behind for every row.  A step is two
-// dependent loads (list chunk, then posteriors) instead of one -- and still the faster form from one 512-item batch (0.58
-// against 0.80 ms) to a launch group of eight (1.86 against 3.11 ms: 4096 paths move 11.8 GB through row staging).
 template <int NQ>
 struct GatherWalker {
     const float *__restrict__ h;          // [T][S] posterior rows of the item
@@ -426,17 +363,6 @@ __device__ __forceinline__ void backtrace_gather_item(const float *__restrict__ 
                                                       int32_t *__restrict__ o, int T, int S, int lane) {
     const GatherWalker<NQ> w{h, rowmax, sorted, SpP, shift, S, lane};
     walk_item(w, f, o, T, lane);
-}
-
-template <int NQ>
-__global__ __launch_bounds__(64) void backtrace_sorted_kernel(const float *__restrict__ hist,
-                                                              const float2 *__restrict__ sorted, int SpP, int shift,
-                                                              const int32_t *__restrict__ frames,
-                                                              int32_t *__restrict__ out, int B, int T, int S) {
-    extern __shared__ __attribute__((aligned(16))) float hrow_lds[];
-    const int b = blockIdx.x;
-    backtrace_sorted_item<NQ>(hist + (size_t)b * T * S, sorted, SpP, shift, frames[b], out + (size_t)b * T, T, S,
-                              threadIdx.x, hrow_lds);
 }
 
 template <int NQ>

@@ -913,27 +913,8 @@ __device__ __forceinline__ int batch_of_item(const Group &grp, int item) {
     return k;
 }
 
-template <int NQ>
-__global__ __launch_bounds__(64) void group_backtrace_prefetch_kernel(Group grp, const float *__restrict__ trans, int S) {
-    const Batch &bat = grp.batch[batch_of_item(grp, blockIdx.x)];
-    const int b = (int)blockIdx.x - bat.item0;
-    lazy::backtrace_prefetch_item<NQ>(bat.hist + (size_t)b * bat.T * S, trans, bat.frames[b], bat.out + (size_t)b * bat.T,
-                                      bat.T, S, threadIdx.x);
-}
-
-template <int NQ>
-__global__ __launch_bounds__(64) void group_backtrace_sorted_kernel(Group grp, const float2 *__restrict__ sorted, int SpP,
-                                                                    int S) {
-    extern __shared__ __attribute__((aligned(16))) float hrow_lds[];
-    const Batch &bat = grp.batch[batch_of_item(grp, blockIdx.x)];
-    const int b = (int)blockIdx.x - bat.item0;
-    // (list offsets = state * bytes of a tile row: 64 with 16-item tiles, 32 with 8-item tiles)
-    lazy::backtrace_sorted_item<NQ>(bat.hist + (size_t)b * bat.T * S, sorted, SpP, tile_items(S) == kNI ? 6 : 5,
-                                    bat.frames[b], bat.out + (size_t)b * bat.T, bat.T, S, threadIdx.x, hrow_lds);
-}
-
-// the same with the posteriors gathered from the history where the list points (no row staging): for launches with many
-// waves per compute unit, which are bound by the bytes they move, not by the latency of a step (lazy_backtrace.hpp)
+// the walk down the sorted transition rows, the posteriors gathered from the history where the list points (GatherWalker,
+// lazy_backtrace.hpp); list offsets = state * bytes of a tile row: 64 with 16-item tiles, 32 with 8-item tiles
 template <int NQ>
 __global__ __launch_bounds__(64) void group_backtrace_gather_kernel(Group grp, const float2 *__restrict__ sorted, int SpP, int S) {
     const Batch &bat = grp.batch[batch_of_item(grp, blockIdx.x)];

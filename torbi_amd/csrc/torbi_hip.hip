@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include <stdint.h>
 #include <stddef.h>
@@ -555,19 +556,13 @@ inline int cluster_members(int tiles, int S, int cus) {
     return R < 2 ? 1 : R;
 }
 
-// AUTO takes the held-matrix kernel up to this many items (TORBI_HIP_HELD_ITEMS overrides; 0 = never).  tools/held_probe.py,
+// AUTO takes the held-matrix kernel up to this many items.  tools/held_probe.py,
 // ms per decode against the best per-timestep kernel (profiles/r03_held_probe.txt): 500 frames x 1440 states 1 item
 // 1.10 / 2.41, 2 items 1.38 / 2.52, 3 items 2.16 / 2.69, 4 items 2.83 / 2.85, 8 items 5.44 / 4.31; 300 frames x 4096 states
 // 1 item 1.28 / 3.87, 2 items 1.86 / 4.20, 4 items 3.79 / 5.95, 8 items 7.41 / 9.34.  A timestep of the kernel costs one
 // hand-off (~1.5 us) for up to two sequences and ~1.3 us of instruction issue for every further one; a launch of the
 // per-timestep kernels 4.4 us plus ~0.3 us per item.
-inline bool held_auto(int B, int S) {
-    static const int limit = [] {
-        const char *e = getenv("TORBI_HIP_HELD_ITEMS");
-        return e ? atoi(e) : -1;
-    }();
-    return B <= (limit >= 0 ? limit : S > held::kSmallS ? 8 : 3);
-}
+inline bool held_auto(int B, int S) { return B <= (S > held::kSmallS ? 8 : 3); }
 
 // route of ONE batch.  AUTO: the time-resident kernel -- whole tiles per workgroup when the batch alone gives at least
 // half the compute units a workgroup, tiles split over clusters of workgroups for smaller batches of >= 17 items --
@@ -575,12 +570,8 @@ inline bool held_auto(int B, int S) {
 inline bool small_block_auto(int B, int S, int cus) {
     // (value-only since round 5: ahead of the time-resident kernels at every batch size up to 192 states -- 8192 x 200 x 128
     // 2.0 against 4.0 ms, 8192 x 100 x 192 2.8 against 3.0 -- and up to ~3000 sequences at 256: 2048 x 200 x 256 1.6 against
-    // 2.3 ms, 4096 x 200 x 256 3.2 against 2.9.  TORBI_HIP_SMALL_BLOCK_LIMIT: cells per compute unit, in units of 65536)
-    static const long long limit = [] {
-        const char *e = getenv("TORBI_HIP_SMALL_BLOCK_LIMIT");
-        return e ? atoll(e) : 12ll;
-    }();
-    return small::block_supported(S) && (S <= 192 || (long long)B * S * S <= (limit << 16) * cus);
+    // 2.3 ms, 4096 x 200 x 256 3.2 against 2.9.  The limit: 12 x 65536 cells per compute unit)
+    return small::block_supported(S) && (S <= 192 || (long long)B * S * S <= (12ll << 16) * cus);
 }
 inline Route route_for(int path, int B, int S, int cus, bool allow_held = true) {
     if (path == TORBI_HIP_FORWARD_BAND) path = TORBI_HIP_FORWARD_AUTO;     // (a band is known to torbi_hip_viterbi_decode_banded only)
@@ -823,29 +814,9 @@ struct DenseWorkspace {
     size_t bytes;
 };
 
-// TORBI_HIP_BL=4|8 forces the batch-tile width of the dense path (experiments; default heuristic)
-inline int bl_override() {
-    static const int v = [] {
-        const char *e = getenv("TORBI_HIP_BL");
-        const int x = e ? atoi(e) : 0;
-        return (x == 4 || x == 8) ? x : 0;
-    }();
-    return v;
-}
-
-// TORBI_HIP_NW=8|16 forces the waves per workgroup of the 8x6 dense tile (experiments)
-inline int nw_override() {
-    static const int v = [] {
-        const char *e = getenv("TORBI_HIP_NW");
-        const int x = e ? atoi(e) : 0;
-        return (x == 8 || x == 16) ? x : 0;
-    }();
-    return v;
-}
-
 inline DenseWorkspace carve_dense(void *base, int B, int T, int S, int cus) {
     DenseWorkspace w;
-    w.plan = dense::make_plan(B, S, cus, bl_override(), nw_override());
+    w.plan = dense::make_plan(B, S, cus);
     char *p = static_cast<char *>(base);
     const size_t panel_bytes = align_up(sizeof(float) * (size_t)w.plan.n_bt * w.plan.Kp * w.plan.BT, 256);
     const size_t trp_bytes = align_up(sizeof(float) * (size_t)w.plan.n_jt * w.plan.Kp * w.plan.W, 256);
@@ -996,11 +967,10 @@ hipError_t launch_held_forward(const float *obs, const int32_t *frames, const fl
     if (launches) *launches = 1;
     if (T < 2) return hipGetLastError();
     // how long a workgroup waits for the others before it gives up (ticks of the 100 MHz wall clock): 20 x T x 2.5 us, at
-    // least 2 ms -- 25 ms for 500 frames, against the ~1 ms the launch takes when it is resident.  TORBI_HIP_HELD_WAIT_US
-    // overrides; TORBI_HIP_HELD_SPIN_LIMIT (polls of ~1 us, the round-3 knob; 0 forces the repair path in the tests) too.
+    // least 2 ms -- 25 ms for 500 frames, against the ~1 ms the launch takes when it is resident.  TORBI_HIP_HELD_SPIN_LIMIT
+    // overrides (polls of ~1 us; 0 forces the repair path in the tests).
     unsigned long long wait_ticks = std::max<unsigned long long>(200000ull, 5000ull * (unsigned long long)T);
-    if (const char *us = getenv("TORBI_HIP_HELD_WAIT_US")) wait_ticks = 100ull * strtoull(us, nullptr, 10);
-    else if (const char *polls = getenv("TORBI_HIP_HELD_SPIN_LIMIT")) wait_ticks = 100ull * strtoull(polls, nullptr, 10);
+    if (const char *polls = getenv("TORBI_HIP_HELD_SPIN_LIMIT")) wait_ticks = 100ull * strtoull(polls, nullptr, 10);
     const dim3 grid(held::workgroups(S)), block(held::block_threads(S));
     const int K = (S + held::threads(S) - 1) / held::threads(S);
 #define TORBI_HELD(K_, R_, N_)                                                                                       \
@@ -1080,6 +1050,20 @@ hipError_t launch_small(const float *obs, const int32_t *frames, const float *tr
         default: return launch_small_as<64, 4>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
     }
 }
+
+// THE ladder from a state count to a backtrace instance: a lane of those kernels holds NQ float4 of a posterior row, which
+// covers S <= 256 * NQ states.  Calls f(std::integral_constant<int, NQ>) for the first NQ of the list that covers S (the
+// last one when none does: the callers have bounded S); without a list 2, 6, 8, 16 -- steps at 512, 1536 and 2048 states.
+template <int NQ, int... MORE, class F>
+inline void by_state_count(int S, F &&f) {
+    if constexpr (sizeof...(MORE) == 0) f(std::integral_constant<int, NQ>());
+    else if (S <= 256 * NQ) f(std::integral_constant<int, NQ>());
+    else by_state_count<MORE...>(S, f);
+}
+// (overload resolution keeps the two apart: an int as first template argument does not fit `class F`, so a call with a list
+// sees the form above alone, and a call without one cannot deduce NQ and sees the form below alone)
+template <class F>
+inline void by_state_count(int S, F &&f) { by_state_count<2, 6, 8, 16>(S, f); }
 
 // 65 .. 256 states: the value-only workgroup kernel + backtrace launches of their own (small_states.hpp, block_value_kernel)
 inline int backtrace_segments(int items);
@@ -1178,12 +1162,8 @@ hipError_t launch_dense_forward(const float *obs, const int32_t *frames, const f
     if (pl.BL == BL_ && pl.JL == JL_ && pl.NW == NW_ && pl.KC == KC_ && pl.MSL == MSL_)         \
         return launch_dense_steps<BL_, JL_, NW_, KC_, MSL_>(obs, frames, w, B, T, S, stream, launches, clock_out)
     TORBI_DENSE_CASE(8, 6, 8, 12, 8);
-    TORBI_DENSE_CASE(8, 6, 16, 6, 8);
     TORBI_DENSE_CASE(8, 4, 8, 12, 8);
     TORBI_DENSE_CASE(8, 2, 8, 12, 8);
-    TORBI_DENSE_CASE(4, 6, 8, 12, 8);
-    TORBI_DENSE_CASE(4, 4, 8, 12, 8);
-    TORBI_DENSE_CASE(4, 2, 8, 12, 8);
 #undef TORBI_DENSE_CASE
     return hipErrorInvalidValue;
 }
@@ -1212,19 +1192,16 @@ hipError_t launch_backtrace_on(const float *hist, const float *trans, const int3
     const bool vec = (S % 4 == 0) && ((reinterpret_cast<uintptr_t>(trans) & 15) == 0);
     if (vec && S <= 256 * 16) {
         if (!ranges) widest = nullptr;
-#define TORBI_BT_CASE(NQ_)                                                                          \
-    if (S <= 256 * NQ_) {                                                                           \
-        if (ranges)                                                                                 \
-            hipLaunchKernelGGL(lazy::backtrace_ranged_kernel<NQ_>, dim3(B), dim3(64), 0, stream, hist, trans, ranges, \
-                               widest, frames, out, B, T, S);                                       \
-        hipLaunchKernelGGL(lazy::backtrace_prefetch_kernel<NQ_>, dim3(B), dim3(64), 0, stream, hist, \
-                           trans, frames, out, B, T, S, widest);                                    \
-        return hipGetLastError();                                                                   \
-    }
-        TORBI_BT_CASE(2)
-        TORBI_BT_CASE(6)
-        TORBI_BT_CASE(16)
-#undef TORBI_BT_CASE
+        // (three steps, no <8>: 1537 .. 2048 states take the <16> instances here)
+        by_state_count<2, 6, 16>(S, [&](auto nq) {
+            constexpr int NQ = decltype(nq)::value;
+            if (ranges)
+                hipLaunchKernelGGL(lazy::backtrace_ranged_kernel<NQ>, dim3(B), dim3(64), 0, stream, hist, trans, ranges,
+                                   widest, frames, out, B, T, S);
+            hipLaunchKernelGGL(lazy::backtrace_prefetch_kernel<NQ>, dim3(B), dim3(64), 0, stream, hist,
+                               trans, frames, out, B, T, S, widest);
+        });
+        return hipGetLastError();
     }
     if (vec)
         hipLaunchKernelGGL(lazy::backtrace_kernel<4>, dim3(B), dim3(64), 0, stream, hist, trans,
@@ -1235,54 +1212,20 @@ hipError_t launch_backtrace_on(const float *hist, const float *trans, const int3
     return hipGetLastError();
 }
 
-// backtrace over the SORTED transition rows the pruned / time-resident forward pass prepared (lazy_backtrace.hpp):
-// a path step reads the posterior row + 0.5-1 KB of list instead of the posterior row + a whole transition row.
-// TORBI_HIP_BACKTRACE=rows selects the transition-row form everywhere (experiments).
-inline bool backtrace_sorted_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("TORBI_HIP_BACKTRACE");
-        return !(e && e[0] == 'r');
-    }();
-    return v;
-}
-
-// (`rowmax`: the row maxima the forward pass left, or null: with them the walk gathers instead of staging rows)
+// backtrace over the SORTED transition rows the sorted-row scan prepared (lazy_backtrace.hpp): a path step reads 0.5-1 KB of
+// list and the posteriors it points at instead of the posterior row + a whole transition row.  `rowmax`: the row maxima the
+// forward pass left, which bound the walk down a list.
 hipError_t launch_backtrace_sorted(const float *hist, const float2 *sorted, int SpP, int items_per_tile,
                                    const float *trans, const int32_t *frames, int32_t *out, int B, int T, int S,
-                                   hipStream_t stream, const float *rowmax = nullptr) {
-    if (!backtrace_sorted_enabled() || S % 4 != 0 || S > 256 * 16)
+                                   hipStream_t stream, const float *rowmax) {
+    if (S % 4 != 0 || S > 256 * 16)
         return launch_backtrace_on(hist, trans, frames, out, B, T, S, stream);
     const int shift = items_per_tile == pruned::kNB ? 6 : 5;      // list offsets = prev-state * 4 * items per tile
-    const size_t lds = sizeof(float) * (size_t)S;
-    static const bool gather = [] {
-        const char *e = getenv("TORBI_HIP_BACKTRACE_GATHER");
-        return !e || atoi(e) != 0;
-    }();
-    if (rowmax && gather) {
-#define TORBI_BTG_CASE(NQ_)                                                                                     \
-        if (S <= 256 * NQ_) {                                                                                   \
-            hipLaunchKernelGGL(lazy::backtrace_gather_kernel<NQ_>, dim3(B), dim3(64), 0, stream, hist, rowmax, sorted, \
-                               SpP, shift, frames, out, B, T, S);                                               \
-            return hipGetLastError();                                                                           \
-        }
-        TORBI_BTG_CASE(2)
-        TORBI_BTG_CASE(6)
-        TORBI_BTG_CASE(8)
-        TORBI_BTG_CASE(16)
-#undef TORBI_BTG_CASE
-    }
-#define TORBI_BTS_CASE(NQ_)                                                                              \
-    if (S <= 256 * NQ_) {                                                                                \
-        hipLaunchKernelGGL(lazy::backtrace_sorted_kernel<NQ_>, dim3(B), dim3(64), lds, stream, hist, sorted, SpP, \
-                           shift, frames, out, B, T, S);                                                 \
-        return hipGetLastError();                                                                        \
-    }
-    TORBI_BTS_CASE(2)
-    TORBI_BTS_CASE(6)
-    TORBI_BTS_CASE(8)
-    TORBI_BTS_CASE(16)
-#undef TORBI_BTS_CASE
-    return hipErrorInvalidValue;
+    by_state_count(S, [&](auto nq) {
+        hipLaunchKernelGGL(lazy::backtrace_gather_kernel<decltype(nq)::value>, dim3(B), dim3(64), 0, stream, hist, rowmax, sorted,
+                           SpP, shift, frames, out, B, T, S);
+    });
+    return hipGetLastError();
 }
 
 // ---- time-resident path: several batches, one forward launch, one backtrace launch -------------------------
@@ -1294,17 +1237,8 @@ struct HostBatch {
     int B, T;
 };
 
-// seeds per item of the time-resident kernel: 3, or 1 with TORBI_HIP_FEW_SEEDS; TORBI_HIP_RESIDENT_KR=0|1|3 overrides
-// both (experiments)
-inline int resident_seeds(bool few) {
-    static const int forced = [] {
-        const char *e = getenv("TORBI_HIP_RESIDENT_KR");
-        const int x = e ? atoi(e) : -1;
-        return (x == 0 || x == 1 || x == 3) ? x : -1;
-    }();
-    return forced >= 0 ? forced : (few ? 1 : 3);
-}
-// seeds of a launch from the call's flags: FEW -> one, MANY -> three, neither -> one in the cluster form, three with whole tiles
+// seeds per item of a time-resident launch (3, or 1: `few`) from the call's flags: FEW -> one, MANY -> three, neither -> one
+// in the cluster form, three with whole tiles
 inline bool few_seeds(unsigned flags, bool clusters) {
     if (flags & TORBI_HIP_FEW_SEEDS) return true;
     if (flags & TORBI_HIP_MANY_SEEDS) return false;
@@ -1324,11 +1258,10 @@ hipError_t launch_resident_variant(const resident::Group &grp, const resident::C
     return hipGetLastError();
 }
 
-// (seeds: 3, or 1 with TORBI_HIP_FEW_SEEDS; the experiment value 0 of TORBI_HIP_RESIDENT_KR runs as 1)
 template <int KW, int MAXP, bool CLUSTER, int NI = 16>
 hipError_t launch_resident_kernel(const resident::Group &grp, const resident::Cluster &clu, int workgroups,
                                   const ResidentWorkspace &w, const float *init, int S, hipStream_t stream, bool few) {
-    return resident_seeds(few) == 3 ? launch_resident_variant<KW, MAXP, 3, CLUSTER, NI>(grp, clu, workgroups, w, init, S, stream)
+    return !few ? launch_resident_variant<KW, MAXP, 3, CLUSTER, NI>(grp, clu, workgroups, w, init, S, stream)
                                     : launch_resident_variant<KW, MAXP, 1, CLUSTER, NI>(grp, clu, workgroups, w, init, S, stream);
 }
 
@@ -1348,14 +1281,9 @@ hipError_t launch_repair_variant(const resident::Group &grp, const resident::Clu
 inline hipError_t launch_repair(const resident::Group &grp, const resident::Cluster &clu, int tiles, const ResidentWorkspace &w,
                                 const float *init, int S, hipStream_t s, bool few) {
     const bool small = resident::tile_items(S) != resident::kNI;
-    if (resident_seeds(few) == 3)
+    if (!few)
         return small ? launch_repair_variant<3, 8>(grp, clu, tiles, w, init, S, s) : launch_repair_variant<3, 16>(grp, clu, tiles, w, init, S, s);
     return small ? launch_repair_variant<1, 8>(grp, clu, tiles, w, init, S, s) : launch_repair_variant<1, 16>(grp, clu, tiles, w, init, S, s);
-}
-
-inline bool cluster_eight_waves() {             // TORBI_HIP_CLUSTER_KW8=0: the twelve-wave instances everywhere (experiments)
-    const char *e = getenv("TORBI_HIP_CLUSTER_KW8");
-    return !e || atoi(e) != 0;
 }
 
 // every workgroup owns a whole tile (resident_forward_kernel without clusters)
@@ -1427,70 +1355,64 @@ inline hipError_t nonfinite_end(const HostBatch *hb, int n, const float *trans, 
     return hipGetLastError();
 }
 
-// batches with B > 0 only; the preparation lives in the first batch's workspace, or in `kept` (marked valid once this call
-// has enqueued its filling)
-hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const float *init, int S, int cus, hipStream_t s,
-                        hipEvent_t *ev, int *launches, bool reuse, bool ascending, bool clusters, bool few,
-                        Preparation *kept) {
-    resident::Group grp{};
+// how long the members of a cluster (time-resident and band forms) wait for each other before they give their tile up, in
+// ticks of the 100 MHz wall clock.  TORBI_HIP_CLUSTER_WAIT_US overrides (read per launch: the tests switch it).
+inline unsigned long long cluster_wait_ticks() {
+    const char *e = getenv("TORBI_HIP_CLUSTER_WAIT_US");
+    return e ? 100ull * strtoull(e, nullptr, 10) : resident::kClusterWaitTicks;
+}
+
+// A table of batches (B > 0 each) as ONE launch group, ready for a forward launch over its tiles: `grp` filled from the
+// time-resident layout of every batch's workspace (tile map and statistics in the first batch's), and on the stream the
+// launches that rank every batch's items by length, cut them into tiles of `items_per_tile` and rank the tiles -- the first of
+// which stamps `route` into every batch's route record, the last of which zeroes the `nflags` cluster words at `flags`.
+// Behind a nonfinite_begin (the group carries that decode's serial number).
+struct LaunchGroup {
+    resident::Group grp;
+    int tiles, items;
+};
+hipError_t assemble_group(const HostBatch *hb, int n, int S, int cus, hipStream_t s, bool ascending, int items_per_tile,
+                          Route route, unsigned *flags, int nflags, LaunchGroup &g) {
+    resident::Group &grp = g.grp;
     resident::OrderJobs jobs{};
-    jobs.ascending = ascending ? 1 : 0;
+    grp = resident::Group{};
     grp.n = n;
-    {
-        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, cus, s, false);
-        if (ne != hipSuccess) return ne;
-    }
     grp.serial = t_serial;
     int tiles = 0, items = 0, widest = 0;
     for (int k = 0; k < n; ++k) {
         resident::Batch &b = grp.batch[k];
         const ResidentWorkspace wk = carve_resident(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        b.alarm = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus) + nonfinite::kAlarmWord;
+        int32_t *const record = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
+        b.alarm = record + nonfinite::kAlarmWord;
         b.obs = hb[k].obs;
         b.frames = hb[k].frames;
         b.out = hb[k].out;
         b.hist = wk.hist;
         b.order = wk.order;
         b.rowmax = wk.rowmax;
-        jobs.job[k] = resident::OrderJob{hb[k].frames, wk.order, hb[k].B, hb[k].T, tiles, wk.lengths_hist, nullptr, 0};
+        jobs.job[k] = resident::OrderJob{hb[k].frames, wk.order, hb[k].B, hb[k].T, tiles, wk.lengths_hist, record, (int)route};
         widest = std::max(widest, hb[k].B);
         b.B = hb[k].B;
         b.T = hb[k].T;
         b.tile0 = tiles;
         b.item0 = items;
-        tiles += tiles_of(hb[k].B, S);
+        tiles += (hb[k].B + items_per_tile - 1) / items_per_tile;
         items += hb[k].B;
     }
-    const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus, kept);
     if (tiles > kMaxGroupTiles) return hipErrorInvalidValue;
+    g.tiles = tiles;
+    g.items = items;
+    const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus);
     grp.tile_map = w.tile_map;
     grp.stats = w.stats;
+    jobs.ascending = ascending ? 1 : 0;
     jobs.stats = w.stats;
     jobs.n = n;
     jobs.tiles = tiles;
     jobs.tile_map = w.tile_map;
-    // cluster form: R workgroups per tile (exchange buffers in the first batch's workspace, flags and tickets zeroed)
-    const int R = clusters ? cluster_members(tiles, S, cus) : 1;
-    unsigned *const control = w.flags + (size_t)std::max(cus / 2, 1) * resident::kMaxR;
-    const char *wait_env = getenv("TORBI_HIP_CLUSTER_WAIT_US");         // (read per launch: the tests switch it)
-    const unsigned long long wait_ticks = wait_env ? 100ull * strtoull(wait_env, nullptr, 10) : resident::kClusterWaitTicks;
-    // (flags [ctiles][kMaxR], control [16], failed [ctiles], where [ctiles][kMaxR]: all zeroed by order_tiles_kernel)
-    // Above 2048 states (8-item tiles) the sorted lists are what the launch fetches -- 134 MB at 4096 states, far beyond an
-    // XCD's 4 MB L2, walked by every tile: 232 GB per 128 x 2000 x 4096 decode against 8.4 GB algorithmic
-    // (profiles/r06_c5_pmc.json).  Member m of EVERY tile on one XCD keeps that member's rows' lists in its L2; the exchange
-    // then crosses XCDs (write-through), which costs less than it saves there: 19.8 -> 17.3 us per timestep at 128 items,
-    // 34.3 -> 30.6 at 256; up to 2048 states it loses 1-3 % (profiles/r06_c5_spread.txt).  TORBI_HIP_CLUSTER_SPREAD=0|1 overrides.
-    const char *spread_env = getenv("TORBI_HIP_CLUSTER_SPREAD");
-    const int spread = (R % 8 == 0 && (spread_env ? atoi(spread_env) != 0 : resident::tile_items(S) == 8)) ? 1 : 0;
-    resident::Cluster clu{w.xchg, control + 16 + std::max(cus / 2, 1), tiles, control, control + 16, R, wait_ticks, spread};
-    if (ev) (void)hipEventRecord(ev[0], s);
-    for (int k = 0; k < n; ++k) {            // (order_items_kernel stamps the batches' route records)
-        jobs.job[k].route_record = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        jobs.job[k].route = (int)(R > 1 ? ROUTE_CLUSTER : ROUTE_RESIDENT);
-    }
-    if (kept) reuse = kept->valid;       // the caller's buffer: the promise is about IT, whichever batch
-    if (!reuse) launch_list_preparation(trans, w.sorted, w.row_range, w.tt, S, w.SpP, w.NPOW, resident::tile_items(S), s);
-    if (kept) kept->valid = true;
+    jobs.ni = items_per_tile;
+    jobs.flags = flags;
+    jobs.nflags = nflags;
     hipLaunchKernelGGL(resident::order_items_kernel, dim3((widest + 255) / 256, n), dim3(256), 0, s, jobs);
     for (int k = 0; k < n; ++k) {            // batches too large for the all-pairs ranking: counting sort over the lengths
         const resident::OrderJob &jb = jobs.job[k];
@@ -1502,11 +1424,43 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
         hipLaunchKernelGGL(resident::order_large_scan_kernel, dim3(1), dim3(1024), 0, s, jb, jobs.ascending);
         hipLaunchKernelGGL(resident::order_large_place_kernel, dim3((jb.B + 255) / 256), dim3(256), 0, s, jb);
     }
-    jobs.ni = resident::tile_items(S);
-    jobs.flags = w.flags;
-    jobs.nflags = R > 1 ? (int)(w.flag_bytes / sizeof(unsigned)) : 0;
     hipLaunchKernelGGL(resident::order_tiles_kernel, dim3((tiles + 255) / 256), dim3(256), 0, s, jobs);
-    hipError_t e;
+    return hipSuccess;
+}
+
+// batches with B > 0 only; the preparation lives in the first batch's workspace, or in `kept` (marked valid once this call
+// has enqueued its filling)
+hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const float *init, int S, int cus, hipStream_t s,
+                        hipEvent_t *ev, int *launches, bool reuse, bool ascending, bool clusters, bool few,
+                        Preparation *kept) {
+    {
+        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, cus, s, false);
+        if (ne != hipSuccess) return ne;
+    }
+    int tiles = 0;
+    for (int k = 0; k < n; ++k) tiles += tiles_of(hb[k].B, S);
+    const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus, kept);
+    // cluster form: R workgroups per tile (exchange buffers in the first batch's workspace, flags and tickets zeroed)
+    const int R = clusters ? cluster_members(tiles, S, cus) : 1;
+    unsigned *const control = w.flags + (size_t)std::max(cus / 2, 1) * resident::kMaxR;
+    // (flags [ctiles][kMaxR], control [16], failed [ctiles], where [ctiles][kMaxR]: all zeroed by order_tiles_kernel)
+    // Above 2048 states (8-item tiles) the sorted lists are what the launch fetches -- 134 MB at 4096 states, far beyond an
+    // XCD's 4 MB L2, walked by every tile: 232 GB per 128 x 2000 x 4096 decode against 8.4 GB algorithmic
+    // (profiles/r06_c5_pmc.json).  Member m of EVERY tile on one XCD keeps that member's rows' lists in its L2; the exchange
+    // then crosses XCDs (write-through), which costs less than it saves there: 19.8 -> 17.3 us per timestep at 128 items,
+    // 34.3 -> 30.6 at 256; up to 2048 states it loses 1-3 % (profiles/r06_c5_spread.txt).
+    const int spread = (R % 8 == 0 && resident::tile_items(S) == 8) ? 1 : 0;
+    resident::Cluster clu{w.xchg, control + 16 + std::max(cus / 2, 1), tiles, control, control + 16, R, cluster_wait_ticks(), spread};
+    if (ev) (void)hipEventRecord(ev[0], s);
+    if (kept) reuse = kept->valid;       // the caller's buffer: the promise is about IT, whichever batch
+    if (!reuse) launch_list_preparation(trans, w.sorted, w.row_range, w.tt, S, w.SpP, w.NPOW, resident::tile_items(S), s);
+    if (kept) kept->valid = true;
+    LaunchGroup group;
+    hipError_t e = assemble_group(hb, n, S, cus, s, ascending, resident::tile_items(S), R > 1 ? ROUTE_CLUSTER : ROUTE_RESIDENT,
+                                  w.flags, R > 1 ? (int)(w.flag_bytes / sizeof(unsigned)) : 0, group);
+    if (e != hipSuccess) return e;
+    const resident::Group &grp = group.grp;
+    const int items = group.items;
     if (ev) (void)hipEventRecord(ev[3], s);
     const int nrg = (S + resident::pass_rows(S) - 1) / resident::pass_rows(S);
     const bool small = resident::tile_items(S) != resident::kNI;       // 8-item tiles (2048 < S <= 4096)
@@ -1520,15 +1474,14 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
         // (eight dispatch classes of R x ceil(tiles / 8) workgroups each: resident_forward.hpp, struct Cluster)
         const int grid = 8 * ((tiles + 7) / 8) * R;
         const int share = (nrg + R - 1) / R;                    // row groups of the largest share
-        if (small && share <= 16 && cluster_eight_waves()) {
+        if (small && share <= 16) {
             // 8-item tiles, at most 16 row groups a member: EIGHT waves (256 registers each: the twelve-wave instances of
             // the 8-item tile spill 20-80 registers at 168, and every scratch reload waits for the write-through stores
             // ahead of it); 128 x 4096 (16 tiles x 16 members, 8 row groups each) kept four of twelve waves idle anyway
             if (share <= 8) e = launch_resident_kernel<8, 1, true, 8>(grp, clu, grid, w, init, S, s, few);
             else e = launch_resident_kernel<8, 2, true, 8>(grp, clu, grid, w, init, S, s, few);
-        } else if (small) {
-            if (passes <= 1) e = launch_resident_kernel<12, 1, true, 8>(grp, clu, grid, w, init, S, s, few);
-            else if (passes <= 2) e = launch_resident_kernel<12, 2, true, 8>(grp, clu, grid, w, init, S, s, few);
+        } else if (small) {         // (more than 16 row groups a member: at least two passes of twelve waves)
+            if (passes <= 2) e = launch_resident_kernel<12, 2, true, 8>(grp, clu, grid, w, init, S, s, few);
             else if (passes <= 4) e = launch_resident_kernel<12, 4, true, 8>(grp, clu, grid, w, init, S, s, few);
             else e = launch_resident_kernel<12, 6, true, 8>(grp, clu, grid, w, init, S, s, few);
         } else if (passes <= 1) e = launch_resident_kernel<12, 1, true>(grp, clu, grid, w, init, S, s, few);
@@ -1548,60 +1501,25 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
     if (launches) *launches = 1;
     if (ev) (void)hipEventRecord(ev[1], s);
     if (e != hipSuccess) return e;
-    const bool vec = (S % 4 == 0) && ((reinterpret_cast<uintptr_t>(trans) & 15) == 0);
-    const size_t row_lds = sizeof(float) * (size_t)S;
     // the backtrace gathers the posteriors the lists point at instead of staging whole rows in the LDS: half the bytes, and
-    // faster from one batch (0.58 against 0.80 ms) to eight (1.86 against 3.11 ms; tools/backtrace_probe.py,
-    // profiles/r03_backtrace_gather.txt).  TORBI_HIP_BACKTRACE_GATHER=0 brings the staging form back.
-    static const bool gather = [] {
-        const char *e = getenv("TORBI_HIP_BACKTRACE_GATHER");
-        return !e || atoi(e) != 0;
-    }();
+    // faster from one batch (0.58 against 0.80 ms) to eight (1.86 against 3.11 ms; profiles/r03_backtrace_gather.txt).
     // few paths (one batch): every path in speculative segments, K waves per item, then one wave per item at the joints
     // (lazy_backtrace.hpp, chase_segment); the forward launch is done with the tile map, which holds the segments' ends
     const int K = backtrace_segments(items);
-    if (S % 4 == 0 && backtrace_sorted_enabled() && gather && K > 1) {
+    if (S % 4 == 0 && K > 1) {
         int32_t *const arrive = w.tile_map;
-#define TORBI_SEGMENTED(NQ_)                                                                                                      \
-        hipLaunchKernelGGL(resident::group_segment_gather_kernel<NQ_>, dim3(items * K), dim3(64), 0, s, grp, w.sorted, w.SpP, S, K, \
-                           arrive);                                                                                               \
-        hipLaunchKernelGGL(resident::group_stitch_gather_kernel<NQ_>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S, K, arrive)
-        if (S <= 512) { TORBI_SEGMENTED(2); }
-        else if (S <= 1536) { TORBI_SEGMENTED(6); }
-        else if (S <= 2048) { TORBI_SEGMENTED(8); }
-        else { TORBI_SEGMENTED(16); }
-#undef TORBI_SEGMENTED
-    } else if (S % 4 == 0 && backtrace_sorted_enabled() && gather) {
-        if (S <= 512)
-            hipLaunchKernelGGL(resident::group_backtrace_gather_kernel<2>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S);
-        else if (S <= 1536)
-            hipLaunchKernelGGL(resident::group_backtrace_gather_kernel<6>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S);
-        else if (S <= 2048)
-            hipLaunchKernelGGL(resident::group_backtrace_gather_kernel<8>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S);
-        else
-            hipLaunchKernelGGL(resident::group_backtrace_gather_kernel<16>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S);
-    } else if (S % 4 == 0 && backtrace_sorted_enabled()) {
-        if (S <= 512)
-            hipLaunchKernelGGL(resident::group_backtrace_sorted_kernel<2>, dim3(items), dim3(64), row_lds, s, grp,
-                               w.sorted, w.SpP, S);
-        else if (S <= 1536)
-            hipLaunchKernelGGL(resident::group_backtrace_sorted_kernel<6>, dim3(items), dim3(64), row_lds, s, grp,
-                               w.sorted, w.SpP, S);
-        else if (S <= 2048)
-            hipLaunchKernelGGL(resident::group_backtrace_sorted_kernel<8>, dim3(items), dim3(64), row_lds, s, grp,
-                               w.sorted, w.SpP, S);
-        else
-            hipLaunchKernelGGL(resident::group_backtrace_sorted_kernel<16>, dim3(items), dim3(64), row_lds, s, grp,
-                               w.sorted, w.SpP, S);
-    } else if (vec && S <= 512)
-        hipLaunchKernelGGL(resident::group_backtrace_prefetch_kernel<2>, dim3(items), dim3(64), 0, s, grp, trans, S);
-    else if (vec && S <= 1536)
-        hipLaunchKernelGGL(resident::group_backtrace_prefetch_kernel<6>, dim3(items), dim3(64), 0, s, grp, trans, S);
-    else if (vec && S <= 2048)
-        hipLaunchKernelGGL(resident::group_backtrace_prefetch_kernel<8>, dim3(items), dim3(64), 0, s, grp, trans, S);
-    else if (vec)
-        hipLaunchKernelGGL(resident::group_backtrace_prefetch_kernel<16>, dim3(items), dim3(64), 0, s, grp, trans, S);
-    else
+        by_state_count(S, [&](auto nq) {
+            constexpr int NQ = decltype(nq)::value;
+            hipLaunchKernelGGL(resident::group_segment_gather_kernel<NQ>, dim3(items * K), dim3(64), 0, s, grp, w.sorted, w.SpP, S, K,
+                               arrive);
+            hipLaunchKernelGGL(resident::group_stitch_gather_kernel<NQ>, dim3(items), dim3(64), 0, s, grp, w.sorted, w.SpP, S, K, arrive);
+        });
+    } else if (S % 4 == 0) {
+        by_state_count(S, [&](auto nq) {
+            hipLaunchKernelGGL(resident::group_backtrace_gather_kernel<decltype(nq)::value>, dim3(items), dim3(64), 0, s, grp, w.sorted,
+                               w.SpP, S);
+        });
+    } else
         hipLaunchKernelGGL(resident::group_backtrace_kernel<1>, dim3(items), dim3(64), 0, s, grp, trans, S);
     {
         const hipError_t ne = nonfinite_end(hb, n, trans, init, S, cus, s);
@@ -1661,76 +1579,34 @@ inline bool choose_band(int S, int hl, int hr, int tiles, int cus, BandChoice &c
 hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float *init, int S, const BandChoice &choice, int cus,
                     hipStream_t s, hipEvent_t *ev, int *launches, bool ascending) {
     const band::Plan &pl = choice.pl;
-    resident::Group grp{};
-    resident::OrderJobs jobs{};
     band::Exchange ex{};
     band::ClearJobs clear{};
-    jobs.ascending = ascending ? 1 : 0;
-    grp.n = n;
     {
         const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, cus, s, false, pl.hl, pl.hr, true, choice.background);     // (and the band's promise)
         if (ne != hipSuccess) return ne;
     }
-    grp.serial = t_serial;
-    int tiles = 0, items = 0, widest = 0;
     size_t most = 0;
     for (int k = 0; k < n; ++k) {
-        resident::Batch &b = grp.batch[k];
         const BandWorkspace wk = carve_band(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        b.alarm = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus) + nonfinite::kAlarmWord;
-        b.obs = hb[k].obs;
-        b.frames = hb[k].frames;
-        b.out = hb[k].out;
-        b.hist = wk.base.hist;
-        b.order = wk.base.order;
-        b.rowmax = wk.base.rowmax;
-        jobs.job[k] = resident::OrderJob{hb[k].frames, wk.base.order, hb[k].B, hb[k].T, tiles, wk.base.lengths_hist,
-                                         route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus), (int)ROUTE_BAND};
         ex.xchg[k] = wk.xchg;
         clear.xchg[k] = wk.xchg;
-        clear.bytes[k] = pl.R > 1 ? band::xchg_bytes(hb[k].B, S) : 0;
+        clear.bytes[k] = pl.R > 1 && !choice.whole ? band::xchg_bytes(hb[k].B, S) : 0;      // (whole tiles exchange nothing)
         most = std::max(most, clear.bytes[k]);
-        widest = std::max(widest, hb[k].B);
-        b.B = hb[k].B;
-        b.T = hb[k].T;
-        b.tile0 = tiles;
-        b.item0 = items;
-        tiles += band_tiles(hb[k].B);
-        items += hb[k].B;
     }
-    if (tiles > kMaxGroupTiles) return hipErrorInvalidValue;
     const BandWorkspace w = carve_band(hb[0].workspace, hb[0].B, hb[0].T, S, cus);
-    grp.tile_map = w.base.tile_map;
-    grp.stats = w.base.stats;
-    jobs.stats = w.base.stats;
-    jobs.n = n;
-    jobs.tiles = tiles;
-    jobs.tile_map = w.base.tile_map;
-    jobs.ni = band::kNI;
+    if (ev) (void)hipEventRecord(ev[0], s);
+    LaunchGroup group;
+    hipError_t e = assemble_group(hb, n, S, cus, s, ascending, band::kNI, ROUTE_BAND, nullptr, 0, group);
+    if (e != hipSuccess) return e;
+    const resident::Group &grp = group.grp;
+    const int tiles = group.tiles, items = group.items;
     const int nlaunch = choice.whole ? 1 : (tiles + choice.cap - 1) / choice.cap;
     ex.failed = w.words + 16;
     unsigned *const tickets = w.words + 16 + kMaxGroupTiles;        // [8] per launch
-    const char *wait_env = getenv("TORBI_HIP_CLUSTER_WAIT_US");         // (read per launch: the tests switch it)
-    ex.wait_ticks = wait_env ? 100ull * strtoull(wait_env, nullptr, 10) : resident::kClusterWaitTicks;
+    ex.wait_ticks = cluster_wait_ticks();
     clear.words = w.words;
     clear.nwords = 16 + kMaxGroupTiles + 8 * nlaunch;
     clear.n = n;
-    if (choice.whole)
-        for (int k = 0; k < n; ++k) clear.bytes[k] = 0;
-    if (ev) (void)hipEventRecord(ev[0], s);
-    hipLaunchKernelGGL(resident::order_items_kernel, dim3((widest + 255) / 256, n), dim3(256), 0, s, jobs);
-    for (int k = 0; k < n; ++k) {            // batches too large for the all-pairs ranking: counting sort over the lengths
-        const resident::OrderJob &jb = jobs.job[k];
-        if (jb.B <= resident::kMaxOrdered) continue;
-        const BandWorkspace wk = carve_band(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        hipError_t me = hipMemsetAsync(wk.base.lengths_hist, 0, wk.base.lengths_hist_bytes, s);
-        if (me != hipSuccess) return me;
-        hipLaunchKernelGGL(resident::order_large_count_kernel, dim3((jb.B + 255) / 256), dim3(256), 0, s, jb);
-        hipLaunchKernelGGL(resident::order_large_scan_kernel, dim3(1), dim3(1024), 0, s, jb, jobs.ascending);
-        hipLaunchKernelGGL(resident::order_large_place_kernel, dim3((jb.B + 255) / 256), dim3(256), 0, s, jb);
-    }
-    hipLaunchKernelGGL(resident::order_tiles_kernel, dim3((tiles + 255) / 256), dim3(256), 0, s, jobs);
-    hipError_t e;
     if (choice.whole) {
         // whole tiles: the band packed in the lanes' reading order (1 MB at 1440 states, reach 87: ~10 us), then ONE launch
         const band::TilePlan &tp = choice.tile;
@@ -1791,21 +1667,18 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
     if (ev) (void)hipEventRecord(ev[1], s);
     const int K = backtrace_segments(items);          // (few paths: speculative segments, as behind run_resident)
     int32_t *const arrive = w.base.tile_map;
-#define TORBI_BAND_BACKTRACE(NQ_)                                                                                                  \
-    if (K > 1) {                                                                                                                   \
-        hipLaunchKernelGGL(band::group_segment_band_kernel<NQ_>, dim3(items * K), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr, K,   \
-                           arrive, choice.background);                                                                             \
-        hipLaunchKernelGGL(band::group_stitch_band_kernel<NQ_>, dim3(items), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr, K, arrive, \
-                           choice.background);                                                                                     \
-    } else {                                                                                                                       \
-        hipLaunchKernelGGL(band::group_backtrace_band_kernel<NQ_>, dim3(items), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr,        \
-                           choice.background);                                                                                     \
-    }
-    if (S <= 512) { TORBI_BAND_BACKTRACE(2) }
-    else if (S <= 1536) { TORBI_BAND_BACKTRACE(6) }
-    else if (S <= 2048) { TORBI_BAND_BACKTRACE(8) }
-    else { TORBI_BAND_BACKTRACE(16) }
-#undef TORBI_BAND_BACKTRACE
+    by_state_count(S, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (K > 1) {
+            hipLaunchKernelGGL(band::group_segment_band_kernel<NQ>, dim3(items * K), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr, K,
+                               arrive, choice.background);
+            hipLaunchKernelGGL(band::group_stitch_band_kernel<NQ>, dim3(items), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr, K, arrive,
+                               choice.background);
+        } else {
+            hipLaunchKernelGGL(band::group_backtrace_band_kernel<NQ>, dim3(items), dim3(64), 0, s, grp, trans, S, pl.hl, pl.hr,
+                               choice.background);
+        }
+    });
     {
         const hipError_t ne = nonfinite_end(hb, n, trans, init, S, cus, s);
         if (ne != hipSuccess) return ne;

@@ -491,6 +491,32 @@ int torbi_hip_forward_backward_counts(const float *observation, const int32_t *b
                                       size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
 /*
+ * Band route of forward-backward (added within ABI 17): torbi_hip_forward_backward's quantities for a matrix that holds ONE
+ * value outside a band.  The caller states the band -- transition[j][i] with j - reach_left <= i <= j + reach_right ([next][prev],
+ * as torbi_hip_band_reach_over answers) -- and `background` (finite or -inf), and promises that every entry outside the band
+ * equals `background` bit for bit.  With ebg = exp(background) (0 for -inf) each product is the band's sum of
+ * (exp(transition) - ebg) plus ebg times the operand's sum, so a frame costs W = reach_left + reach_right + 1 multiplies per
+ * state.  The call reads the whole matrix once on the device and checks the promise: where it is broken, every log-likelihood
+ * and every posterior row t < F_b is NaN (no error code: nothing waits for the device).  Contract, non-finite rules and
+ * independence of items as torbi_hip_forward_backward (an in-band NaN or +inf reaches every item with F_b >= 2); the
+ * rounding differs from the dense route's, an item's bits do not depend on how many items share its workgroup.
+ *
+ * torbi_hip_forward_backward_band_covers: 1 where the entry point takes the call -- 1 <= S <= 4096, at most 64 in-band
+ * entries in a matrix row (min(W, S) <= 64 with the reaches clamped to S - 1), a background that is neither NaN nor +inf, B
+ * and T within torbi_hip_forward_backward's limits --, else 0.  It and _workspace_bytes answer without a device.
+ * workspace: torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation.
+ * Four launches per call whatever T is (the time loop runs inside one launch, a workgroup owns whole items), no host
+ * synchronisation: with a caller-owned workspace a call can be captured into a graph.  Errors as
+ * torbi_hip_forward_backward (TORBI_HIP_EINVAL also for a negative reach), and TORBI_HIP_EUNSUPPORTED where _covers answers 0.
+ */
+int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_forward_backward_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                    const float *initial, int reach_left, int reach_right, float background,
+                                    float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B,
+                                    int T, int S, int device, void *stream);
+
+/*
  * k-best Viterbi decoding (added within ABI 17): the k best state sequences of every item with their exact scores, on the
  * model torbi_hip_viterbi_decode decodes (torbi_amd/k_best.py, KBEST.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log; 1 <= k <= 32.

@@ -18,7 +18,8 @@ from .pipeline import DecodePipeline
 from .state import reset as reset_path_state
 from .core import release_job_memory
 from .stream import StreamDecoder
-from .posterior import forward_backward, forward_backward_workspace_bytes, state_posteriors
+from .posterior import (forward_backward, forward_backward_banded, forward_backward_banded_workspace_bytes,
+                        forward_backward_workspace_bytes, posterior_route, state_posteriors)
 from .training import (expected_counts, expected_counts_workspace_bytes, forward_backward_counts,
                        log_likelihood)
 from .k_best import best_paths, decode_k_best, decode_k_best_workspace_bytes
@@ -28,4 +29,5 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'distributed', 'DecodePipeline', 'BATCH_SIZE', 'NUM_WORKERS', 'reset_path_state', 'release_job_memory', 'timer',
            'StreamDecoder', 'state_posteriors', 'forward_backward', 'forward_backward_workspace_bytes',
            'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood',
-           'best_paths', 'decode_k_best', 'decode_k_best_workspace_bytes']
+           'best_paths', 'decode_k_best', 'decode_k_best_workspace_bytes', 'forward_backward_banded',
+           'forward_backward_banded_workspace_bytes', 'posterior_route']

@@ -1,0 +1,305 @@
+// forward_backward_band.hpp -- state posteriors and log-likelihood for a transition matrix that holds ONE value outside a
+// band (torbi_hip_forward_backward_band, torbi_amd/posterior.py forward_backward_banded, POSTERIOR.md "Band route").
+//
+// The model, the contract and the scaled recurrence are forward_backward.hpp's.  The caller states a band
+// j - reach_left <= i <= j + reach_right of A [next j][prev i] and a `background`: every entry outside the band equals
+// `background` bit for bit.  With ebg = exp(background) (0 for -inf) each product splits into the band and one constant:
+//     forward   (E a)[j]   = sum_{i in band(j)}  (E[j,i] - ebg) a[i]  +  ebg * sum_i a[i]        (sum_i a[i] = c_{t-1})
+//     backward  (E^T w)[i] = sum_{j: i in band(j)} (E[j,i] - ebg) w[j]  +  ebg * sum_j w[j]
+// so a step costs W = reach_left + reach_right + 1 multiplies per state where the dense route spends S.
+//
+// Workspace (torbi_hip_forward_backward_band_workspace_bytes), every piece 256-B aligned, Sd = S up to 64:
+//     Df   [W][Sd] fp32   Df[k][j] = E[j][j - reach_left + k] - ebg     (forward: diagonal k along the next state)
+//     Db   [W][Sd] fp32   Db[k][i] = E[i + reach_left - k][i] - ebg     (backward: the same diagonal along the prev state)
+//                         positions clipped at the matrix edges are 0
+//     m    [B][T]  fp32   row maxima (fb_rowmax_kernel)
+//     c    [B][T]  fp32   row sums c_t
+//     flag int32          1 when an entry outside the stated band differs from `background`
+//
+// fb_band_kernel<G>: ONE launch runs all T frames of both passes.  A workgroup of 1024 threads owns G whole items, so
+// nothing waits across workgroups; thread `tid` owns states tid, tid + 1024, ... of every item of the tile in both passes.
+// The rows a_{t-1} / a_t (then w_{t+1} / w_t) of the tile live in LDS with a zero halo of max(reach) on both sides, the
+// diagonals stream from L2 and every load of one is shared by the G items.  One barrier per frame and pass.
+//
+// Reductions, per item and in a fixed order that does not depend on G: the states of a wave by a 64-lane butterfly, the
+// 16 wave sums by a 16-lane butterfly (every lane of every wave computes the same bits); L as in fb_loglik_kernel over
+// t = tid, tid + 1024, ... in fp64, a butterfly per wave, the 16 wave sums in order.  No float atomics, vector stores only.
+#pragma once
+
+#include "forward_backward.hpp"
+
+namespace fbb {
+
+constexpr int kThreads = 1024, kWaves = kThreads / 64;
+constexpr int kMaxStates = 4096;
+constexpr int kMaxWindow = 64;               // in-band entries of one matrix row: min(W, S) <= 64
+constexpr int kMaxGroup = 8;                 // items per workgroup (16 would not fit 128 VGPRs without scratch)
+constexpr int kMaxLdsBytes = 64 * 1024;
+
+__host__ __device__ inline int clamp_reach(int reach, int S) { return reach < 0 ? 0 : (reach > S - 1 ? S - 1 : reach); }
+
+struct Layout {
+    int reach_left, reach_right, W, Sd;      // (the reaches clamped to S - 1)
+    size_t Df, Db, m, c, flag, total;
+};
+
+inline Layout layout(int B, int T, int S, int reach_left, int reach_right) {
+    Layout l;
+    l.reach_left = clamp_reach(reach_left, S);
+    l.reach_right = clamp_reach(reach_right, S);
+    l.W = l.reach_left + l.reach_right + 1;
+    l.Sd = (int)fb::round_up((size_t)S, 64);
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at = fb::round_up(at + bytes, 256); return here; };
+    l.Df = take((size_t)l.W * l.Sd * 4);
+    l.Db = take((size_t)l.W * l.Sd * 4);
+    l.m = take((size_t)B * T * 4);
+    l.c = take((size_t)B * T * 4);
+    l.flag = take(4);
+    l.total = at + 256;                      // (room to align the caller's base)
+    return l;
+}
+
+// LDS of a tile of G items: the rows [2][G][S + 2 halo] and the wave sums [2][G][16] fp32, the fp64 wave sums of L
+// [G][16] and L [G]
+__host__ __device__ inline int row_stride(int S, int halo) { return S + 2 * halo; }
+inline size_t lds_bytes(int G, int S, int halo) {
+    return (size_t)G * ((size_t)2 * row_stride(S, halo) * 4 + 2 * kWaves * 4 + kWaves * 8 + 8) + 16;
+}
+
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+// the 16 wave sums of one item (lane l holds number l & 15): every lane gets the same bits
+__device__ __forceinline__ float sum16(float x) {
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// ---- the diagonals of E - ebg in both orders; resets the promise flag ----
+__global__ void fb_band_prepare_kernel(const float *__restrict__ A, float *__restrict__ Df, float *__restrict__ Db,
+                                       int32_t *__restrict__ flag, float ebg, int reach_left, int W, int Sd, int S) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *flag = 0;
+    const size_t n = (size_t)W * Sd;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(e / Sd), x = (int)(e % Sd);
+        const int i = x - reach_left + k;            // forward: x is the next state, i the prev state
+        const int j = x + reach_left - k;            // backward: x is the prev state, j the next state
+        Df[e] = (x < S && i >= 0 && i < S) ? expf(A[(size_t)x * S + i]) - ebg : 0.f;
+        Db[e] = (x < S && j >= 0 && j < S) ? expf(A[(size_t)j * S + x]) - ebg : 0.f;
+    }
+}
+
+// ---- the promise: every entry outside the band equals `background` bit for bit; one wave per matrix row ----
+__global__ __launch_bounds__(64) void fb_band_verify_kernel(const float *__restrict__ A, int32_t *__restrict__ flag,
+                                                            float background, int reach_left, int reach_right, int S) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const float *row = A + (size_t)j * S;
+    const unsigned want = __float_as_uint(background);
+    bool broken = false;
+    for (int i = lane; i < S; i += 64)
+        if ((i < j - reach_left || i > j + reach_right) && __float_as_uint(row[i]) != want) broken = true;
+    if (broken) *flag = 1;
+}
+
+// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, S, halo) ----
+template <int G>
+__global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
+                                                           const float *__restrict__ initial, const float *__restrict__ Df,
+                                                           const float *__restrict__ Db, const float *__restrict__ m,
+                                                           float *__restrict__ cbuf, const int32_t *__restrict__ flag,
+                                                           float *__restrict__ post, float *__restrict__ loglik, float ebg,
+                                                           int reach_left, int reach_right, int W, int Sd, int B, int T,
+                                                           int S) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int halo = reach_left > reach_right ? reach_left : reach_right, stride = row_stride(S, halo);
+    double *lsum = reinterpret_cast<double *>(lds_raw);                 // [G][16]
+    double *Ls = lsum + G * kWaves;                                      // [G] (L as the float the caller gets)
+    float *rows = reinterpret_cast<float *>(Ls + G);                     // [2][G][stride]
+    float *part = rows + (size_t)2 * G * stride;                         // [2][G][16]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * G;
+    constexpr int kUnroll = G <= 2 ? 8 : (G <= 4 ? 4 : 2);          // diagonal loads in flight per band sum
+
+    int F[G], Fmax = 1;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;       // (0: an item beyond the batch never takes a step)
+        Fmax = F[g] > Fmax ? F[g] : Fmax;
+    }
+    for (int e = tid; e < 2 * G * stride; e += kThreads) rows[e] = 0.f;  // (the halos stay zero for the whole call)
+    // rows an item does not have
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (b0 + g >= B) continue;
+        float *out = post + (size_t)(b0 + g) * T * S;
+        for (size_t e = (size_t)F[g] * S + tid; e < (size_t)T * S; e += kThreads) out[e] = 0.f;
+    }
+    __syncthreads();
+
+    // c_t of every item of the tile from the wave sums of frame t; thread 0 stores it for the backward pass and L
+    auto row_sums = [&](int t, float *c) {
+        const float *p = part + (size_t)(t & 1) * G * kWaves;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            c[g] = sum16(p[g * kWaves + (lane & 15)]);
+            if (tid == 0 && t < F[g]) cbuf[(size_t)(b0 + g) * T + t] = c[g];
+        }
+    };
+
+    // ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1} ----
+    for (int t = 0; t < Fmax; ++t) {
+        float *cur = rows + (size_t)(t & 1) * G * stride;
+        const float *prev = rows + (size_t)((t & 1) ^ 1) * G * stride;
+        float cprev[G], acc[G];
+        if (t > 0) row_sums(t - 1, cprev);
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = 0.f;
+        float mt[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
+        for (int j = tid; j < S; j += kThreads) {
+            float s[G], ot[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                s[g] = 0.f;
+                ot[g] = t < F[g] ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;    // (in flight during the band sum)
+            }
+            if (t > 0) {
+                const float *d = Df + j;
+                const float *x = prev + halo - reach_left + j;
+#pragma unroll kUnroll
+                for (int k = 0; k < W; ++k) {
+                    const float dk = d[(size_t)k * Sd];
+#pragma unroll
+                    for (int g = 0; g < G; ++g) s[g] = fmaf(dk, x[g * stride + k], s[g]);
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (t >= F[g]) continue;
+                const size_t row = (size_t)(b0 + g) * T + t;
+                const float o = ot[g], mm = mt[g];
+                float v;
+                if (t == 0) {
+                    v = expf(initial[j] + o - mm);
+                } else {
+                    const float e = expf(o - mm), c = cprev[g];
+                    const float u = e * (ebg != 0.f ? fmaf(ebg, c, s[g]) : s[g]);
+                    v = c == 0.f ? u * 0.f : u / c;                      // (after a zero-probability frame: 0, or NaN from NaN)
+                }
+                cur[g * stride + halo + j] = v;
+                post[row * S + j] = v;
+                acc[g] += v;
+            }
+        }
+        float *p = part + (size_t)(t & 1) * G * kWaves;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float a = wave_sum(acc[g]);
+            if (lane == 0) p[g * kWaves + wave] = a;
+        }
+        __syncthreads();
+    }
+    {
+        float c[G];
+        row_sums(Fmax - 1, c);
+    }
+    __syncthreads();                                                     // (c_t written by thread 0 is read by all below)
+
+    // ---- L = sum_{t<F} (log c_t + m_t) in fp64; NaN when the sum is NaN or +inf, or the promise is broken ----
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        double a = 0.;
+        for (int t = tid; t < F[g]; t += kThreads) {
+            const size_t row = (size_t)(b0 + g) * T + t;
+            a += log((double)cbuf[row]) + (double)m[row];
+        }
+        a = wave_sum(a);
+        if (lane == 0) lsum[g * kWaves + wave] = a;
+    }
+    __syncthreads();
+    if (tid < G) {
+        double L = 0.;
+        for (int w = 0; w < kWaves; ++w) L += lsum[tid * kWaves + w];
+        float out = (L != L || L == (double)INFINITY) ? NAN : (float)L;
+        if (*flag != 0) out = NAN;
+        Ls[tid] = (double)out;
+        if (b0 + tid < B) loglik[b0 + tid] = out;
+    }
+    __syncthreads();
+    bool bad[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) bad[g] = !isfinite(Ls[g]);
+
+    // ---- backward: b_{F-1} = 1, b_t = E^T w_{t+1}; gamma_t = a_t b_t / c_t in place, w_t = e_t b_t / c_t ----
+    for (int t = Fmax - 1; t >= 0; --t) {
+        float *cur = rows + (size_t)(t & 1) * G * stride;
+        const float *prev = rows + (size_t)((t & 1) ^ 1) * G * stride;
+        const bool step = t < Fmax - 1;
+        float sw[G], acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) sw[g] = acc[g] = 0.f;
+        if (ebg != 0.f && step) {
+            const float *p = part + (size_t)((t & 1) ^ 1) * G * kWaves;
+#pragma unroll
+            for (int g = 0; g < G; ++g) sw[g] = sum16(p[g * kWaves + (lane & 15)]);
+        }
+        float mt[G], ct[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
+            ct[g] = t < F[g] ? cbuf[(size_t)(b0 + g) * T + t] : 1.f;
+        }
+        for (int j = tid; j < S; j += kThreads) {
+            float s[G], ot[G], at[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                s[g] = 0.f;
+                const size_t at_j = ((size_t)(b0 + g) * T + t) * S + j;
+                ot[g] = t < F[g] ? obs[at_j] : 0.f;                      // (in flight during the band sum)
+                at[g] = t < F[g] ? post[at_j] : 0.f;
+            }
+            if (step) {
+                const float *d = Db + j;
+                const float *x = prev + halo + reach_left + j;
+#pragma unroll kUnroll
+                for (int k = 0; k < W; ++k) {
+                    const float dk = d[(size_t)k * Sd];
+#pragma unroll
+                    for (int g = 0; g < G; ++g) s[g] = fmaf(dk, x[g * stride - k], s[g]);
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (t >= F[g]) continue;
+                const size_t row = (size_t)(b0 + g) * T + t;
+                const float o = ot[g], mm = mt[g], c = ct[g], a = at[g];
+                const float beta = t == F[g] - 1 ? 1.f : (ebg != 0.f ? fmaf(ebg, sw[g], s[g]) : s[g]);
+                const float w = (expf(o - mm) * beta) / c;              // (w_0 is never read)
+                post[row * S + j] = bad[g] ? NAN : (a * beta) / c;
+                cur[g * stride + halo + j] = w;
+                acc[g] += w;
+            }
+        }
+        if (ebg != 0.f) {
+            float *p = part + (size_t)(t & 1) * G * kWaves;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float a = wave_sum(acc[g]);
+                if (lane == 0) p[g * kWaves + wave] = a;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace fbb

@@ -39,6 +39,7 @@
 #include "band_tile_forward.hpp"
 #include "stream.hpp"
 #include "forward_backward.hpp"
+#include "forward_backward_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
 
@@ -2510,6 +2511,88 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
                        posterior_out, loglik_out, T, S);
+    return (int)hipGetLastError();
+}
+
+// ---- forward-backward on a band with one constant outside it (forward_backward_band.hpp) ----
+
+// Items per workgroup of fb_band_kernel<G>: as many as the LDS rows let share one load of every diagonal, but no fewer
+// workgroups than compute units while there are items for them (the rule of stream_tile).
+static int fb_band_tile(int B, int S, int halo, int cus) {
+    int G = fbb::kMaxGroup;
+    while (G > 1 && fbb::lds_bytes(G, S, halo) > (size_t)fbb::kMaxLdsBytes) G >>= 1;
+    while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
+    return G;
+}
+
+int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                           int device) {
+    (void)device;
+    if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    if (background != background || background == INFINITY) return 0;
+    if ((size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32) return 0;
+    const int W = fbb::clamp_reach(reach_left, S) + fbb::clamp_reach(reach_right, S) + 1;
+    return (W < S ? W : S) <= fbb::kMaxWindow ? 1 : 0;       // at most 64 in-band entries in a matrix row
+}
+
+size_t torbi_hip_forward_backward_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbb::layout(B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                    const float *initial, int reach_left, int reach_right, float background,
+                                    float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B,
+                                    int T, int S, int device, void *stream) {
+    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (S > fb::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32)
+        return TORBI_HIP_ERANGE;
+    if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device))
+        return TORBI_HIP_EUNSUPPORTED;
+    if (workspace_bytes < torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right))
+        return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbb::Layout l = fbb::layout(B, T, S, reach_left, reach_right);
+    char *base = fb_base(workspace);
+    float *Df = reinterpret_cast<float *>(base + l.Df), *Db = reinterpret_cast<float *>(base + l.Db);
+    float *m = reinterpret_cast<float *>(base + l.m), *cbuf = reinterpret_cast<float *>(base + l.c);
+    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
+    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    hipError_t e;
+    {
+        const size_t n = (size_t)l.W * l.Sd;
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, Df, Db, flag, ebg,
+                           l.reach_left, l.W, l.Sd, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, flag, background, l.reach_left,
+                       l.reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int halo = std::max(l.reach_left, l.reach_right);
+    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
+    const int G = fb_band_tile(B, S, halo, cus);
+    const dim3 grid((B + G - 1) / G);
+    const size_t lds = fbb::lds_bytes(G, S, halo);
+#define TORBI_FB_BAND(g)                                                                                                   \
+    hipLaunchKernelGGL((fbb::fb_band_kernel<g>), grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, Df, \
+                       Db, m, cbuf, flag, posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S)
+    switch (G) {
+        case 8: TORBI_FB_BAND(8); break;
+        case 4: TORBI_FB_BAND(4); break;
+        case 2: TORBI_FB_BAND(2); break;
+        default: TORBI_FB_BAND(1); break;
+    }
+#undef TORBI_FB_BAND
     return (int)hipGetLastError();
 }
 

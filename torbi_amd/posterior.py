@@ -7,8 +7,10 @@ For t < F_b (log space, A indexed [next, prev]):
     log beta_{F-1}[j] = 0                         log beta_t[i]  = logsumexp_j (A[j, i] + o_{t+1}[j] + log beta_{t+1}[j])
     L_b = logsumexp_j log alpha_{F-1}[j]          gamma_t[j]     = exp(log alpha_t[j] + log beta_t[j] - L_b)
 
-The HIP route is csrc/forward_backward.hpp behind torbi_hip_forward_backward / _uniform (include/torbi_hip.h); `gpu=None`
-runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and the numbers.
+The HIP route is csrc/forward_backward.hpp behind torbi_hip_forward_backward / _uniform (include/torbi_hip.h), and for a
+matrix that holds one value outside a band csrc/forward_backward_band.hpp behind torbi_hip_forward_backward_band;
+`gpu=None` runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and
+the numbers.
 """
 import ctypes
 import math
@@ -16,7 +18,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs
+from . import _lib, inputs, viterbi
 
 
 def forward_backward_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -95,9 +97,109 @@ def forward_backward(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     return _run(obs, frames, transition, None, initial, workspace)
 
 
+def forward_backward_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_banded` needs for a (B, T, S) problem with this band."""
+    return int(_lib.load().torbi_hip_forward_backward_band_workspace_bytes(B, T, S, int(reach_left), int(reach_right)))
+
+
+def _covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_forward_backward_band_covers: the band route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_forward_backward_band_covers(B, T, S, int(reach_left), int(reach_right),
+                                                                   ctypes.c_float(background), index))
+
+
+def _run_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
+    """One call of the band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
+    `frames` there: (posterior, log_likelihood)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    device = observation.device
+    lib = _lib.load()
+    post = torch.empty((B, T, S), dtype=torch.float32, device=device)
+    loglik = torch.empty((B,), dtype=torch.float32, device=device)
+    if B == 0:
+        return post, loglik
+    need = lib.torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
+    init = initial.to(device=device, dtype=torch.float32).contiguous()
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    _lib.check(lib.torbi_hip_forward_backward_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(),
+                                                   init.data_ptr(), reach_left, reach_right, ctypes.c_float(background),
+                                                   post.data_ptr(), loglik.data_ptr(), workspace.data_ptr(),
+                                                   workspace.numel(), B, T, S, index, stream),
+               'torbi_hip_forward_backward_band')
+    return post, loglik
+
+
+def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                            initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
+                            workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_backward` for a matrix that holds ONE value outside a band, at the cost of the band alone.
+
+    The caller states the band -- transition[j, i] ([next, prev]) with j - reach_left <= i <= j + reach_right -- and
+    promises that every entry outside it equals `background` bit for bit (`viterbi.band_over` answers both for a device
+    matrix).  The call checks the promise on the device without waiting for it: where it is broken, every log-likelihood
+    and every posterior row t < F_b is NaN.
+
+    Args:
+        observation, batch_frames, transition, initial: as `forward_backward`
+        reach_left, reach_right: the band, >= 0
+        background: the value outside the band, finite or -inf
+        workspace: optional uint8 device tensor of >= `forward_backward_banded_workspace_bytes(B, T, S, reach_left,
+            reach_right)` bytes (then the call allocates nothing but its outputs and can be captured into a graph)
+
+    Returns:
+        (posterior (B, T, S) float32, log_likelihood (B,) float32) on the device; rows t >= F_b are 0
+
+    Raises where the band route does not cover the call (torbi_hip_forward_backward_band_covers: up to 4096 states, at most
+    64 in-band entries in a matrix row, a background that is neither NaN nor +inf).
+    """
+    if transition is None or initial is None:
+        raise RuntimeError('forward_backward_banded needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
+    if reach_left < 0 or reach_right < 0:
+        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
+    if B > 0 and not _covered(B, T, S, reach_left, reach_right, background):
+        raise RuntimeError(f'forward_backward_banded does not cover B={B}, T={T}, S={S}, reach {reach_left}/{reach_right}, '
+                           f'background {background} (forward_backward takes any matrix)')
+    obs, frames = _operands('forward_backward_banded', observation, batch_frames, transition, initial)
+    return _run_band(obs, frames, transition, initial, reach_left, reach_right, background, workspace)
+
+
+def _band(trans, original, B, T, S, index):
+    """(reach_left, reach_right, background) when the band route would take the prepared device matrix `trans` (`original`:
+    the caller's tensor, which the look is remembered with), else None.  The structure is what `viterbi.band_over` answers
+    -- one look per tensor version; an unseen matrix while a stream is capturing has no band -- and the shape what
+    torbi_hip_forward_backward_band_covers takes."""
+    if B < 1:
+        return None
+    over = viterbi.band_over(trans, original, S)
+    if over is None or not _covered(B, T, S, over[0], over[1], over[2], index):
+        return None
+    return over
+
+
+def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
+                    log_probs: bool = False) -> str:
+    """The route `state_posteriors(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
+    (batch, frames, states) observation: 'uniform' (no matrix: the closed form), 'band' (one value outside a band:
+    `forward_backward_banded`) or 'dense' (`forward_backward`)."""
+    if transition is None:
+        return 'uniform'
+    if tuple(transition.shape) != (states, states):
+        raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
+    device = inputs._compute_device(gpu)
+    if device.type == 'cpu':
+        return 'dense'
+    trans = inputs._prepared_transition(transition, log_probs, device)
+    return 'dense' if _band(trans, transition, int(batch), int(frames), states, device.index) is None else 'band'
+
+
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
                      transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None,
-                     log_probs: bool = False, gpu: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto'
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
     """P(state_t = j | all frames) of every frame, and log P(observations) of every item.
 
     Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
@@ -106,19 +208,34 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     (beta is constant over states).  `gpu` is a HIP device index; None computes in float64 on the CPU.  The caller's
     tensors are not written.
 
+    route: which device route a given matrix takes.  'auto': the band route where the matrix holds one value outside a
+        band that route covers (`posterior_route` answers which), else the dense one; 'dense': always the dense route;
+        'band': the band route, raising where the matrix has no covered band.  Both meet the same tolerance against
+        float64; their roundings differ.  Ignored by `gpu=None` and `transition=None`.
+
     Returns:
         (posterior (batch, frames, states) float32, log_likelihood (batch,) float32) on the compute device.  Rows
         t >= batch_frames[b] are 0; an item of total probability 0 has log-likelihood -inf and NaN rows, an item that reads
         a NaN or +inf has NaN for both.
     """
+    if route not in ('auto', 'dense', 'band'):
+        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
+    original = transition
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
     obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
         return gamma.to(torch.float32), L.to(torch.float32)
+    if uniform is None and route != 'dense':
+        band = _band(transition, original, B, T, S, device.index)
+        if band is not None:
+            return _run_band(obs, frames, transition, initial, band[0], band[1], band[2])
+        if route == 'band':
+            raise RuntimeError("state_posteriors(route='band'): the transition matrix has no band that "
+                               'forward_backward_banded covers')
     return _run(obs, frames, transition, uniform, initial)
 
 

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include "scratch.hpp"
 
 namespace fb {
 
@@ -36,27 +37,27 @@ constexpr int kRowRegs = 8;                 // float4 per lane of a uniform-rout
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__host__ __device__ inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
-__host__ __device__ inline int padded_states(int S) { return (int)round_up((size_t)S, 32); }
-__host__ __device__ inline int padded_rows(int S) { return (int)round_up((size_t)S, 64); }
+__host__ __device__ inline int padded_states(int S) { return (int)align_up((size_t)S, 32); }
+__host__ __device__ inline int padded_rows(int S) { return (int)align_up((size_t)S, 64); }
 __host__ __device__ inline int partials_of(int S) { return (S + kRowsPerPartial - 1) / kRowsPerPartial; }
 
 struct Layout {
-    size_t E, Et, m, c, partial, w, total;
+    float *E, *Et, *m, *c, *partial, *w;
+    size_t total;
 };
 
-inline Layout layout(int B, int T, int S) {
+// `base`: the caller's workspace aligned up to 256 bytes, or null for the byte count alone
+inline Layout layout(char *base, int B, int T, int S) {
     const size_t Sp = (size_t)padded_states(S), Mp = (size_t)padded_rows(S), BT = (size_t)B * T;
+    Scratch a(base);
     Layout l;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at = round_up(at + bytes, 256); return here; };
-    l.E = take(Mp * Sp * 4);
-    l.Et = take(Mp * Sp * 4);
-    l.m = take(BT * 4);
-    l.c = take(BT * 4);
-    l.partial = take(BT * (size_t)partials_of(S) * 4);
-    l.w = take((size_t)2 * B * Sp * 4);
-    l.total = at + 256;                      // (room to align the caller's base)
+    l.E = a.take<float>(Mp * Sp);
+    l.Et = a.take<float>(Mp * Sp);
+    l.m = a.take<float>(BT);
+    l.c = a.take<float>(BT);
+    l.partial = a.take<float>(BT * (size_t)partials_of(S));
+    l.w = a.take<float>((size_t)2 * B * Sp);
+    l.total = a.bytes + 256;                 // (room to align the caller's base)
     return l;
 }
 

@@ -40,23 +40,23 @@ __host__ __device__ inline int clamp_reach(int reach, int S) { return reach < 0 
 
 struct Layout {
     int reach_left, reach_right, W, Sd;      // (the reaches clamped to S - 1)
-    size_t Df, Db, m, c, flag, total;
+    float *Df, *Db, *m, *c; int32_t *flag; size_t total;
 };
 
-inline Layout layout(int B, int T, int S, int reach_left, int reach_right) {
+// `base`: the caller's workspace aligned up to 256 bytes, or null for the byte count alone
+inline Layout layout(char *base, int B, int T, int S, int reach_left, int reach_right) {
     Layout l;
     l.reach_left = clamp_reach(reach_left, S);
     l.reach_right = clamp_reach(reach_right, S);
     l.W = l.reach_left + l.reach_right + 1;
-    l.Sd = (int)fb::round_up((size_t)S, 64);
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at = fb::round_up(at + bytes, 256); return here; };
-    l.Df = take((size_t)l.W * l.Sd * 4);
-    l.Db = take((size_t)l.W * l.Sd * 4);
-    l.m = take((size_t)B * T * 4);
-    l.c = take((size_t)B * T * 4);
-    l.flag = take(4);
-    l.total = at + 256;                      // (room to align the caller's base)
+    l.Sd = (int)align_up((size_t)S, 64);
+    Scratch a(base);
+    l.Df = a.take<float>((size_t)l.W * l.Sd);
+    l.Db = a.take<float>((size_t)l.W * l.Sd);
+    l.m = a.take<float>((size_t)B * T);
+    l.c = a.take<float>((size_t)B * T);
+    l.flag = a.take<int32_t>(1);
+    l.total = a.bytes + 256;                 // (room to align the caller's base)
     return l;
 }
 

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include "scratch.hpp"
 
 namespace kb {
 
@@ -36,28 +37,24 @@ struct Final {
 };
 
 struct Layout {
-    size_t vals, ptrs, tt, final_, count, flag, total;
+    float *vals, *tt;
+    int32_t *ptrs, *count, *flag;
+    Final *final_;
+    size_t total;
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The uniform route uses layout(B, T, 1, k): its pointers have no state axis and it needs neither vals nor tt.
-inline Layout layout(int B, int T, int S, int k) {
+// `base`: the caller's workspace aligned up to 256 bytes, or null for the byte count alone.
+// The uniform route uses layout(base, B, T, 1, k): its pointers have no state axis and it needs neither vals nor tt.
+inline Layout layout(char *base, int B, int T, int S, int k) {
+    Scratch a(base);
     Layout l;
-    size_t at = 0;
-    l.vals = at;
-    at += align256((size_t)2 * B * k * S * sizeof(float));
-    l.ptrs = at;
-    at += align256((size_t)B * (T - 1) * k * S * sizeof(int32_t));
-    l.tt = at;
-    at += align256((size_t)S * S * sizeof(float));
-    l.final_ = at;
-    at += align256((size_t)B * k * sizeof(Final));
-    l.count = at;
-    at += align256((size_t)B * sizeof(int32_t));
-    l.flag = at;
-    at += align256((size_t)(B + 1) * sizeof(int32_t));     // [0]: matrix flag, [1 + b]: item flag
-    l.total = at + 256;                                      // (the base is aligned up to 256 bytes)
+    l.vals = a.take<float>((size_t)2 * B * k * S);
+    l.ptrs = a.take<int32_t>((size_t)B * (T - 1) * k * S);
+    l.tt = a.take<float>((size_t)S * S);
+    l.final_ = a.take<Final>((size_t)B * k);
+    l.count = a.take<int32_t>((size_t)B);
+    l.flag = a.take<int32_t>((size_t)B + 1);     // [0]: matrix flag, [1 + b]: item flag
+    l.total = a.bytes + 256;                     // (room to align the caller's base)
     return l;
 }
 

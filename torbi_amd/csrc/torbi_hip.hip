@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "torbi_hip.h"
+#include "scratch.hpp"
 #include "dense_forward.hpp"
 #include "lazy_backtrace.hpp"
 #include "uniform_decode.hpp"
@@ -50,8 +51,6 @@ constexpr int kWave = 64;
 // ---------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------
-
-__host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // (value, index) comparator of the reference CPU scan (viterbi.cpp:94-100): a candidate
 // replaces the incumbent only if strictly greater; among equal values the lower index wins.
@@ -617,8 +616,8 @@ inline Route route_for(int path, int B, int S, int cus, bool allow_held = true) 
 }
 
 // ---- workspace layouts: the (B,T,S) history / trellis first, the per-transition preparation behind it ---------
-inline size_t history_bytes(int B, int T, int S) { return align_up(sizeof(float) * (size_t)B * T * S, 256); }
-
+// Every layout states each region once, as a take of a Scratch (scratch.hpp), and its `bytes` are the cursor behind the last
+// of them; a size query lays the same regions out on a null base.
 struct Workspace {
     float *post[2];     // (B,S) ping-pong posterior rows
     int32_t *trellis;   // (B,T,S) backpointers; rows t >= 1 of valid frames are written
@@ -631,59 +630,61 @@ struct Workspace {
 };
 
 inline Workspace carve(void *base, int B, int T, int S) {
-    Workspace w;
-    char *p = static_cast<char *>(base);
-    const size_t post_bytes = align_up(sizeof(float) * (size_t)B * S, 256);
-    w.trellis = reinterpret_cast<int32_t *>(p);
-    w.post[0] = reinterpret_cast<float *>(p + history_bytes(B, T, S));
-    w.post[1] = reinterpret_cast<float *>(p + history_bytes(B, T, S) + post_bytes);
-    w.bytes = history_bytes(B, T, S) + 2 * post_bytes;
-    w.xchg = nullptr;
-    w.control = nullptr;
+    Scratch a(base);
+    Workspace w{};
+    w.trellis = a.take<int32_t>((size_t)B * T * S);
+    for (float *&post : w.post) post = a.take<float>((size_t)B * S);
     if (B <= held::kMaxB && S <= held::kMaxS) {
-        w.control = reinterpret_cast<unsigned *>(p + w.bytes);
-        w.xchg = reinterpret_cast<held::u64 *>(p + w.bytes + 256);
-        w.bytes += 256 + align_up(held::exchange_bytes(B, S), 256);
+        w.control = a.take<unsigned>(64);
+        w.xchg = a.take<held::u64>(held::exchange_bytes(B, S) / sizeof(held::u64));
     }
-    w.maps = nullptr;
-    w.entries = nullptr;
     if (B <= held::kMaxB && S <= held::kMaxS && T - 1 >= kChaseMinSteps) {
         const size_t chunks = (size_t)chase_chunks(T);
-        w.maps = reinterpret_cast<int32_t *>(p + w.bytes);
-        w.bytes += align_up(sizeof(int32_t) * (size_t)B * chunks * S, 256);
-        w.entries = reinterpret_cast<int32_t *>(p + w.bytes);
-        w.bytes += align_up(sizeof(int32_t) * (size_t)B * chunks, 256);
+        w.maps = a.take<int32_t>((size_t)B * chunks * S);
+        w.entries = a.take<int32_t>((size_t)B * chunks);
     }
-    w.arrive = nullptr;
-    if (small::block_supported(S) && B <= 1024) {
-        w.arrive = reinterpret_cast<int32_t *>(p + w.bytes);
-        w.bytes += align_up(sizeof(int32_t) * (size_t)B * 8, 256);
-    }
+    if (small::block_supported(S) && B <= 1024) w.arrive = a.take<int32_t>((size_t)B * 8);
+    w.bytes = a.bytes;
     return w;
 }
 
+// The per-transition preparation of the list scans: every row sorted and arranged (pruned::sort_rows_kernel; a row holds SpP
+// entries, the sort works on NPOW), and for the time-resident routes the transposed matrix and the rows' finite ranges.
+struct ListShape { int SpP, NPOW; };
+inline ListShape list_shape(int S) {
+    ListShape l{(S + 15) / 16 * 16 + pruned::kPad, 64};
+    while (l.NPOW < S) l.NPOW *= 2;
+    return l;
+}
+struct PreparedLists { float2 *sorted; float *tt; int32_t *row_range; };
+inline PreparedLists lay_preparation(Scratch &a, int S) {
+    PreparedLists l;
+    l.sorted = a.take<float2>((size_t)S * list_shape(S).SpP);
+    l.tt = a.take<float>((size_t)S * S);
+    l.row_range = a.take<int32_t>(2 * (size_t)S);
+    return l;
+}
+inline size_t preparation_bytes(int S) { Scratch a(nullptr); lay_preparation(a, S); return a.bytes; }
+
 // the time-resident path: history, tile map, row maxima, sorted lists / transposed matrix, cluster exchange
-struct ResidentWorkspace {
+struct ResidentWorkspace : PreparedLists, ListShape {
     float *hist;
-    float2 *sorted;
-    float *tt;
-    int32_t *row_range;
     int32_t *order;       // [B] this batch's items by descending length
     float *rowmax;        // [B][T] largest entry of every posterior row (left by the forward kernel for the backtrace)
     int32_t *lengths_hist;  // [T + 2] items per length (batches above resident::kMaxOrdered items only, else null)
     size_t lengths_hist_bytes;
     int32_t *tile_map;    // [kMaxGroupTiles] workgroup -> tile of the launch group (first batch's workspace)
     unsigned *stats;      // [128] scan statistics of the last launch group (first batch's workspace)
-    // cluster form (first batch's workspace): exchange buffers of up to cus / 2 tiles
-    float *xchg;          // [tiles][2][S4][16]
-    unsigned *flags;      // [tiles][kMaxR] + 16 control words
-    size_t flag_bytes;
-    int SpP, NPOW;
+    // cluster form (first batch's workspace): exchange buffers of up to cus / 2 tiles, and ONE block of `nflags` words that
+    // order_tiles_kernel zeroes as a whole -- the parts of resident::Cluster
+    float *xchg;          // [tiles][kSlots] slots
+    unsigned *flags, *control, *failed, *where;      // [tiles][kMaxR], [16], [tiles], [tiles][kMaxR]
+    int nflags;
     size_t bytes;
 };
 
-// The per-transition preparation of the time-resident routes (sorted + arranged rows, transposed matrix, row ranges)
-// may live OUTSIDE the workspace (torbi_hip_viterbi_decode_batches_prepared): a caller that allocates a workspace per call
+// The per-transition preparation of the time-resident routes may live OUTSIDE the workspace
+// (torbi_hip_viterbi_decode_batches_prepared): a caller that allocates a workspace per call
 // -- the reference's own calling pattern, torbi/core.py:200-206 -- keeps 25 MB per matrix instead of rebuilding it
 // (0.25 ms per call at 1440 states).  Travels as an argument from the entry point to the one layout that reads it.
 struct Preparation {
@@ -702,53 +703,36 @@ inline int new_serial() {
     t_serial = (int)v;
     return t_serial;
 }
-inline size_t preparation_bytes(int S) {
-    const int Sp = (S + 15) / 16 * 16;
-    return align_up(sizeof(float2) * (size_t)S * (Sp + pruned::kPad), 256) + align_up(sizeof(float) * (size_t)S * S, 256) +
-           align_up(sizeof(int32_t) * 2 * (size_t)S, 256);
-}
 
 // `kept`: the caller's preparation buffer (run_resident only; every other layout of a workspace is the plain one)
 inline ResidentWorkspace carve_resident(void *base, int B, int T, int S, int cus, const Preparation *kept = nullptr) {
-    ResidentWorkspace w;
-    char *p = static_cast<char *>(base);
-    const int Sp = (S + 15) / 16 * 16;
-    w.SpP = Sp + pruned::kPad;
-    w.NPOW = 64;
-    while (w.NPOW < S) w.NPOW *= 2;
-    const size_t hist_bytes = history_bytes(B, T, S);
-    const size_t sorted_bytes = align_up(sizeof(float2) * (size_t)S * w.SpP, 256);
-    const size_t tt_bytes = align_up(sizeof(float) * (size_t)S * S, 256);
-    const size_t range_bytes = align_up(sizeof(int32_t) * 2 * (size_t)S, 256);
-    const size_t hist_len = B > resident::kMaxOrdered ? align_up(sizeof(int32_t) * ((size_t)T + 2), 256) : 0;
-    const size_t order_bytes = align_up(sizeof(int32_t) * (size_t)B, 256) + sizeof(int32_t) * (kMaxGroupTiles + 128) + hist_len;
-    const size_t ctiles = (size_t)std::max(cus / 2, 1);                 // a cluster launch holds at most this many tiles
-    const size_t xchg_bytes = align_up(ctiles * resident::kSlots * resident::cluster_slot_bytes(S), 256);
-    w.flag_bytes = align_up(sizeof(unsigned) * (2 * ctiles * resident::kMaxR + 16 + ctiles), 256);    // flags, control, failed, where
-    w.hist = reinterpret_cast<float *>(p);
-    p += hist_bytes;
-    w.tile_map = reinterpret_cast<int32_t *>(p);   // ahead of the preparation: offsets depend on B and T only
-    w.stats = reinterpret_cast<unsigned *>(w.tile_map + kMaxGroupTiles);
-    w.order = w.tile_map + kMaxGroupTiles + 128;
-    w.lengths_hist_bytes = hist_len;
-    w.lengths_hist = hist_len ? reinterpret_cast<int32_t *>(p + order_bytes - hist_len) : nullptr;
-    p += order_bytes;
-    const size_t rowmax_bytes = align_up(sizeof(float) * (size_t)B * T, 256);
-    w.rowmax = reinterpret_cast<float *>(p);
-    p += rowmax_bytes;
-    w.sorted = reinterpret_cast<float2 *>(p);
-    w.tt = reinterpret_cast<float *>(p + sorted_bytes);
-    w.row_range = reinterpret_cast<int32_t *>(p + sorted_bytes + tt_bytes);
-    if (base && kept && kept->bytes >= preparation_bytes(S)) {      // (the caller keeps it: see above)
-        char *q = static_cast<char *>(kept->pointer);
-        w.sorted = reinterpret_cast<float2 *>(q);
-        w.tt = reinterpret_cast<float *>(q + sorted_bytes);
-        w.row_range = reinterpret_cast<int32_t *>(q + sorted_bytes + tt_bytes);
+    Scratch a(base);
+    ResidentWorkspace w{};
+    static_cast<ListShape &>(w) = list_shape(S);
+    w.hist = a.take<float>((size_t)B * T * S);
+    w.tile_map = a.take<int32_t>(kMaxGroupTiles);      // ahead of the preparation: offsets depend on B and T only
+    w.stats = a.take<unsigned>(128);
+    w.order = a.take<int32_t>((size_t)B);
+    if (B > resident::kMaxOrdered) {
+        const size_t hist_at = a.bytes;
+        w.lengths_hist = a.take<int32_t>((size_t)T + 2);
+        w.lengths_hist_bytes = a.bytes - hist_at;      // (what assemble_group clears: to the end of the region)
     }
-    p += sorted_bytes + tt_bytes + range_bytes;
-    w.xchg = reinterpret_cast<float *>(p);
-    w.flags = reinterpret_cast<unsigned *>(p + xchg_bytes);
-    w.bytes = hist_bytes + order_bytes + rowmax_bytes + sorted_bytes + tt_bytes + range_bytes + xchg_bytes + w.flag_bytes;
+    w.rowmax = a.take<float>((size_t)B * T);
+    static_cast<PreparedLists &>(w) = lay_preparation(a, S);      // (the span stays in the workspace either way)
+    if (base && kept && kept->bytes >= preparation_bytes(S)) {      // (the caller keeps it: see above)
+        Scratch theirs(kept->pointer);
+        static_cast<PreparedLists &>(w) = lay_preparation(theirs, S);
+    }
+    const size_t ctiles = (size_t)std::max(cus / 2, 1);                 // a cluster launch holds at most this many tiles
+    w.xchg = a.take<float>(ctiles * resident::kSlots * resident::cluster_slot_bytes(S) / sizeof(float));
+    const size_t flags_at = a.bytes;
+    w.flags = a.take<unsigned>(2 * ctiles * resident::kMaxR + 16 + ctiles);
+    w.control = behind(w.flags, ctiles * resident::kMaxR);
+    w.failed = behind(w.control, 16);
+    w.where = behind(w.failed, ctiles);
+    w.nflags = (int)((a.bytes - flags_at) / sizeof(unsigned));      // (to the end of the block)
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -758,50 +742,43 @@ inline bool band_shape(int S) { return S % 4 == 0 && resident::supported(S) && S
 struct BandWorkspace {
     ResidentWorkspace base;
     char *xchg;
-    size_t xchg_bytes;
-    unsigned *words;      // [16 ..] failed[kMaxGroupTiles], behind them [8] tickets per launch of the group
+    // ONE block of words that band::clear_exchange_kernel zeroes from its start
+    unsigned *words, *failed, *tickets;      // [16], [kMaxGroupTiles], [8] per launch of the group
     float *tpack;         // whole tiles (band_tile_forward.hpp): the band as the lanes read it
     size_t bytes;
 };
 constexpr size_t kBandWords = 16 + 2 * (size_t)kMaxGroupTiles + 64;
 inline BandWorkspace carve_band(void *base, int B, int T, int S, int cus) {
-    BandWorkspace w;
+    BandWorkspace w{};
     w.base = carve_resident(base, B, T, S, cus);     // (the band route keeps nothing in a caller's preparation buffer)
-    char *p = static_cast<char *>(base) + w.base.bytes;
-    w.xchg_bytes = align_up(band::xchg_bytes(B, S), 256);
-    w.xchg = p;
-    w.words = reinterpret_cast<unsigned *>(p + w.xchg_bytes);
-    const size_t word_bytes = align_up(sizeof(unsigned) * kBandWords, 256);
-    w.tpack = reinterpret_cast<float *>(p + w.xchg_bytes + word_bytes);
-    w.bytes = w.base.bytes + w.xchg_bytes + word_bytes + align_up(band::tile_pack_bytes_max(S), 256);
+    Scratch a(base, w.base.bytes);
+    w.xchg = a.take<char>(band::xchg_bytes(B, S));
+    w.words = a.take<unsigned>(kBandWords);
+    w.failed = behind(w.words, 16);
+    w.tickets = behind(w.failed, kMaxGroupTiles);
+    w.tpack = a.take<float>(band::tile_pack_bytes_max(S) / sizeof(float));
+    w.bytes = a.bytes;
     return w;
 }
 
 // small batches (B <= 16): history + sorted rows (small_batch_forward.hpp)
-struct RowsWorkspace {
+struct RowsWorkspace : ListShape {
     float *hist;
     float2 *sorted;
     int32_t *row_range;
     float *rowmax;     // [B][T] largest entry of every posterior row (step_rows_sorted_kernel leaves it for the backtrace)
-    int SpP, NPOW;
     size_t bytes;
 };
 
 inline RowsWorkspace carve_rows(void *base, int B, int T, int S) {
-    RowsWorkspace w;
-    char *p = static_cast<char *>(base);
-    const int Sp = (S + 15) / 16 * 16;
-    w.SpP = Sp + pruned::kPad;
-    w.NPOW = 64;
-    while (w.NPOW < S) w.NPOW *= 2;
-    const size_t sorted_bytes = align_up(sizeof(float2) * (size_t)S * w.SpP, 256);
-    w.hist = reinterpret_cast<float *>(p);
-    p += history_bytes(B, T, S);
-    w.sorted = reinterpret_cast<float2 *>(p);
-    w.row_range = reinterpret_cast<int32_t *>(p + sorted_bytes);
-    const size_t range_bytes = align_up(sizeof(int32_t) * 2 * (size_t)S, 256);
-    w.rowmax = reinterpret_cast<float *>(p + sorted_bytes + range_bytes);
-    w.bytes = history_bytes(B, T, S) + sorted_bytes + range_bytes + align_up(sizeof(float) * (size_t)B * T, 256);
+    Scratch a(base);
+    RowsWorkspace w{};
+    static_cast<ListShape &>(w) = list_shape(S);
+    w.hist = a.take<float>((size_t)B * T * S);
+    w.sorted = a.take<float2>((size_t)S * w.SpP);
+    w.row_range = a.take<int32_t>(2 * (size_t)S);
+    w.rowmax = a.take<float>((size_t)B * T);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -811,26 +788,22 @@ struct DenseWorkspace {
     float *panel[2];   // [n_bt][Kp][BT] posterior panels (ping-pong)
     float *trp;        // [n_jt][Kp][W]  packed transition panels
     int32_t *chunks;   // [n_jt][NCH+1]  per-tile lists of chunks that are not all -inf
-    int32_t *ranges;   // [S][2] finite range of every transition row + [64] (first word: the widest row window)
+    int32_t *ranges;   // [S][2] finite range of every transition row, and in the same block ...
+    int32_t *widest;   // ... [64], first word: the widest row window
     size_t bytes;
 };
 
 inline DenseWorkspace carve_dense(void *base, int B, int T, int S, int cus) {
-    DenseWorkspace w;
+    Scratch a(base);
+    DenseWorkspace w{};
     w.plan = dense::make_plan(B, S, cus);
-    char *p = static_cast<char *>(base);
-    const size_t panel_bytes = align_up(sizeof(float) * (size_t)w.plan.n_bt * w.plan.Kp * w.plan.BT, 256);
-    const size_t trp_bytes = align_up(sizeof(float) * (size_t)w.plan.n_jt * w.plan.Kp * w.plan.W, 256);
-    const size_t list_bytes = align_up(sizeof(int32_t) * (size_t)w.plan.n_jt * (w.plan.NCH + 1), 256);
-    w.hist = reinterpret_cast<float *>(p);
-    p += history_bytes(B, T, S);
-    w.panel[0] = reinterpret_cast<float *>(p);
-    w.panel[1] = reinterpret_cast<float *>(p + panel_bytes);
-    w.trp = reinterpret_cast<float *>(p + 2 * panel_bytes);
-    w.chunks = reinterpret_cast<int32_t *>(p + 2 * panel_bytes + trp_bytes);
-    w.ranges = reinterpret_cast<int32_t *>(p + 2 * panel_bytes + trp_bytes + list_bytes);
-    w.bytes = history_bytes(B, T, S) + 2 * panel_bytes + trp_bytes + list_bytes +
-              align_up(sizeof(int32_t) * (2 * (size_t)S + 64), 256);
+    w.hist = a.take<float>((size_t)B * T * S);
+    for (float *&panel : w.panel) panel = a.take<float>((size_t)w.plan.n_bt * w.plan.Kp * w.plan.BT);
+    w.trp = a.take<float>((size_t)w.plan.n_jt * w.plan.Kp * w.plan.W);
+    w.chunks = a.take<int32_t>((size_t)w.plan.n_jt * (w.plan.NCH + 1));
+    w.ranges = a.take<int32_t>(2 * (size_t)S + 64);
+    w.widest = behind(w.ranges, 2 * (size_t)S);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -841,7 +814,7 @@ inline size_t layout_bytes(int B, int T, int S, int cus) {
     if (resident::supported(S)) need = std::max(need, carve_resident(nullptr, B, T, S, cus).bytes);
     if (rowscan::supported(B, S)) need = std::max(need, carve_rows(nullptr, B, T, S).bytes);
     if (band_shape(S)) need = std::max(need, carve_band(nullptr, B, T, S, cus).bytes);
-    return align_up(need, 256);
+    return need;
 }
 // ... plus the ROUTE RECORD behind every layout: the forward path the last decode with this workspace actually took
 // (a Route), written on the stream by that decode and read ON THE DEVICE by torbi_hip_read_posterior /
@@ -855,9 +828,9 @@ inline int32_t *route_record(const void *workspace, int B, int T, int S, int cus
 }
 __global__ void stamp_route_kernel(int32_t *record, int route) { *record = route; }
 __global__ void fill_pair_kernel(int32_t *pair, int a, int b) { pair[0] = a; pair[1] = b; }
-inline hipError_t stamp_route(void *workspace, int B, int T, int S, int cus, Route route, hipStream_t s) {
+inline hipError_t stamp_route(int32_t *record, Route route, hipStream_t s) {
     // (a one-thread kernel: hipMemsetD32Async costs ~0.17 ms per call on this stack)
-    hipLaunchKernelGGL(stamp_route_kernel, dim3(1), dim3(1), 0, s, route_record(workspace, B, T, S, cus), (int)route);
+    hipLaunchKernelGGL(stamp_route_kernel, dim3(1), dim3(1), 0, s, record, (int)route);
     return hipGetLastError();
 }
 
@@ -1148,8 +1121,8 @@ hipError_t launch_dense_forward(const float *obs, const int32_t *frames, const f
                            sizeof(int) * (size_t)pl.NCH, stream, w.trp, w.chunks, S, pl.JT, pl.W, pl.Kp, pl.NCH,
                            pl.KC);
         // for the backtrace: the finite range of every row and the widest of them (lazy_backtrace.hpp)
-        hipLaunchKernelGGL(stamp_route_kernel, dim3(1), dim3(1), 0, stream, w.ranges + 2 * (size_t)S, 0);
-        hipLaunchKernelGGL(lazy::row_ranges_kernel, dim3(S), dim3(64), 0, stream, trans, w.ranges, w.ranges + 2 * (size_t)S, S);
+        hipLaunchKernelGGL(stamp_route_kernel, dim3(1), dim3(1), 0, stream, w.widest, 0);
+        hipLaunchKernelGGL(lazy::row_ranges_kernel, dim3(S), dim3(64), 0, stream, trans, w.ranges, w.widest, S);
     }
     {
         const size_t n = (size_t)pl.n_bt * pl.BT * pl.Kp;
@@ -1236,6 +1209,7 @@ struct HostBatch {
     int32_t *out;
     void *workspace;
     int B, T;
+    int32_t *record;      // the workspace's route record (route_record: behind every layout)
 };
 
 // seeds per item of a time-resident launch (3, or 1: `few`) from the call's flags: FEW -> one, MANY -> three, neither -> one
@@ -1315,14 +1289,14 @@ inline int backtrace_segments(int items) {
 // ---- NaN / +inf inputs (nonfinite.hpp): alarms raised with the decode's serial number, a repair launch behind the decode ----
 // Ahead of a decode's forward launches: the matrix and the initial vector; the observations too for the routes whose
 // forward kernels do not look at what they produce (a launch per timestep: generic, held, rows, dense).
-inline hipError_t nonfinite_begin(const HostBatch *hb, int n, const float *trans, const float *init, int S, int cus, hipStream_t s,
+inline hipError_t nonfinite_begin(const HostBatch *hb, int n, const float *trans, const float *init, int S, hipStream_t s,
                                   bool scan_observations, int reach_left = -1, int reach_right = -1, bool scan_matrix = true,
                                   float background = -INFINITY) {
     const int serial = new_serial();
     if (!scan_matrix) return hipSuccess;            // (the small-state kernels hold the whole matrix: they look themselves)
     nonfinite::Records recs{};
     recs.n = n;
-    for (int k = 0; k < n; ++k) recs.record[k] = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
+    for (int k = 0; k < n; ++k) recs.record[k] = hb[k].record;
     const size_t cells = (size_t)S * S;
     hipLaunchKernelGGL(nonfinite::matrix_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(1024, (cells + 2047) / 2048))),
                        dim3(256), 0, s, trans, init, S, recs, serial, reach_left, reach_right, background);
@@ -1336,7 +1310,7 @@ inline hipError_t nonfinite_begin(const HostBatch *hb, int n, const float *trans
     return hipGetLastError();
 }
 // Behind the decode's backtrace: does nothing unless an alarm carries this decode's serial number.
-inline hipError_t nonfinite_end(const HostBatch *hb, int n, const float *trans, const float *init, int S, int cus, hipStream_t s) {
+inline hipError_t nonfinite_end(const HostBatch *hb, int n, const float *trans, const float *init, int S, hipStream_t s) {
     nonfinite::RepairJobs jobs{};
     jobs.n = n;
     int items = 0;
@@ -1345,7 +1319,7 @@ inline hipError_t nonfinite_end(const HostBatch *hb, int n, const float *trans, 
         jobs.frames[k] = hb[k].frames;
         jobs.out[k] = hb[k].out;
         jobs.trellis[k] = static_cast<int32_t *>(hb[k].workspace);
-        jobs.record[k] = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
+        jobs.record[k] = hb[k].record;
         jobs.rows[k] = reinterpret_cast<float *>(reinterpret_cast<char *>(jobs.record[k]) + 256);
         jobs.B[k] = hb[k].B;
         jobs.T[k] = hb[k].T;
@@ -1383,15 +1357,14 @@ hipError_t assemble_group(const HostBatch *hb, int n, int S, int cus, hipStream_
     for (int k = 0; k < n; ++k) {
         resident::Batch &b = grp.batch[k];
         const ResidentWorkspace wk = carve_resident(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        int32_t *const record = route_record(hb[k].workspace, hb[k].B, hb[k].T, S, cus);
-        b.alarm = record + nonfinite::kAlarmWord;
+        b.alarm = hb[k].record + nonfinite::kAlarmWord;
         b.obs = hb[k].obs;
         b.frames = hb[k].frames;
         b.out = hb[k].out;
         b.hist = wk.hist;
         b.order = wk.order;
         b.rowmax = wk.rowmax;
-        jobs.job[k] = resident::OrderJob{hb[k].frames, wk.order, hb[k].B, hb[k].T, tiles, wk.lengths_hist, record, (int)route};
+        jobs.job[k] = resident::OrderJob{hb[k].frames, wk.order, hb[k].B, hb[k].T, tiles, wk.lengths_hist, hb[k].record, (int)route};
         widest = std::max(widest, hb[k].B);
         b.B = hb[k].B;
         b.T = hb[k].T;
@@ -1435,7 +1408,7 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
                         hipEvent_t *ev, int *launches, bool reuse, bool ascending, bool clusters, bool few,
                         Preparation *kept) {
     {
-        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, cus, s, false);
+        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, s, false);
         if (ne != hipSuccess) return ne;
     }
     int tiles = 0;
@@ -1443,22 +1416,20 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
     const ResidentWorkspace w = carve_resident(hb[0].workspace, hb[0].B, hb[0].T, S, cus, kept);
     // cluster form: R workgroups per tile (exchange buffers in the first batch's workspace, flags and tickets zeroed)
     const int R = clusters ? cluster_members(tiles, S, cus) : 1;
-    unsigned *const control = w.flags + (size_t)std::max(cus / 2, 1) * resident::kMaxR;
-    // (flags [ctiles][kMaxR], control [16], failed [ctiles], where [ctiles][kMaxR]: all zeroed by order_tiles_kernel)
     // Above 2048 states (8-item tiles) the sorted lists are what the launch fetches -- 134 MB at 4096 states, far beyond an
     // XCD's 4 MB L2, walked by every tile: 232 GB per 128 x 2000 x 4096 decode against 8.4 GB algorithmic
     // (profiles/r06_c5_pmc.json).  Member m of EVERY tile on one XCD keeps that member's rows' lists in its L2; the exchange
     // then crosses XCDs (write-through), which costs less than it saves there: 19.8 -> 17.3 us per timestep at 128 items,
     // 34.3 -> 30.6 at 256; up to 2048 states it loses 1-3 % (profiles/r06_c5_spread.txt).
     const int spread = (R % 8 == 0 && resident::tile_items(S) == 8) ? 1 : 0;
-    resident::Cluster clu{w.xchg, control + 16 + std::max(cus / 2, 1), tiles, control, control + 16, R, cluster_wait_ticks(), spread};
+    resident::Cluster clu{w.xchg, w.where, tiles, w.control, w.failed, R, cluster_wait_ticks(), spread};
     if (ev) (void)hipEventRecord(ev[0], s);
     if (kept) reuse = kept->valid;       // the caller's buffer: the promise is about IT, whichever batch
     if (!reuse) launch_list_preparation(trans, w.sorted, w.row_range, w.tt, S, w.SpP, w.NPOW, resident::tile_items(S), s);
     if (kept) kept->valid = true;
     LaunchGroup group;
     hipError_t e = assemble_group(hb, n, S, cus, s, ascending, resident::tile_items(S), R > 1 ? ROUTE_CLUSTER : ROUTE_RESIDENT,
-                                  w.flags, R > 1 ? (int)(w.flag_bytes / sizeof(unsigned)) : 0, group);
+                                  w.flags, R > 1 ? w.nflags : 0, group);
     if (e != hipSuccess) return e;
     const resident::Group &grp = group.grp;
     const int items = group.items;
@@ -1523,7 +1494,7 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
     } else
         hipLaunchKernelGGL(resident::group_backtrace_kernel<1>, dim3(items), dim3(64), 0, s, grp, trans, S);
     {
-        const hipError_t ne = nonfinite_end(hb, n, trans, init, S, cus, s);
+        const hipError_t ne = nonfinite_end(hb, n, trans, init, S, s);
         if (ne != hipSuccess) return ne;
     }
     if (ev) (void)hipEventRecord(ev[2], s);
@@ -1583,7 +1554,7 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
     band::Exchange ex{};
     band::ClearJobs clear{};
     {
-        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, cus, s, false, pl.hl, pl.hr, true, choice.background);     // (and the band's promise)
+        const hipError_t ne = nonfinite_begin(hb, n, trans, init, S, s, false, pl.hl, pl.hr, true, choice.background);     // (and the band's promise)
         if (ne != hipSuccess) return ne;
     }
     size_t most = 0;
@@ -1602,8 +1573,7 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
     const resident::Group &grp = group.grp;
     const int tiles = group.tiles, items = group.items;
     const int nlaunch = choice.whole ? 1 : (tiles + choice.cap - 1) / choice.cap;
-    ex.failed = w.words + 16;
-    unsigned *const tickets = w.words + 16 + kMaxGroupTiles;        // [8] per launch
+    ex.failed = w.failed;
     ex.wait_ticks = cluster_wait_ticks();
     clear.words = w.words;
     clear.nwords = 16 + kMaxGroupTiles + 8 * nlaunch;
@@ -1646,7 +1616,7 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
         for (int l = 0; l < nlaunch; ++l) {
             ex.tile0 = l * choice.cap;
             ex.tiles = std::min(tiles, ex.tile0 + choice.cap);
-            ex.control = tickets + 8 * l;
+            ex.control = w.tickets + 8 * l;
             const int here = ex.tiles - ex.tile0;
             const int grid = pl.R > 1 ? 8 * ((here + 7) / 8) * pl.R : here;
             if (bg)
@@ -1681,7 +1651,7 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
         }
     });
     {
-        const hipError_t ne = nonfinite_end(hb, n, trans, init, S, cus, s);
+        const hipError_t ne = nonfinite_end(hb, n, trans, init, S, s);
         if (ne != hipSuccess) return ne;
     }
     if (ev) (void)hipEventRecord(ev[2], s);
@@ -1733,30 +1703,29 @@ hipError_t run_decode(const HostBatch &hb, const float *trans, const float *init
     if (ev) (void)hipEventRecord(ev[3], s);
     // NaN / +inf inputs (nonfinite.hpp): the small-state kernels look at the values they produce; the routes below get
     // their observations looked at by a launch of its own (they launch a kernel per timestep anyway)
-    e = nonfinite_begin(&hb, 1, trans, init, S, cus, s, route != ROUTE_SMALL, -1, -1, route != ROUTE_SMALL);
+    e = nonfinite_begin(&hb, 1, trans, init, S, s, route != ROUTE_SMALL, -1, -1, route != ROUTE_SMALL);
     if (e != hipSuccess) return e;
     if (route == ROUTE_SMALL) {             // one launch: recurrence, backtrace and the route record
         // (the byte plane lies where the generic path's trellis does and is never larger: small_states.hpp)
         // (and so does the value-only form's fp32 history: the trellis region itself)
         const Workspace w = carve(workspace, B, T, S);
-        int32_t *const record = route_record(workspace, B, T, S, cus);
-        e = small::supported(S) ? launch_small(obs, frames, trans, init, w, out, record, B, T, S, s, launches, cus)
-                                : launch_block(obs, frames, trans, init, w, out, record, B, T, S, s, launches, cus);
+        e = small::supported(S) ? launch_small(obs, frames, trans, init, w, out, hb.record, B, T, S, s, launches, cus)
+                                : launch_block(obs, frames, trans, init, w, out, hb.record, B, T, S, s, launches, cus);
         if (ev) (void)hipEventRecord(ev[1], s);
-        if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, cus, s);
+        if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, s);
         if (ev) (void)hipEventRecord(ev[2], s);
         return e;
     }
-    e = stamp_route(workspace, B, T, S, cus, route, s);
+    e = stamp_route(hb.record, route, s);
     if (e != hipSuccess) return e;
     if (route == ROUTE_DENSE) {
         const DenseWorkspace w = carve_dense(workspace, B, T, S, cus);
         // (the route record's words [2], [3]: shader-clock and wall-clock ticks of the last timestep's workgroup 0)
         e = launch_dense_forward(obs, frames, trans, init, w, B, T, S, s, launches, reuse,
-                                 reinterpret_cast<unsigned *>(route_record(workspace, B, T, S, cus)) + 2);
+                                 reinterpret_cast<unsigned *>(hb.record) + 2);
         if (ev) (void)hipEventRecord(ev[1], s);
         if (e == hipSuccess)
-            e = launch_backtrace_on(w.hist, trans, frames, out, B, T, S, s, w.ranges, w.ranges + 2 * (size_t)S);
+            e = launch_backtrace_on(w.hist, trans, frames, out, B, T, S, s, w.ranges, w.widest);
     } else if (route == ROUTE_ROWS) {
         TORBI_NOTE_KERNEL("rowscan::step_rows_sorted_kernel");
         const RowsWorkspace w = carve_rows(workspace, B, T, S);
@@ -1786,7 +1755,7 @@ hipError_t run_decode(const HostBatch &hb, const float *trans, const float *init
         if (ev) (void)hipEventRecord(ev[1], s);
         if (e == hipSuccess) e = launch_finalize(frames, w, out, B, T, S, s);
     }
-    if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, cus, s);
+    if (e == hipSuccess) e = nonfinite_end(&hb, 1, trans, init, S, s);
     if (ev) (void)hipEventRecord(ev[2], s);
     return e;
 }
@@ -1853,7 +1822,8 @@ int decode_group(const torbi_hip_batch *batches, int count, const DecodeCall &ca
                                   b.workspace_bytes, b.B, b.T, S, device);
         if (rc != TORBI_HIP_OK) return rc;
         if (b.B == 0) continue;
-        hb[n++] = HostBatch{b.observation, b.batch_frames, b.indices_out, b.workspace, b.B, b.T};
+        hb[n++] = HostBatch{b.observation, b.batch_frames, b.indices_out, b.workspace, b.B, b.T,
+                            route_record(b.workspace, b.B, b.T, S, cus)};
         tiles += tiles_of(b.B, S);
     }
     if (n == 0) return TORBI_HIP_OK;
@@ -2246,11 +2216,21 @@ int torbi_hip_fill_synthetic(float *dst, uint64_t count, uint64_t start, int str
 
 // ---- streaming decode (stream.hpp) ----
 
-static size_t stream_ring_bytes(int B, int S, int capacity) { return (size_t)B * capacity * S * sizeof(float); }
+// the state of B streams: posterior rows [B][capacity][S], memo [B][capacity], backpointers [B][S]; 4-byte words, packed
+struct StreamState { float *ring; int32_t *memo, *bp; size_t bytes; };
+static StreamState stream_state(void *state, int B, int S, int capacity) {
+    Scratch a(state);
+    StreamState st;
+    st.ring = a.take<float>((size_t)B * capacity * S, 4);
+    st.memo = a.take<int32_t>((size_t)B * capacity, 4);
+    st.bp = a.take<int32_t>((size_t)B * S, 4);
+    st.bytes = a.bytes;
+    return st;
+}
 
 size_t torbi_hip_stream_state_bytes(int B, int S, int capacity) {
     if (B < 1 || S < 1 || capacity < 1) return 0;
-    return stream_ring_bytes(B, S, capacity) + (size_t)B * capacity * sizeof(int32_t) + (size_t)B * S * sizeof(int32_t);
+    return stream_state(nullptr, B, S, capacity).bytes;
 }
 
 static int stream_args_ok(const void *info, const void *transition, const void *state, size_t state_bytes, int capacity,
@@ -2286,9 +2266,9 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const stream::Info *in = reinterpret_cast<const stream::Info *>(info);
-    float *ring = static_cast<float *>(state);
-    int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
-    int32_t *bp = memo + (size_t)B * capacity;
+    const StreamState ss = stream_state(state, B, S, capacity);
+    float *const ring = ss.ring;
+    int32_t *const memo = ss.memo, *const bp = ss.bp;
     if (Tc > 0) {
         const int G = stream_tile(B, S, device);
         const int room = capacity < out_capacity ? capacity : out_capacity;
@@ -2328,11 +2308,10 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
     if (code != TORBI_HIP_OK) return code;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
-    float *ring = static_cast<float *>(state);
-    int32_t *memo = reinterpret_cast<int32_t *>(static_cast<char *>(state) + stream_ring_bytes(B, S, capacity));
+    const StreamState ss = stream_state(state, B, S, capacity);
     hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
-                       static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ring, memo,
-                       memo + (size_t)B * capacity, capacity, indices_out, out_capacity, counts_out, 0, S);
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ss.ring,
+                       ss.memo, ss.bp, capacity, indices_out, out_capacity, counts_out, 0, S);
     return (int)hipGetLastError();
 }
 
@@ -2340,7 +2319,7 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
 
 size_t torbi_hip_forward_backward_workspace_bytes(int B, int T, int S) {
     if (B < 1 || T < 1 || S < 1 || S > fb::kMaxStates) return 256;
-    return fb::layout(B, T, S).total;
+    return fb::layout(nullptr, B, T, S).total;
 }
 
 static int fb_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *post,
@@ -2402,11 +2381,8 @@ static int fb_dense(const float *observation, const int32_t *batch_frames, const
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const fb::Layout l = fb::layout(B, T, S);
-    char *base = fb_base(workspace);
-    float *E = reinterpret_cast<float *>(base + l.E), *Et = reinterpret_cast<float *>(base + l.Et);
-    float *m = reinterpret_cast<float *>(base + l.m), *cbuf = reinterpret_cast<float *>(base + l.c);
-    float *partial = reinterpret_cast<float *>(base + l.partial), *w = reinterpret_cast<float *>(base + l.w);
+    const fb::Layout l = fb::layout(fb_base(workspace), B, T, S);
+    float *const E = l.E, *const Et = l.Et, *const m = l.m, *const cbuf = l.c, *const partial = l.partial, *const w = l.w;
     const size_t wrow = (size_t)B * fb::padded_states(S);
     const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
     hipError_t e;
@@ -2537,7 +2513,7 @@ int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, 
 
 size_t torbi_hip_forward_backward_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right) {
     if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
-    return fbb::layout(B, T, S, reach_left, reach_right).total;
+    return fbb::layout(nullptr, B, T, S, reach_left, reach_right).total;
 }
 
 int torbi_hip_forward_backward_band(const float *observation, const int32_t *batch_frames, const float *transition,
@@ -2557,11 +2533,9 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const fbb::Layout l = fbb::layout(B, T, S, reach_left, reach_right);
-    char *base = fb_base(workspace);
-    float *Df = reinterpret_cast<float *>(base + l.Df), *Db = reinterpret_cast<float *>(base + l.Db);
-    float *m = reinterpret_cast<float *>(base + l.m), *cbuf = reinterpret_cast<float *>(base + l.c);
-    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
+    const fbb::Layout l = fbb::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    float *const Df = l.Df, *const Db = l.Db, *const m = l.m, *const cbuf = l.c;
+    int32_t *const flag = l.flag;
     const float ebg = background == -INFINITY ? 0.f : expf(background);
     hipError_t e;
     {
@@ -2600,7 +2574,7 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
 
 size_t torbi_hip_k_best_workspace_bytes(int B, int T, int S, int k) {
     if (B < 1 || T < 1 || S < 1 || S > kb::kMaxStates || k < 1 || k > kb::kMaxK) return 256;
-    return kb::layout(B, T, S, k).total;
+    return kb::layout(nullptr, B, T, S, k).total;
 }
 
 static int kb_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *indices,
@@ -2660,12 +2634,10 @@ int torbi_hip_k_best(const float *observation, const int32_t *batch_frames, cons
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const kb::Layout l = kb::layout(B, T, S, k);
-    char *base = fb_base(workspace);
-    float *vals = reinterpret_cast<float *>(base + l.vals), *tt = reinterpret_cast<float *>(base + l.tt);
-    int32_t *ptrs = reinterpret_cast<int32_t *>(base + l.ptrs), *count = reinterpret_cast<int32_t *>(base + l.count);
-    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
-    kb::Final *fin = reinterpret_cast<kb::Final *>(base + l.final_);
+    const kb::Layout l = kb::layout(fb_base(workspace), B, T, S, k);
+    float *const vals = l.vals, *const tt = l.tt;
+    int32_t *const ptrs = l.ptrs, *const count = l.count, *const flag = l.flag;
+    kb::Final *const fin = l.final_;
     const size_t plane = (size_t)B * k * S;
     hipError_t e;
     if ((e = hipMemsetAsync(flag, 0, sizeof(int32_t), st)) != hipSuccess) return (int)e;
@@ -2694,11 +2666,9 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const kb::Layout l = kb::layout(B, T, 1, k);
-    char *base = fb_base(workspace);
-    int32_t *ptrs = reinterpret_cast<int32_t *>(base + l.ptrs), *count = reinterpret_cast<int32_t *>(base + l.count);
-    int32_t *flag = reinterpret_cast<int32_t *>(base + l.flag);
-    kb::Final *fin = reinterpret_cast<kb::Final *>(base + l.final_);
+    const kb::Layout l = kb::layout(fb_base(workspace), B, T, 1, k);
+    int32_t *const ptrs = l.ptrs, *const count = l.count, *const flag = l.flag;
+    kb::Final *const fin = l.final_;
     int KMAX = 1;
     while (KMAX < k) KMAX *= 2;
 #define TORBI_KB_UNIFORM(km)                                                                                              \

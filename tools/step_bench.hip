@@ -63,10 +63,10 @@ void run(int B, int T, int S, int reps) {
         for (int t = 1; t <= n; ++t) {
             hipLaunchKernelGGL((dense::step_dense_kernel<BL, JL, NW, KC, MSL>), dim3(grid), dim3(64 * NW), lds, s0, obs, frames, tr,
                                (t & 1) ? p0 : p1, (t & 1) ? p1 : p0, hist, chunks, B, T, S, 1 + (t % (T - 1)), pl.n_bt,
-                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB);
+                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB, nullptr);
             hipLaunchKernelGGL((dense::step_dense_kernel<BL, JL, NW, KC, MSL>), dim3(grid), dim3(64 * NW), lds, s1, obs, frames, tr,
                                (t & 1) ? q0 : q1, (t & 1) ? q1 : q0, hist, chunks, B, T, S, 1 + (t % (T - 1)), pl.n_bt,
-                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB);
+                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB, nullptr);
         }
     };
     if (two) {
@@ -87,7 +87,7 @@ void run(int B, int T, int S, int reps) {
         for (int t = 1; t <= n; ++t)
             hipLaunchKernelGGL((dense::step_dense_kernel<BL, JL, NW, KC, MSL>), dim3(grid), dim3(64 * NW), lds, 0, obs, frames, tr,
                                (t & 1) ? p0 : p1, (t & 1) ? p1 : p0, hist, chunks, B, T, S, 1 + (t % (T - 1)), pl.n_bt,
-                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB);
+                               pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB, nullptr);
     };
     go(20); CHECK(hipDeviceSynchronize());
     float best = 1e30f;

@@ -323,7 +323,7 @@ inline bool block_supported(int S) { return S > kMaxS && S <= kBlockMaxS; }
 // independent).
 // NSEQ = 2: a workgroup decodes TWO sequences against the one copy of the matrix in its registers -- the two barriers and
 // the merge of a timestep, which nothing overlaps when a 16-wave workgroup has a compute unit to itself, are shared by two
-// independent recurrences; taken when the compute units are full without it (torbi_hip.hip, launch_block_value_as).
+// independent recurrences; taken when the compute units are full without it (torbi_hip.hip, launch_block).
 template <int PQ, int L, int NSEQ>
 __global__ __launch_bounds__(64 * PQ * PQ) void block_value_kernel(
     const float *__restrict__ obs, const int32_t *__restrict__ frames, const float *__restrict__ trans,

@@ -28,6 +28,7 @@
 
 #include "torbi_hip.h"
 #include "scratch.hpp"
+#include "dispatch.hpp"
 #include "dense_forward.hpp"
 #include "lazy_backtrace.hpp"
 #include "uniform_decode.hpp"
@@ -440,6 +441,11 @@ inline hipError_t ensure_dynamic_lds(const void *fn, size_t bytes) {
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) g_lds_grants.push_back(LdsGrant{fn, device, bytes});
     return e;
+}
+// (for the very pointer a launch site launches: dispatch.hpp)
+template <class... A>
+inline hipError_t ensure_dynamic_lds(void (*kernel)(A...), size_t bytes) {
+    return ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), bytes);
 }
 
 // Decodes of this library that may still be running on a device, by stream: the end of every decode is marked with an
@@ -894,38 +900,35 @@ hipError_t launch_forward(const float *obs, const int32_t *frames, const float *
     return hipGetLastError();
 }
 
-// The held-matrix kernel's instantiation for S states: kernel, grid, block.
-struct HeldLaunch { const void *fn; int grid, block; };
-inline HeldLaunch held_launch(int S) {
+// THE held-matrix instance for S states (all six share one signature): what the occupancy query asks about and what the
+// launch launches -- a kernel whose workgroups wait for each other must be the one whose residency was checked.
+using HeldKernel = decltype(&held::held_forward_kernel<1, 8, 512, true>);
+struct HeldLaunch { HeldKernel kernel; int grid, block; };
+inline HeldLaunch held_instance(int S) {
     const int K = (S + held::threads(S) - 1) / held::threads(S);
-    const void *fn;
-    if (S <= held::kSmallS)
-        fn = K == 1 ? (const void *)&held::held_forward_kernel<1, 8, 512, true>
-           : K == 2 ? (const void *)&held::held_forward_kernel<2, 8, 512, true>
-           : K == 3 ? (const void *)&held::held_forward_kernel<3, 8, 512, true>
-                    : (const void *)&held::held_forward_kernel<4, 8, 512, true>;
-    else
-        fn = K == 3 ? (const void *)&held::held_forward_kernel<3, 16, 1024, false>
-                    : (const void *)&held::held_forward_kernel<4, 16, 1024, false>;
-    return HeldLaunch{fn, held::workgroups(S), held::block_threads(S)};
+    const HeldKernel kernel =
+        S <= held::kSmallS
+            ? by_value<1, 2, 3, 4>(K, [](auto k) -> HeldKernel { return &held::held_forward_kernel<decltype(k)::value, 8, 512, true>; })
+            : by_value<3, 4>(K, [](auto k) -> HeldKernel { return &held::held_forward_kernel<decltype(k)::value, 16, 1024, false>; });
+    return HeldLaunch{kernel, held::workgroups(S), held::block_threads(S)};
 }
 // Can every workgroup of that launch be resident at once on `device`?  The runtime's occupancy answer for the very
 // kernel (registers, LDS, waves), queried once per (kernel, device) -- held::supported()'s "two workgroups per compute
 // unit up to 2048 states" is an assumption about this build on an MI355X, this is the check.
 inline bool held_resident(int S, int device, int cus) {
-    struct Known { const void *fn; int device; int per_cu; };
+    struct Known { HeldKernel kernel; int device; int per_cu; };
     static std::mutex mu;
     static std::vector<Known> known;
-    const HeldLaunch h = held_launch(S);
+    const HeldLaunch h = held_instance(S);
     std::lock_guard<std::mutex> hold(mu);
     for (auto &k : known)
-        if (k.fn == h.fn && k.device == device) return h.grid <= k.per_cu * cus;
+        if (k.kernel == h.kernel && k.device == device) return h.grid <= k.per_cu * cus;
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h.fn, h.block, 0) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(h.kernel), h.block, 0) != hipSuccess) {
         (void)hipGetLastError();
         per_cu = 0;
     }
-    known.push_back(Known{h.fn, device, per_cu});
+    known.push_back(Known{h.kernel, device, per_cu});
     return h.grid <= per_cu * cus;
 }
 
@@ -945,22 +948,9 @@ hipError_t launch_held_forward(const float *obs, const int32_t *frames, const fl
     // overrides (polls of ~1 us; 0 forces the repair path in the tests).
     unsigned long long wait_ticks = std::max<unsigned long long>(200000ull, 5000ull * (unsigned long long)T);
     if (const char *polls = getenv("TORBI_HIP_HELD_SPIN_LIMIT")) wait_ticks = 100ull * strtoull(polls, nullptr, 10);
-    const dim3 grid(held::workgroups(S)), block(held::block_threads(S));
-    const int K = (S + held::threads(S) - 1) / held::threads(S);
-#define TORBI_HELD(K_, R_, N_)                                                                                       \
-    hipLaunchKernelGGL((held::held_forward_kernel<K_, R_, N_, (N_ < 1024)>), grid, block, 0, stream, obs, frames, trans, \
-                       w.post[0], w.post[1], w.trellis, w.xchg, w.control, B, T, S, wait_ticks)
-    if (S <= held::kSmallS) {
-        if (K == 1) TORBI_HELD(1, 8, 512);
-        else if (K == 2) TORBI_HELD(2, 8, 512);
-        else if (K == 3) TORBI_HELD(3, 8, 512);
-        else TORBI_HELD(4, 8, 512);
-    } else if (K == 3) {
-        TORBI_HELD(3, 16, 1024);
-    } else {
-        TORBI_HELD(4, 16, 1024);
-    }
-#undef TORBI_HELD
+    const HeldLaunch h = held_instance(S);
+    hipLaunchKernelGGL(h.kernel, dim3(h.grid), dim3(h.block), 0, stream, obs, frames, trans, w.post[0], w.post[1], w.trellis, w.xchg,
+                       w.control, B, T, S, wait_ticks);
     // does nothing unless a workgroup above gave up waiting (held_matrix_forward.hpp)
     hipLaunchKernelGGL(held::repair_kernel, dim3(B), dim3(1024), 2 * sizeof(float) * (size_t)S, stream, obs, frames, trans, init,
                        w.post[0], w.post[1], w.trellis, w.control, B, T, S);
@@ -994,87 +984,53 @@ inline bool small_value_form(int B, int S, int cus) {
     if (const char *e = getenv("TORBI_HIP_SMALL_VALUE")) return atoi(e) != 0;
     return small::padded_states(S) >= 32 && (long long)B >= 2ll * cus;
 }
-template <int SP, int CH>
-hipError_t launch_small_as(const float *obs, const int32_t *frames, const float *trans, const float *init, const Workspace &w,
-                           int32_t *out, int32_t *record, int B, int T, int S, hipStream_t stream, bool value_form) {
-    if (value_form) {
-        TORBI_NOTE_KERNEL("small::decode_value_kernel<%d, %d>", SP, CH);
-        hipLaunchKernelGGL((small::decode_value_kernel<SP, CH>), dim3((B + 3) / 4), dim3(256), 0, stream, obs, frames, trans, init,
-                           out, reinterpret_cast<float *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S, t_serial);
-        return hipGetLastError();
-    }
-    TORBI_NOTE_KERNEL("small::decode_kernel<%d, %d>", SP, CH);
-    hipLaunchKernelGGL((small::decode_kernel<SP, CH>), dim3(B), dim3(64), 0, stream, obs, frames, trans, init, out,
-                       reinterpret_cast<uint32_t *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S, t_serial);
-    return hipGetLastError();
-}
 hipError_t launch_small(const float *obs, const int32_t *frames, const float *trans, const float *init, const Workspace &w,
                         int32_t *out, int32_t *record, int B, int T, int S, hipStream_t stream, int *launches, int cus = 256) {
     if (launches) *launches += 1;
-    const bool v = small_value_form(B, S, cus);
-    switch (small::padded_states(S)) {
-        case 4: return launch_small_as<4, 16>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 8: return launch_small_as<8, 16>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 16: return launch_small_as<16, 16>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 24: return launch_small_as<24, 8>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 32: return launch_small_as<32, 8>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 40: return launch_small_as<40, 8>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 48: return launch_small_as<48, 4>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        case 56: return launch_small_as<56, 4>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-        default: return launch_small_as<64, 4>(obs, frames, trans, init, w, out, record, B, T, S, stream, v);
-    }
+    const bool value_form = small_value_form(B, S, cus);
+    return by_value<4, 8, 16, 24, 32, 40, 48, 56, 64>(small::padded_states(S), [&](auto sp) {
+        constexpr int SP = decltype(sp)::value, CH = SP <= 16 ? 16 : SP <= 40 ? 8 : 4;
+        if (value_form) {
+            auto *kernel = &small::decode_value_kernel<SP, CH>;
+            TORBI_NOTE_KERNEL("small::decode_value_kernel<%d, %d>", SP, CH);
+            hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, stream, obs, frames, trans, init, out,
+                               reinterpret_cast<float *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S, t_serial);
+        } else {
+            auto *kernel = &small::decode_kernel<SP, CH>;
+            TORBI_NOTE_KERNEL("small::decode_kernel<%d, %d>", SP, CH);
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, stream, obs, frames, trans, init, out,
+                               reinterpret_cast<uint32_t *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S, t_serial);
+        }
+        return hipGetLastError();
+    });
 }
-
-// THE ladder from a state count to a backtrace instance: a lane of those kernels holds NQ float4 of a posterior row, which
-// covers S <= 256 * NQ states.  Calls f(std::integral_constant<int, NQ>) for the first NQ of the list that covers S (the
-// last one when none does: the callers have bounded S); without a list 2, 6, 8, 16 -- steps at 512, 1536 and 2048 states.
-template <int NQ, int... MORE, class F>
-inline void by_state_count(int S, F &&f) {
-    if constexpr (sizeof...(MORE) == 0) f(std::integral_constant<int, NQ>());
-    else if (S <= 256 * NQ) f(std::integral_constant<int, NQ>());
-    else by_state_count<MORE...>(S, f);
-}
-// (overload resolution keeps the two apart: an int as first template argument does not fit `class F`, so a call with a list
-// sees the form above alone, and a call without one cannot deduce NQ and sees the form below alone)
-template <class F>
-inline void by_state_count(int S, F &&f) { by_state_count<2, 6, 8, 16>(S, f); }
 
 // 65 .. 256 states: the value-only workgroup kernel + backtrace launches of their own (small_states.hpp, block_value_kernel)
 inline int backtrace_segments(int items);
 hipError_t launch_backtrace_on(const float *hist, const float *trans, const int32_t *frames, int32_t *out,
                                int B, int T, int S, hipStream_t stream, const int32_t *ranges, const int32_t *widest);
-template <int PQ, int L>
-hipError_t launch_block_value_as(const float *obs, const int32_t *frames, const float *trans, const float *init,
-                                 const Workspace &w, int32_t *record, int B, int T, int S, hipStream_t stream, int cus) {
-    const int NB = (S + 63) / 64;
-    // two sequences per workgroup once the compute units are full without it: a 9- or 16-wave workgroup has a unit to
-    // itself (512 x 500 x 256: 1.07 -> 1.03 ms, 2048 x 200 x 192: 1.33 -> 1.19), several 4-wave workgroups share one and
-    // overlap anyway (512 x 500 x 128: 0.44 -> 0.64, but 4096 x 200 x 128: 0.95 -> 0.89).  TORBI_HIP_BLOCK_PAIRS=0 / 1 overrides
-    const char *env = getenv("TORBI_HIP_BLOCK_PAIRS");
-    const bool pairs = env ? atoi(env) != 0 : B > cus * (NB * PQ >= 9 ? 1 : 8);
-    TORBI_NOTE_KERNEL("small::block_value_kernel<%d, %d, %d>", PQ, L, pairs ? 2 : 1);
-    if (pairs)
-        hipLaunchKernelGGL((small::block_value_kernel<PQ, L, 2>), dim3((B + 1) / 2), dim3(64 * NB * PQ), 0, stream, obs, frames,
-                           trans, init, reinterpret_cast<float *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B,
-                           T, S, NB, t_serial);
-    else
-        hipLaunchKernelGGL((small::block_value_kernel<PQ, L, 1>), dim3(B), dim3(64 * NB * PQ), 0, stream, obs, frames, trans,
-                           init, reinterpret_cast<float *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S,
-                           NB, t_serial);
-    return hipGetLastError();
-}
 hipError_t launch_block(const float *obs, const int32_t *frames, const float *trans, const float *init, const Workspace &w,
                         int32_t *out, int32_t *record, int B, int T, int S, hipStream_t stream, int *launches, int cus) {
     const bool narrow = small::block_row_registers(S) == 48;
     if (launches) *launches += 2;
-    hipError_t e;
-    switch (small::block_splits(S)) {
-        case 2: e = narrow ? launch_block_value_as<2, 48>(obs, frames, trans, init, w, record, B, T, S, stream, cus)
-                           : launch_block_value_as<2, 64>(obs, frames, trans, init, w, record, B, T, S, stream, cus); break;
-        case 3: e = narrow ? launch_block_value_as<3, 48>(obs, frames, trans, init, w, record, B, T, S, stream, cus)
-                           : launch_block_value_as<3, 64>(obs, frames, trans, init, w, record, B, T, S, stream, cus); break;
-        default: e = launch_block_value_as<4, 64>(obs, frames, trans, init, w, record, B, T, S, stream, cus);
-    }
+    const int NB = (S + 63) / 64;
+    // (PQ, L): 2 or 3 splits with 48 or 64 row registers, 4 splits with 64
+    const hipError_t e = by_value<2, 3, 4>(small::block_splits(S), [&](auto pq) { return by_flag(narrow, [&](auto narrow_) {
+        constexpr int PQ = decltype(pq)::value, L = decltype(narrow_)::value && PQ < 4 ? 48 : 64;
+        // two sequences per workgroup once the compute units are full without it: a 9- or 16-wave workgroup has a unit to
+        // itself (512 x 500 x 256: 1.07 -> 1.03 ms, 2048 x 200 x 192: 1.33 -> 1.19), several 4-wave workgroups share one and
+        // overlap anyway (512 x 500 x 128: 0.44 -> 0.64, but 4096 x 200 x 128: 0.95 -> 0.89).  TORBI_HIP_BLOCK_PAIRS=0 / 1 overrides
+        const char *env = getenv("TORBI_HIP_BLOCK_PAIRS");
+        return by_flag(env ? atoi(env) != 0 : B > cus * (NB * PQ >= 9 ? 1 : 8), [&](auto pairs) {
+            constexpr int NSEQ = decltype(pairs)::value ? 2 : 1;
+            auto *kernel = &small::block_value_kernel<PQ, L, NSEQ>;
+            TORBI_NOTE_KERNEL("small::block_value_kernel<%d, %d, %d>", PQ, L, NSEQ);
+            hipLaunchKernelGGL(kernel, dim3((B + NSEQ - 1) / NSEQ), dim3(64 * NB * PQ), 0, stream, obs, frames, trans, init,
+                               reinterpret_cast<float *>(w.trellis), w.post[0], w.post[1], record, (int)ROUTE_SMALL, B, T, S, NB,
+                               t_serial);
+            return hipGetLastError();
+        });
+    }); });
     if (e != hipSuccess) return e;
     const float *hist = reinterpret_cast<const float *>(w.trellis);
     const bool vec = (S % 4 == 0) && ((reinterpret_cast<uintptr_t>(trans) & 15) == 0);
@@ -1094,16 +1050,16 @@ hipError_t launch_dense_steps(const float *obs, const int32_t *frames, const Den
                               int B, int T, int S, hipStream_t stream, int *launches, unsigned *clock_out) {
     const dense::Plan &pl = w.plan;
     const size_t lds = dense::lds_bytes<BL, JL, NW, KC, MSL>();
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&dense::step_dense_kernel<BL, JL, NW, KC, MSL>), lds);
+    auto *kernel = &dense::step_dense_kernel<BL, JL, NW, KC, MSL>;
+    hipError_t e = ensure_dynamic_lds(kernel, lds);
     if (e != hipSuccess) return e;
     TORBI_NOTE_KERNEL("dense::step_dense_kernel<%d, %d, %d, %d, %d>", BL, JL, NW, KC, MSL);
     const int ntiles = pl.n_bt * pl.n_jt;
     const int grid = 8 * ((ntiles + 7) / 8);
     int n = 0;
     for (int t = 1; t < T; ++t) {
-        hipLaunchKernelGGL((dense::step_dense_kernel<BL, JL, NW, KC, MSL>), dim3(grid), dim3(64 * NW), lds, stream, obs,
-                           frames, w.trp, w.panel[(t - 1) & 1], w.panel[t & 1], w.hist, w.chunks, B, T, S,
-                           t, pl.n_bt, pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB, clock_out);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * NW), lds, stream, obs, frames, w.trp, w.panel[(t - 1) & 1],
+                           w.panel[t & 1], w.hist, w.chunks, B, T, S, t, pl.n_bt, pl.n_jt, pl.JT, pl.Kp, pl.NCH, pl.RB, clock_out);
         ++n;
     }
     if (launches) *launches = n;
@@ -1132,14 +1088,12 @@ hipError_t launch_dense_forward(const float *obs, const int32_t *frames, const f
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-#define TORBI_DENSE_CASE(BL_, JL_, NW_, KC_, MSL_)                                             \
-    if (pl.BL == BL_ && pl.JL == JL_ && pl.NW == NW_ && pl.KC == KC_ && pl.MSL == MSL_)         \
-        return launch_dense_steps<BL_, JL_, NW_, KC_, MSL_>(obs, frames, w, B, T, S, stream, launches, clock_out)
-    TORBI_DENSE_CASE(8, 6, 8, 12, 8);
-    TORBI_DENSE_CASE(8, 4, 8, 12, 8);
-    TORBI_DENSE_CASE(8, 2, 8, 12, 8);
-#undef TORBI_DENSE_CASE
-    return hipErrorInvalidValue;
+    return by_value<6, 4, 2>(pl.JL, [&](auto jl) {
+        constexpr int BL = 8, JL = decltype(jl)::value, NW = 8, KC = 12, MSL = 8;
+        // (a plan no instance matches)
+        if (pl.BL != BL || pl.JL != JL || pl.NW != NW || pl.KC != KC || pl.MSL != MSL) return hipErrorInvalidValue;
+        return launch_dense_steps<BL, JL, NW, KC, MSL>(obs, frames, w, B, T, S, stream, launches, clock_out);
+    });
 }
 
 // per-transition preparation shared by the pruned and the time-resident paths: descending rows with their
@@ -1220,60 +1174,38 @@ inline bool few_seeds(unsigned flags, bool clusters) {
     return clusters;
 }
 
-template <int KW, int MAXP, int KR, bool CLUSTER, int NI>
-hipError_t launch_resident_variant(const resident::Group &grp, const resident::Cluster &clu, int workgroups,
-                                   const ResidentWorkspace &w, const float *init, int S, hipStream_t stream) {
-    const size_t lds = resident::lds_bytes(S, KR + 1);
-    const void *fn = reinterpret_cast<const void *>(&resident::resident_forward_kernel<KW, MAXP, true, KR, CLUSTER, NI>);
-    hipError_t e = ensure_dynamic_lds(fn, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((resident::resident_forward_kernel<KW, MAXP, true, KR, CLUSTER, NI>), dim3(workgroups), dim3(64 * KW), lds,
-                       stream, grp, clu, w.tt, w.sorted, init, S, w.SpP);
-    TORBI_NOTE_KERNEL("resident::resident_forward_kernel<%d, %d, true, %d, %s, %d, false>", KW, MAXP, KR, CLUSTER ? "true" : "false", NI);
-    return hipGetLastError();
-}
-
-template <int KW, int MAXP, bool CLUSTER, int NI = 16>
+// THE time-resident instance: one pointer for the LDS grant and the launch, one set of constants for the reported name.
+// KR: seeds per item (3, or 1: `few`); NI: items per tile (16, 8 above 2048 states) -- both chosen once, in run_resident, for
+// the forward launch and the repair launch behind a cluster launch (REPAIR: whole tiles, only where Group::only is set)
+template <int KW, int MAXP, int KR, bool CLUSTER, int NI, bool REPAIR = false>
 hipError_t launch_resident_kernel(const resident::Group &grp, const resident::Cluster &clu, int workgroups,
-                                  const ResidentWorkspace &w, const float *init, int S, hipStream_t stream, bool few) {
-    return !few ? launch_resident_variant<KW, MAXP, 3, CLUSTER, NI>(grp, clu, workgroups, w, init, S, stream)
-                                    : launch_resident_variant<KW, MAXP, 1, CLUSTER, NI>(grp, clu, workgroups, w, init, S, stream);
-}
-
-// the repair launch behind a cluster launch: whole tiles, only where Group::only is set; ONE instance per seed count and
-// tile size (eleven passes cover every supported state count)
-template <int KR, int NI>
-hipError_t launch_repair_variant(const resident::Group &grp, const resident::Cluster &clu, int tiles, const ResidentWorkspace &w,
-                                 const float *init, int S, hipStream_t stream) {
+                                  const ResidentWorkspace &w, const float *init, int S, hipStream_t stream) {
     const size_t lds = resident::lds_bytes(S, KR + 1);
-    const void *fn = reinterpret_cast<const void *>(&resident::resident_forward_kernel<12, 11, true, KR, false, NI, true>);
-    hipError_t e = ensure_dynamic_lds(fn, lds);
+    auto *kernel = &resident::resident_forward_kernel<KW, MAXP, true, KR, CLUSTER, NI, REPAIR>;
+    const hipError_t e = ensure_dynamic_lds(kernel, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((resident::resident_forward_kernel<12, 11, true, KR, false, NI, true>), dim3(tiles), dim3(64 * 12), lds,
-                       stream, grp, clu, w.tt, w.sorted, init, S, w.SpP);
+    hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(64 * KW), lds, stream, grp, clu, w.tt, w.sorted, init, S, w.SpP);
+    if (!REPAIR)
+        TORBI_NOTE_KERNEL("resident::resident_forward_kernel<%d, %d, true, %d, %s, %d, false>", KW, MAXP, KR,
+                          CLUSTER ? "true" : "false", NI);
     return hipGetLastError();
-}
-inline hipError_t launch_repair(const resident::Group &grp, const resident::Cluster &clu, int tiles, const ResidentWorkspace &w,
-                                const float *init, int S, hipStream_t s, bool few) {
-    const bool small = resident::tile_items(S) != resident::kNI;
-    if (!few)
-        return small ? launch_repair_variant<3, 8>(grp, clu, tiles, w, init, S, s) : launch_repair_variant<3, 16>(grp, clu, tiles, w, init, S, s);
-    return small ? launch_repair_variant<1, 8>(grp, clu, tiles, w, init, S, s) : launch_repair_variant<1, 16>(grp, clu, tiles, w, init, S, s);
 }
 
 // every workgroup owns a whole tile (resident_forward_kernel without clusters)
-inline hipError_t launch_whole_tiles(const resident::Group &grp, const resident::Cluster &clu, int tiles,
-                                     const ResidentWorkspace &w, const float *init, int S, hipStream_t s, bool few) {
+template <int KR, int NI>
+hipError_t launch_whole_tiles(const resident::Group &grp, const resident::Cluster &clu, int tiles, const ResidentWorkspace &w,
+                              const float *init, int S, hipStream_t s) {
     const int nrg = (S + resident::pass_rows(S) - 1) / resident::pass_rows(S);
-    if (resident::tile_items(S) != resident::kNI) {       // 8-item tiles (2048 < S <= 4096)
+    if constexpr (NI != resident::kNI) {       // 8-item tiles (2048 < S <= 4096)
         // (eight waves x 16 passes with 256 registers each measured slower than twelve x 8-11 at 168: 197 against 183 us per
         // timestep at 4096 states with a third of the units busy, equal on a full chip)
-        if (nrg <= 96) return launch_resident_kernel<12, 8, false, 8>(grp, clu, tiles, w, init, S, s, few);
-        return launch_resident_kernel<12, 11, false, 8>(grp, clu, tiles, w, init, S, s, few);
+        if (nrg <= 96) return launch_resident_kernel<12, 8, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+        return launch_resident_kernel<12, 11, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+    } else {
+        if (nrg <= 72) return launch_resident_kernel<12, 6, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+        if (nrg <= 96) return launch_resident_kernel<12, 8, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+        return launch_resident_kernel<12, 11, KR, false, NI>(grp, clu, tiles, w, init, S, s);
     }
-    if (nrg <= 72) return launch_resident_kernel<12, 6, false>(grp, clu, tiles, w, init, S, s, few);
-    if (nrg <= 96) return launch_resident_kernel<12, 8, false>(grp, clu, tiles, w, init, S, s, few);
-    return launch_resident_kernel<12, 11, false>(grp, clu, tiles, w, init, S, s, few);
 }
 
 // segments per path of the backtrace behind a time-resident forward launch: 8 while the launch holds few paths (a wave per
@@ -1436,7 +1368,9 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
     if (ev) (void)hipEventRecord(ev[3], s);
     const int nrg = (S + resident::pass_rows(S) - 1) / resident::pass_rows(S);
     const bool small = resident::tile_items(S) != resident::kNI;       // 8-item tiles (2048 < S <= 4096)
-    if (R > 1) {
+    e = by_flag(few, [&](auto few_) { return by_flag(small, [&](auto small_) {
+        constexpr int KR = decltype(few_)::value ? 1 : 3, NI = decltype(small_)::value ? 8 : resident::kNI;
+        if (R <= 1) return launch_whole_tiles<KR, NI>(grp, clu, tiles, w, init, S, s);
         {       // the slots this launch uses start out absent (resident_forward.hpp, cluster_slot_bytes)
             const size_t granules = (size_t)tiles * resident::kSlots * resident::cluster_slot_bytes(S) / 16;
             hipLaunchKernelGGL(resident::absent_kernel, dim3((unsigned)std::min<size_t>((granules + 255) / 256, 2048)), dim3(256),
@@ -1446,30 +1380,29 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
         // (eight dispatch classes of R x ceil(tiles / 8) workgroups each: resident_forward.hpp, struct Cluster)
         const int grid = 8 * ((tiles + 7) / 8) * R;
         const int share = (nrg + R - 1) / R;                    // row groups of the largest share
-        if (small && share <= 16) {
+        hipError_t ce;
+        if constexpr (NI == 8) {
             // 8-item tiles, at most 16 row groups a member: EIGHT waves (256 registers each: the twelve-wave instances of
             // the 8-item tile spill 20-80 registers at 168, and every scratch reload waits for the write-through stores
             // ahead of it); 128 x 4096 (16 tiles x 16 members, 8 row groups each) kept four of twelve waves idle anyway
-            if (share <= 8) e = launch_resident_kernel<8, 1, true, 8>(grp, clu, grid, w, init, S, s, few);
-            else e = launch_resident_kernel<8, 2, true, 8>(grp, clu, grid, w, init, S, s, few);
-        } else if (small) {         // (more than 16 row groups a member: at least two passes of twelve waves)
-            if (passes <= 2) e = launch_resident_kernel<12, 2, true, 8>(grp, clu, grid, w, init, S, s, few);
-            else if (passes <= 4) e = launch_resident_kernel<12, 4, true, 8>(grp, clu, grid, w, init, S, s, few);
-            else e = launch_resident_kernel<12, 6, true, 8>(grp, clu, grid, w, init, S, s, few);
-        } else if (passes <= 1) e = launch_resident_kernel<12, 1, true>(grp, clu, grid, w, init, S, s, few);
-        else if (passes <= 2) e = launch_resident_kernel<12, 2, true>(grp, clu, grid, w, init, S, s, few);
-        else if (passes <= 4) e = launch_resident_kernel<12, 4, true>(grp, clu, grid, w, init, S, s, few);
-        else e = launch_resident_kernel<12, 6, true>(grp, clu, grid, w, init, S, s, few);
+            if (share <= 8) ce = launch_resident_kernel<8, 1, KR, true, NI>(grp, clu, grid, w, init, S, s);
+            else if (share <= 16) ce = launch_resident_kernel<8, 2, KR, true, NI>(grp, clu, grid, w, init, S, s);
+            // (more than 16 row groups a member: at least two passes of twelve waves)
+            else if (passes <= 2) ce = launch_resident_kernel<12, 2, KR, true, NI>(grp, clu, grid, w, init, S, s);
+            else if (passes <= 4) ce = launch_resident_kernel<12, 4, KR, true, NI>(grp, clu, grid, w, init, S, s);
+            else ce = launch_resident_kernel<12, 6, KR, true, NI>(grp, clu, grid, w, init, S, s);
+        } else if (passes <= 1) ce = launch_resident_kernel<12, 1, KR, true, NI>(grp, clu, grid, w, init, S, s);
+        else if (passes <= 2) ce = launch_resident_kernel<12, 2, KR, true, NI>(grp, clu, grid, w, init, S, s);
+        else if (passes <= 4) ce = launch_resident_kernel<12, 4, KR, true, NI>(grp, clu, grid, w, init, S, s);
+        else ce = launch_resident_kernel<12, 6, KR, true, NI>(grp, clu, grid, w, init, S, s);
+        if (ce != hipSuccess) return ce;
         // a cluster that could not complete in time (resident_forward.hpp: CLUSTER_WAIT_TICKS) has flagged its tile: the
-        // launch behind decodes those tiles again, whole -- it returns at once wherever nothing was flagged (every run so far)
-        if (e == hipSuccess) {
-            resident::Group again = grp;
-            again.only = clu.failed;
-            e = launch_repair(again, clu, tiles, w, init, S, s, few);
-        }
-    } else {
-        e = launch_whole_tiles(grp, clu, tiles, w, init, S, s, few);
-    }
+        // launch behind decodes those tiles again, whole -- it returns at once wherever nothing was flagged (every run so far);
+        // ONE instance per seed count and tile size (eleven passes cover every supported state count)
+        resident::Group again = grp;
+        again.only = clu.failed;
+        return launch_resident_kernel<12, 11, KR, false, NI, true>(again, clu, tiles, w, init, S, s);
+    }); });
     if (launches) *launches = 1;
     if (ev) (void)hipEventRecord(ev[1], s);
     if (e != hipSuccess) return e;
@@ -1584,51 +1517,49 @@ hipError_t run_band(const HostBatch *hb, int n, const float *trans, const float 
         hipLaunchKernelGGL(band::pack_band_kernel, dim3(tp.nblk * tp.Dq4), dim3(64), 0, s, trans, w.tpack, S, tp.hl, tp.hr, tp.Dq,
                            tp.Dq4);
         if (ev) (void)hipEventRecord(ev[3], s);
-#define TORBI_BAND_TILE_AS(BPW_, NW_, BG_)                                                                                         \
-        {                                                                                                                         \
-            e = ensure_dynamic_lds(reinterpret_cast<const void *>(&band::band_tile_kernel<BPW_, NW_, BG_>), (size_t)tp.lds_bytes); \
-            if (e != hipSuccess) return e;                                                                                        \
-            TORBI_NOTE_KERNEL("band::band_tile_kernel<" #BPW_ ", " #NW_ ", " #BG_ ">");                                           \
-            hipLaunchKernelGGL((band::band_tile_kernel<BPW_, NW_, BG_>), dim3(tiles), dim3(64 * tp.waves), (size_t)tp.lds_bytes, s, \
-                               grp, tp, w.tpack, init);                                                                          \
-        }
-#define TORBI_BAND_TILE(BPW_, NW_)                                                                                                \
-        if (tp.background != -INFINITY) TORBI_BAND_TILE_AS(BPW_, NW_, true) else TORBI_BAND_TILE_AS(BPW_, NW_, false)
-        if (tp.bpw == 1) TORBI_BAND_TILE(1, 12)
-        else if (tp.waves == 12) TORBI_BAND_TILE(2, 12)
-        else if (tp.bpw == 2) TORBI_BAND_TILE(2, 8)
-        else TORBI_BAND_TILE(3, 8)
-#undef TORBI_BAND_TILE_AS
-#undef TORBI_BAND_TILE
+        // (bpw, waves of the instance): (1, 12), (2, 12), (2, 8), (3, 8) -- a workgroup of twelve waves holds at most two blocks a
+        // wave (make_tile_plan), and one block a wave runs the twelve-wave instance whatever the workgroup's size
+        e = by_value<1, 2, 3>(tp.bpw, [&](auto bpw) { return by_flag(tp.waves == 12, [&](auto twelve) {
+            return by_flag(tp.background != -INFINITY, [&](auto bg) {
+                constexpr int BPW = decltype(bpw)::value, NW = BPW == 1 || (BPW == 2 && decltype(twelve)::value) ? 12 : 8;
+                constexpr bool BG = decltype(bg)::value;
+                auto *kernel = &band::band_tile_kernel<BPW, NW, BG>;
+                const hipError_t le = ensure_dynamic_lds(kernel, (size_t)tp.lds_bytes);
+                if (le != hipSuccess) return le;
+                TORBI_NOTE_KERNEL("band::band_tile_kernel<%d, %d, %s>", BPW, NW, BG ? "true" : "false");
+                hipLaunchKernelGGL(kernel, dim3(tiles), dim3(64 * tp.waves), (size_t)tp.lds_bytes, s, grp, tp, w.tpack, init);
+                return hipSuccess;
+            });
+        }); });
+        if (e != hipSuccess) return e;
     } else {
         {
             const size_t blocks = std::max<size_t>(1, std::min<size_t>(2048, (most / 16 + 255) / 256));
             hipLaunchKernelGGL(band::clear_exchange_kernel, dim3((unsigned)blocks, n), dim3(256), 0, s, clear);
         }
         if (ev) (void)hipEventRecord(ev[3], s);
-        const bool bg = choice.background != -INFINITY;
-        e = bg ? ensure_dynamic_lds(reinterpret_cast<const void *>(&band::band_forward_kernel<true>), (size_t)pl.lds_bytes)
-               : ensure_dynamic_lds(reinterpret_cast<const void *>(&band::band_forward_kernel<false>), (size_t)pl.lds_bytes);
+        e = by_flag(choice.background != -INFINITY, [&](auto bg) {
+            constexpr bool BG = decltype(bg)::value;
+            auto *kernel = &band::band_forward_kernel<BG>;
+            const hipError_t le = ensure_dynamic_lds(kernel, (size_t)pl.lds_bytes);
+            if (le != hipSuccess) return le;
+            TORBI_NOTE_KERNEL("band::band_forward_kernel<%s>", BG ? "true" : "false");
+            // (R > 1: eight dispatch classes of R x ceil(tiles / 8) workgroups each -- band_forward.hpp, membership; a launch
+            // never holds more members than one XCD has units for its class: choose_band)
+            for (int l = 0; l < nlaunch; ++l) {
+                ex.tile0 = l * choice.cap;
+                ex.tiles = std::min(tiles, ex.tile0 + choice.cap);
+                ex.control = w.tickets + 8 * l;
+                const int here = ex.tiles - ex.tile0;
+                const int grid = pl.R > 1 ? 8 * ((here + 7) / 8) * pl.R : here;
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pl.waves), (size_t)pl.lds_bytes, s, grp, ex, pl, trans, init);
+            }
+            return hipSuccess;
+        });
         if (e != hipSuccess) return e;
-        TORBI_NOTE_KERNEL(bg ? "band::band_forward_kernel<true>" : "band::band_forward_kernel<false>");
-        // (R > 1: eight dispatch classes of R x ceil(tiles / 8) workgroups each -- band_forward.hpp, membership; a launch
-        // never holds more members than one XCD has units for its class: choose_band)
-        for (int l = 0; l < nlaunch; ++l) {
-            ex.tile0 = l * choice.cap;
-            ex.tiles = std::min(tiles, ex.tile0 + choice.cap);
-            ex.control = w.tickets + 8 * l;
-            const int here = ex.tiles - ex.tile0;
-            const int grid = pl.R > 1 ? 8 * ((here + 7) / 8) * pl.R : here;
-            if (bg)
-                hipLaunchKernelGGL(band::band_forward_kernel<true>, dim3(grid), dim3(64 * pl.waves), (size_t)pl.lds_bytes, s, grp, ex,
-                                   pl, trans, init);
-            else
-                hipLaunchKernelGGL(band::band_forward_kernel<false>, dim3(grid), dim3(64 * pl.waves), (size_t)pl.lds_bytes, s, grp, ex,
-                                   pl, trans, init);
-        }
         if (pl.R > 1) {          // does nothing unless a member gave up waiting (band_forward.hpp)
             const size_t lds = 32 * (size_t)S;
-            e = ensure_dynamic_lds(reinterpret_cast<const void *>(&band::band_repair_kernel), lds);
+            e = ensure_dynamic_lds(&band::band_repair_kernel, lds);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(band::band_repair_kernel, dim3(tiles), dim3(1024), lds, s, grp, ex.failed, trans, init, S, pl.hl,
                                pl.hr, choice.background);
@@ -2102,29 +2033,23 @@ int decode_uniform_as(const float *observation, const int32_t *batch_frames, flo
     // 500 x 1440 decode, 16 / 4 waves: 1 item 0.081 / 0.148, 128: 0.107 / 0.160, 256: 0.141 / 0.206; two 8-wave workgroups
     // per unit for 257..512 items run like the 4-wave ones
     const bool few = B <= cu_count(device);
-#define TORBI_UNIFORM_ROWS(NQW_, R_)                                                                     \
-    if (S <= 256 * NQW_) {                                                                               \
-        constexpr int NWF = NQW_ <= 8 ? 16 : 8;                                                          \
-        if (few)                                                                                         \
-            hipLaunchKernelGGL((uniform::uniform_rows_kernel<NQW_, 1, PROBS, NWF>), dim3(B), dim3(64 * NWF), 0, s, \
-                               observation, batch_frames, initial, log_transition, indices_out, B, T, S); \
-        else                                                                                             \
-            hipLaunchKernelGGL((uniform::uniform_rows_kernel<NQW_, R_, PROBS>), dim3(B), dim3(256), 0, s, \
-                               observation, batch_frames, initial, log_transition, indices_out, B, T, S); \
-        hipLaunchKernelGGL((uniform::uniform_repair_kernel<PROBS>), dim3(B), dim3(256), 0, s, observation, batch_frames, \
-                           initial, log_transition, indices_out, B, T, S);     /* (items that read a NaN / +inf) */ \
-        mark_decode_end(device, s);                                                                      \
-        return (int)hipGetLastError();                                                                   \
-    }
-    TORBI_UNIFORM_ROWS(1, 2)
-    TORBI_UNIFORM_ROWS(2, 2)
-    TORBI_UNIFORM_ROWS(4, 2)
-    TORBI_UNIFORM_ROWS(6, 2)
-    TORBI_UNIFORM_ROWS(8, 2)
-    TORBI_UNIFORM_ROWS(12, 1)
-    TORBI_UNIFORM_ROWS(16, 1)
-#undef TORBI_UNIFORM_ROWS
-    return TORBI_HIP_EUNSUPPORTED;
+    // NQW float4 of a row per lane and pass (S <= 4096: the last instance covers what got here)
+    by_state_count<1, 2, 4, 6, 8, 12, 16>(S, [&](auto nqw) {
+        constexpr int NQW = decltype(nqw)::value, NWF = NQW <= 8 ? 16 : 8, R = NQW <= 8 ? 2 : 1;
+        if (few) {
+            auto *kernel = &uniform::uniform_rows_kernel<NQW, 1, PROBS, NWF>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * NWF), 0, s, observation, batch_frames, initial, log_transition, indices_out,
+                               B, T, S);
+        } else {
+            auto *kernel = &uniform::uniform_rows_kernel<NQW, R, PROBS>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, s, observation, batch_frames, initial, log_transition, indices_out, B,
+                               T, S);
+        }
+    });
+    hipLaunchKernelGGL(uniform::uniform_repair_kernel<PROBS>, dim3(B), dim3(256), 0, s, observation, batch_frames, initial,
+                       log_transition, indices_out, B, T, S);     // (items that read a NaN / +inf)
+    mark_decode_end(device, s);
+    return (int)hipGetLastError();
 }
 }  // namespace
 }  // extern "C++"
@@ -2247,11 +2172,8 @@ static int stream_args_ok(const void *info, const void *transition, const void *
 static int stream_tile(int B, int S, int device) {
     if (B < 1 || S < 1) return TORBI_HIP_EINVAL;
     if (S > stream::kMaxStates) return TORBI_HIP_ERANGE;
-    int G = 16;
-    while (G > 1 && (size_t)2 * G * S * sizeof(float) > (size_t)stream::kMaxLdsBytes) G >>= 1;
-    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
-    while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
-    return G;
+    return items_per_workgroup(16, B, 1, cu_count(device),
+                               [&](int G) { return (size_t)2 * G * S * sizeof(float) <= (size_t)stream::kMaxLdsBytes; });
 }
 
 int torbi_hip_stream_tile(int B, int S, int device) { return stream_tile(B, S, device); }
@@ -2275,21 +2197,11 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
         const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(transition_t) & 15) == 0;
         const dim3 grid((B + G - 1) / G);
         const size_t lds = (size_t)2 * G * S * sizeof(float);
-#define TORBI_STREAM_FORWARD(g)                                                                                         \
-        if (vec)                                                                                                        \
-            hipLaunchKernelGGL((stream::stream_forward_kernel<g, 4>), grid, dim3(stream::kThreads), lds, st, observation, \
-                               Tc, in, transition_t, initial, ring, memo, capacity, room, B, S);                              \
-        else                                                                                                            \
-            hipLaunchKernelGGL((stream::stream_forward_kernel<g, 1>), grid, dim3(stream::kThreads), lds, st, observation, \
-                               Tc, in, transition_t, initial, ring, memo, capacity, room, B, S)
-        switch (G) {
-            case 16: TORBI_STREAM_FORWARD(16); break;
-            case 8: TORBI_STREAM_FORWARD(8); break;
-            case 4: TORBI_STREAM_FORWARD(4); break;
-            case 2: TORBI_STREAM_FORWARD(2); break;
-            default: TORBI_STREAM_FORWARD(1); break;
-        }
-#undef TORBI_STREAM_FORWARD
+        by_value<16, 8, 4, 2, 1>(G, [&](auto g) { by_flag(vec, [&](auto vec_) {
+            auto *kernel = &stream::stream_forward_kernel<decltype(g)::value, decltype(vec_)::value ? 4 : 1>;
+            hipLaunchKernelGGL(kernel, grid, dim3(stream::kThreads), lds, st, observation, Tc, in, transition_t, initial, ring, memo,
+                               capacity, room, B, S);
+        }); });
         if ((code = (int)hipGetLastError()) != hipSuccess) return code;
         if (S > 1) {
             hipLaunchKernelGGL(stream::stream_first_step_kernel, dim3((S + 3) / 4, B), dim3(stream::kThreads), 0, st, in,
@@ -2322,14 +2234,18 @@ size_t torbi_hip_forward_backward_workspace_bytes(int B, int T, int S) {
     return fb::layout(nullptr, B, T, S).total;
 }
 
+// what the grids of the forward-backward kernels hold, dense or band: 32-item tiles on grid y of the step kernels, rows / 4
+// workgroups on grid x of the row kernels
+static bool fb_shape_in_range(int B, int T, int S) {
+    return S <= fb::kMaxStates && (size_t)B * T * S <= (size_t)1 << 40 && (B + 31) / 32 <= 65535 && (size_t)B * T <= (size_t)1 << 32;
+}
+
 static int fb_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *post,
                       const void *loglik, const void *ws, size_t ws_bytes, int B, int T, int S) {
     if (B < 0 || T < 1 || S < 1) return TORBI_HIP_EINVAL;
     if (B == 0) return TORBI_HIP_OK;
     if (!obs || !frames || !matrix || !initial || !post || !loglik || !ws) return TORBI_HIP_EINVAL;
-    // (grid limits: 32-item tiles on grid y of the step kernels; rows / 4 workgroups on grid x of the row kernels)
-    if (S > fb::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32)
-        return TORBI_HIP_ERANGE;
+    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
     if (ws_bytes < torbi_hip_forward_backward_workspace_bytes(B, T, S)) return TORBI_HIP_EWORKSPACE;
     return TORBI_HIP_OK;
 }
@@ -2347,23 +2263,14 @@ static hipError_t fb_step(const float *obs, const int32_t *frames, const float *
                           int T, int S, bool vec, int cus, hipStream_t st) {
     const unsigned tiles = (unsigned)((S + 31) / 32) * (unsigned)((B + 31) / 32);
     const dim3 grid((S + 31) / 32, (B + 31) / 32);
-#define TORBI_FB_STEP(staged, ks)                                                                                         \
-    do {                                                                                                                  \
-        if (vec)                                                                                                          \
-            hipLaunchKernelGGL((fb::fb_step_kernel<staged, BACKWARD, true>), grid, dim3(64 * (ks)), 0, st, obs, frames, mat, \
-                               m, cbuf, partial, loglik, post, x_in, w_out, t, B, T, S, ks);                               \
-        else                                                                                                              \
-            hipLaunchKernelGGL((fb::fb_step_kernel<staged, BACKWARD, false>), grid, dim3(64 * (ks)), 0, st, obs, frames,   \
-                               mat, m, cbuf, partial, loglik, post, x_in, w_out, t, B, T, S, ks);                          \
-    } while (0)
-    if (tiles >= 2u * cus) {
-        TORBI_FB_STEP(true, 4);
-    } else {
-        int KS = 1;
-        while (KS * 2 <= fb::kMaxWaves && (long long)tiles * KS < 8LL * cus && 8 * KS * 2 <= S) KS *= 2;
-        TORBI_FB_STEP(false, KS);
-    }
-#undef TORBI_FB_STEP
+    const bool staged = tiles >= 2u * cus;
+    int KS = staged ? 4 : 1;
+    while (!staged && KS * 2 <= fb::kMaxWaves && (long long)tiles * KS < 8LL * cus && 8 * KS * 2 <= S) KS *= 2;
+    by_flag(staged, [&](auto staged_) { by_flag(vec, [&](auto vec_) {
+        auto *kernel = &fb::fb_step_kernel<decltype(staged_)::value, BACKWARD, decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * KS), 0, st, obs, frames, mat, m, cbuf, partial, loglik, post, x_in, w_out, t, B, T,
+                           S, KS);
+    }); });
     return hipGetLastError();
 }
 
@@ -2384,7 +2291,7 @@ static int fb_dense(const float *observation, const int32_t *batch_frames, const
     const fb::Layout l = fb::layout(fb_base(workspace), B, T, S);
     float *const E = l.E, *const Et = l.Et, *const m = l.m, *const cbuf = l.c, *const partial = l.partial, *const w = l.w;
     const size_t wrow = (size_t)B * fb::padded_states(S);
-    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
+    const int cus = cu_count(device);
     hipError_t e;
     {
         const size_t n = (size_t)fb::padded_rows(S) * fb::padded_states(S);
@@ -2414,12 +2321,11 @@ static int fb_dense(const float *observation, const int32_t *batch_frames, const
         if (counts) {
             const float *wt = w + ((t + 1) & 1) * wrow;
             const int first = t == T - 2;
-            if (vec)
-                hipLaunchKernelGGL(fb::fb_counts_kernel<true>, cgrid, dim3(256), 0, st, batch_frames, counts->weights,
-                                   loglik_out, cbuf, posterior_out, wt, counts->counts, t + 1, B, T, S, first);
-            else
-                hipLaunchKernelGGL(fb::fb_counts_kernel<false>, cgrid, dim3(256), 0, st, batch_frames, counts->weights,
-                                   loglik_out, cbuf, posterior_out, wt, counts->counts, t + 1, B, T, S, first);
+            by_flag(vec, [&](auto vec_) {
+                auto *kernel = &fb::fb_counts_kernel<decltype(vec_)::value>;
+                hipLaunchKernelGGL(kernel, cgrid, dim3(256), 0, st, batch_frames, counts->weights, loglik_out, cbuf, posterior_out,
+                                   wt, counts->counts, t + 1, B, T, S, first);
+            });
             if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         }
         if ((e = fb_step<true>(observation, batch_frames, Et, m, cbuf, partial, loglik_out, posterior_out,
@@ -2477,12 +2383,11 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
     double *lse = reinterpret_cast<double *>(fb_base(workspace));
     const size_t rows = (size_t)B * T;
     const bool vec = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(observation) | reinterpret_cast<uintptr_t>(posterior_out)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(fb::fb_uniform_rows_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation,
-                           batch_frames, initial, posterior_out, lse, B, T, S);
-    else
-        hipLaunchKernelGGL(fb::fb_uniform_rows_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation,
-                           batch_frames, initial, posterior_out, lse, B, T, S);
+    by_flag(vec, [&](auto vec_) {
+        auto *kernel = &fb::fb_uniform_rows_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames, initial,
+                           posterior_out, lse, B, T, S);
+    });
     hipError_t e;
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
@@ -2493,12 +2398,9 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
 // ---- forward-backward on a band with one constant outside it (forward_backward_band.hpp) ----
 
 // Items per workgroup of fb_band_kernel<G>: as many as the LDS rows let share one load of every diagonal, but no fewer
-// workgroups than compute units while there are items for them (the rule of stream_tile).
+// workgroups than compute units while there are items for them.
 static int fb_band_tile(int B, int S, int halo, int cus) {
-    int G = fbb::kMaxGroup;
-    while (G > 1 && fbb::lds_bytes(G, S, halo) > (size_t)fbb::kMaxLdsBytes) G >>= 1;
-    while (G > 1 && (B + G - 1) / G < cus) G >>= 1;
-    return G;
+    return items_per_workgroup(fbb::kMaxGroup, B, 1, cus, [&](int G) { return fbb::lds_bytes(G, S, halo) <= (size_t)fbb::kMaxLdsBytes; });
 }
 
 int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
@@ -2506,7 +2408,7 @@ int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, 
     (void)device;
     if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
     if (background != background || background == INFINITY) return 0;
-    if ((size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32) return 0;
+    if (!fb_shape_in_range(B, T, S)) return 0;
     const int W = fbb::clamp_reach(reach_left, S) + fbb::clamp_reach(reach_right, S) + 1;
     return (W < S ? W : S) <= fbb::kMaxWindow ? 1 : 0;       // at most 64 in-band entries in a matrix row
 }
@@ -2524,8 +2426,7 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
     if (B == 0) return TORBI_HIP_OK;
     if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !workspace)
         return TORBI_HIP_EINVAL;
-    if (S > fb::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (B + 31) / 32 > 65535 || (size_t)B * T > (size_t)1 << 32)
-        return TORBI_HIP_ERANGE;
+    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
     if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device))
         return TORBI_HIP_EUNSUPPORTED;
     if (workspace_bytes < torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right))
@@ -2553,20 +2454,14 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
                        initial, m, B, T, S);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     const int halo = std::max(l.reach_left, l.reach_right);
-    const int cus = cu_count(device) > 0 ? cu_count(device) : 256;
-    const int G = fb_band_tile(B, S, halo, cus);
+    const int G = fb_band_tile(B, S, halo, cu_count(device));
     const dim3 grid((B + G - 1) / G);
     const size_t lds = fbb::lds_bytes(G, S, halo);
-#define TORBI_FB_BAND(g)                                                                                                   \
-    hipLaunchKernelGGL((fbb::fb_band_kernel<g>), grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, Df, \
-                       Db, m, cbuf, flag, posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S)
-    switch (G) {
-        case 8: TORBI_FB_BAND(8); break;
-        case 4: TORBI_FB_BAND(4); break;
-        case 2: TORBI_FB_BAND(2); break;
-        default: TORBI_FB_BAND(1); break;
-    }
-#undef TORBI_FB_BAND
+    by_value<8, 4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbb::fb_band_kernel<decltype(g)::value>;
+        hipLaunchKernelGGL(kernel, grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, Df, Db, m, cbuf, flag,
+                           posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S);
+    });
     return (int)hipGetLastError();
 }
 
@@ -2595,33 +2490,19 @@ static hipError_t kb_step(const float *obs, const int32_t *frames, const float *
                           int32_t *ptrs, int t, int B, int T, int S, int k, hipStream_t st) {
     int KMAX = 1;
     while (KMAX < k) KMAX *= 2;
-    int G = std::min(8, std::max(1, 16 / KMAX));
-    while (G > 1 && (size_t)G * S * sizeof(float) > (size_t)kb::kRowLdsBytes) G >>= 1;
     const int jblocks = (S + kb::kThreads - 1) / kb::kThreads;
-    while (G > 1 && (long long)((B + G - 1) / G) * jblocks < kb::kStepWorkgroups) G >>= 1;
+    const int G = items_per_workgroup(std::min(8, std::max(1, 16 / KMAX)), B, jblocks, kb::kStepWorkgroups,
+                                      [&](int g) { return (size_t)g * S * sizeof(float) <= (size_t)kb::kRowLdsBytes; });
     const int n = kb::list_length(k, S, t - 1), m = kb::list_length(k, S, t);
     const dim3 grid((B + G - 1) / G, jblocks);
     const size_t lds = (size_t)G * S * sizeof(float);
-#define TORBI_KB_STEP(km, g)                                                                                              \
-    hipLaunchKernelGGL((kb::kb_step_kernel<km, g>), grid, dim3(kb::kThreads), lds, st, obs, frames, tt, prev, cur, ptrs, t, \
-                       B, T, S, k, n, m)
-#define TORBI_KB_G(km)                                                                                                    \
-    switch (G) {                                                                                                          \
-        case 8: TORBI_KB_STEP(km, (km <= 2 ? 8 : 1)); break;                                                              \
-        case 4: TORBI_KB_STEP(km, (km <= 4 ? 4 : 1)); break;                                                              \
-        case 2: TORBI_KB_STEP(km, (km <= 8 ? 2 : 1)); break;                                                              \
-        default: TORBI_KB_STEP(km, 1); break;                                                                             \
-    }
-    switch (KMAX) {
-        case 1: TORBI_KB_G(1); break;
-        case 2: TORBI_KB_G(2); break;
-        case 4: TORBI_KB_G(4); break;
-        case 8: TORBI_KB_G(8); break;
-        case 16: TORBI_KB_G(16); break;
-        default: TORBI_KB_G(32); break;
-    }
-#undef TORBI_KB_G
-#undef TORBI_KB_STEP
+    by_value<1, 2, 4, 8, 16, 32>(KMAX, [&](auto kmax) { by_value<8, 4, 2, 1>(G, [&](auto g) {
+        // an instance <KMAX, G> exists only while G * KMAX <= 16 list entries fit a thread; the host's G never exceeds that
+        // (max_g above), so the clamp only keeps the other pairs of the two lists from being compiled
+        constexpr int KM = decltype(kmax)::value, GI = decltype(g)::value * KM <= 16 ? decltype(g)::value : 1;
+        auto *kernel = &kb::kb_step_kernel<KM, GI>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kb::kThreads), lds, st, obs, frames, tt, prev, cur, ptrs, t, B, T, S, k, n, m);
+    }); });
     return hipGetLastError();
 }
 
@@ -2671,18 +2552,11 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
     kb::Final *const fin = l.final_;
     int KMAX = 1;
     while (KMAX < k) KMAX *= 2;
-#define TORBI_KB_UNIFORM(km)                                                                                              \
-    hipLaunchKernelGGL(kb::kb_uniform_kernel<km>, dim3(B), dim3(64), 0, st, observation, batch_frames, uniform_value, initial, \
-                       ptrs, fin, count, flag, B, T, S, k)
-    switch (KMAX) {
-        case 1: TORBI_KB_UNIFORM(1); break;
-        case 2: TORBI_KB_UNIFORM(2); break;
-        case 4: TORBI_KB_UNIFORM(4); break;
-        case 8: TORBI_KB_UNIFORM(8); break;
-        case 16: TORBI_KB_UNIFORM(16); break;
-        default: TORBI_KB_UNIFORM(32); break;
-    }
-#undef TORBI_KB_UNIFORM
+    by_value<1, 2, 4, 8, 16, 32>(KMAX, [&](auto kmax) {
+        auto *kernel = &kb::kb_uniform_kernel<decltype(kmax)::value>;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, st, observation, batch_frames, uniform_value, initial, ptrs, fin, count, flag,
+                           B, T, S, k);
+    });
     hipError_t e;
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(kb::kb_walk_kernel<true>, dim3(B), dim3(64), 0, st, batch_frames, ptrs, fin, count, flag, indices_out,

@@ -438,11 +438,27 @@ int torbi_hip_fill_synthetic(float *dst, uint64_t count, uint64_t start, int str
  * 16-byte aligned, else 1), a function of (B, S, compute units) only and the choice the push itself makes; TORBI_HIP_EINVAL /
  * TORBI_HIP_ERANGE for a shape the push turns down.  Touches no device memory; without a usable device it answers for 256
  * compute units.
+ *
+ * torbi_hip_stream_push_lag (added within ABI 17) is the push with a decision depth (truncated, or fixed-lag, Viterbi): at
+ * most `max_lag` frames of a stream stay pending after the call.  With n frames so far and c_nat the newest frame the rule
+ * above decides (-1: none), a stream that receives at least one frame returns its frames up to c = max(c_nat, n - 1 - max_lag).
+ * Frames above c_nat are FORCED: their states lie on the backtrace from the final state of the newest row (its first NaN,
+ * otherwise its first maximum: flush's rule), so every call's output is the corresponding span of the whole-sequence decode
+ * of the stream's first n frames.  A forced span and the span after it need not join into one path: a later frame may move
+ * the best path, nothing is repaired.  forced_out [B] int32: how many of the counts_out[b] frames were forced (0 for a
+ * stream whose info does not fit, or that received no frame); state, info, indices_out and counts_out as for the push.
+ * max_lag = -1: no bound, forced_out may be NULL and the call IS torbi_hip_stream_push (which forwards here).
+ * TORBI_HIP_EINVAL for max_lag < -1 and for max_lag >= 0 without forced_out, looked at after every argument of the push.
+ * With pending <= max_lag the caller's ring never needs more than max_lag + Tc slots.
  */
 size_t torbi_hip_stream_state_bytes(int B, int S, int capacity);
 int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
                           const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+int torbi_hip_stream_push_lag(const float *observation, int Tc, const int32_t *info, const float *transition,
+                              const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
+                              int32_t *indices_out, int out_capacity, int32_t *counts_out, int max_lag, int32_t *forced_out,
+                              int B, int S, int device, void *stream);
 int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *state, size_t state_bytes, int capacity,
                            int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
 int torbi_hip_stream_tile(int B, int S, int device);

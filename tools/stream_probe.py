@@ -6,6 +6,15 @@
   (c) B=1, S=1440, 1-frame pushes: host wall time per push, p50 / p99
   (d) state bytes per stream and the largest `pending` seen on (a) and (b)
 Every figure of (a)-(c) is the median of --repeats runs with its min and max, device synchronised around each timed span.
+
+--max-lag N [N ...] adds, per decision depth N (StreamDecoder(max_lag=N)):
+  (e) case (c) again: p50 / p99 per push, the share of pushes that forced frames out, and the SEAMS on this input: a forced
+      span whose last state is not the backpointer of the next returned frame (the whole sequence's backpointers, numpy
+      float32 on the host, from the states actually returned)
+  (f) an identity matrix, --identity-pushes one-frame pushes (every commit is forced): the smallest and largest capacity and
+      state bytes once the bound binds (from push N + 2 on), and the time per push of the first and of the last hundred
+      forcing pushes
+--only-single skips the timed batches (a), (b) and (d); the input of (c) stays the same.
 """
 import argparse
 import json
@@ -63,6 +72,75 @@ def batch_case(obs, trans, init, push, repeats):
             'state_bytes_per_stream': dec._state_bytes // B, 'pending_max': pending_max}
 
 
+def single_case(one, trans, init, repeats, max_lag=None):
+    """(c): one live stream, one frame per push; the outputs of the last run come back as well."""
+    S = one.shape[2]
+    runs, outputs, forced_pushes = [], [], 0
+    for _ in range(repeats):
+        dec = torbi_amd.StreamDecoder(1, S, trans, init, log_probs=True, gpu=0, **({} if max_lag is None else {'max_lag': max_lag}))
+        outputs, forced_pushes = [], 0
+        for t in range(20):                                  # warm-up pushes (ring growth)
+            outputs.append(dec.push(one[:, t:t + 1])[0])
+        times = []
+        for t in range(20, one.shape[1]):
+            before = int(dec.forced[0]) if max_lag is not None else 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = dec.push(one[:, t:t + 1])[0]
+            times.append(time.perf_counter() - t0)
+            outputs.append(out)
+            forced_pushes += max_lag is not None and int(dec.forced[0]) > before
+        outputs = [o.cpu().numpy() for o in outputs]
+        dec.flush()
+        runs.append((np.percentile(times, 50) * 1e3, np.percentile(times, 99) * 1e3))
+    return {'p50': spread([r[0] for r in runs]), 'p99': spread([r[1] for r in runs])}, outputs, forced_pushes / len(times)
+
+
+def backpointers(seq, trans, init):
+    """The whole sequence's backpointers, numpy float32 (first maximum; the probe's inputs hold no NaN)."""
+    T, S = seq.shape
+    bp = np.zeros((T, S), np.int64)
+    post = seq[0] + init
+    for t in range(1, T):
+        cand = post[None, :] + trans
+        bp[t] = cand.argmax(axis=1)
+        post = seq[t] + cand.max(axis=1)
+    return bp
+
+
+def seams(outputs, bp):
+    """Pushes whose returned span does not continue the span before it: bp[first frame][its state] != the state before."""
+    count, frame, last = 0, 0, None
+    for out in outputs:
+        if len(out):
+            count += last is not None and int(bp[frame][int(out[0])]) != last
+            frame, last = frame + len(out), int(out[-1])
+    return count, frame
+
+
+def identity_case(S, pushes, max_lag):
+    """(f): nothing is ever decided, every returned frame is forced."""
+    dev = torch.device('cuda:0')
+    eye = torch.full((S, S), -math.inf, device=dev).fill_diagonal_(0.)
+    flat = torch.full((S,), math.log(1. / S), dtype=torch.float32, device=dev)
+    obs = peaked(1, pushes, S, dev)
+    dec = torbi_amd.StreamDecoder(1, S, eye, flat, log_probs=True, gpu=0, max_lag=max_lag)
+    times, capacity, nbytes = [], [], []
+    for t in range(pushes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec.push(obs[:, t:t + 1])
+        times.append(time.perf_counter() - t0)
+        capacity.append(dec.capacity)
+        nbytes.append(dec._state_bytes)
+    warm = max_lag + 1                                        # pushes until the bound binds; the ring has its size by then
+    first, last = np.array(times[warm:warm + 100]) * 1e3, np.array(times[-100:]) * 1e3      # (both force every push)
+    return {'pushes': pushes, 'capacity': [min(capacity[warm:]), max(capacity[warm:])],
+            'state_bytes': [min(nbytes[warm:]), max(nbytes[warm:])],
+            'pending': int(dec.pending[0]), 'forced': int(dec.forced[0]),
+            'first_hundred_ms': spread(first.tolist()), 'last_hundred_ms': spread(last.tolist())}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batch', type=int, default=512)
@@ -71,6 +149,9 @@ def main():
     ap.add_argument('--push', type=int, default=100)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--single-pushes', type=int, default=400)
+    ap.add_argument('--max-lag', type=int, nargs='*', default=[], help='decision depths to measure: cases (e) and (f)')
+    ap.add_argument('--identity-pushes', type=int, default=1000)
+    ap.add_argument('--only-single', action='store_true', help='skip the timed batches (a), (b), (d)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     B, T, S = args.batch, args.frames, args.states
@@ -79,29 +160,29 @@ def main():
     _, trans, init = synth.problem(1, 1, S, seed=0)
     trans, init = torch.from_numpy(trans).to(dev), torch.from_numpy(init).to(dev)
     obs = viterbi.fill_synthetic((B, T, S), synth.STREAM_OBSERVATION, seed=0, device=dev)
-    result['a_dense'] = batch_case(obs, trans, init, args.push, args.repeats)
+    if not args.only_single:
+        result['a_dense'] = batch_case(obs, trans, init, args.push, args.repeats)
     del obs
     band = torch.from_numpy(synth.banded_transition(S, 87.2)).to(dev)
     flat = torch.full((S,), math.log(1. / S), dtype=torch.float32, device=dev)
     obs = peaked(B, T, S, dev)
-    result['b_pitch'] = batch_case(obs, band, flat, args.push, args.repeats)
+    if not args.only_single:
+        result['b_pitch'] = batch_case(obs, band, flat, args.push, args.repeats)
 
     # (c) one live stream, one frame per push
     one = obs[:1, :args.single_pushes + 20].contiguous()
-    runs = []
-    for _ in range(args.repeats):
-        dec = torbi_amd.StreamDecoder(1, S, band, flat, log_probs=True, gpu=0)
-        for t in range(20):                                  # warm-up pushes (ring growth)
-            dec.push(one[:, t:t + 1])
-        times = []
-        for t in range(20, one.shape[1]):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            dec.push(one[:, t:t + 1])
-            times.append(time.perf_counter() - t0)
-        dec.flush()
-        runs.append((np.percentile(times, 50) * 1e3, np.percentile(times, 99) * 1e3))
-    result['c_single_push_ms'] = {'p50': spread([r[0] for r in runs]), 'p99': spread([r[1] for r in runs])}
+    result['c_single_push_ms'], _, _ = single_case(one, band, flat, args.repeats)
+    if args.max_lag:
+        seq = one[0].clone()                                 # the epsilon round trip of the decoder's input
+        torch.exp_(seq)
+        seq += torch.finfo(torch.float32).tiny
+        torch.log_(seq)
+        bp = backpointers(seq.cpu().numpy(), band.cpu().numpy(), flat.cpu().numpy())
+    for lag in args.max_lag:
+        ms, outputs, share = single_case(one, band, flat, args.repeats, max_lag=lag)
+        found, returned = seams(outputs, bp)
+        result[f'e_max_lag_{lag}'] = {'single_push_ms': ms, 'share_of_pushes_forced': share, 'seams': found,
+                                      'frames_returned': returned, 'identity': identity_case(S, args.identity_pushes, lag)}
     result['d_bytes_per_pending_frame_per_stream'] = 4 * S + 4
     print(json.dumps(result))
 

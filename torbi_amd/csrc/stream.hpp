@@ -17,6 +17,8 @@
 //                           stopping at the first frame whose set is a single state (the newest decided frame), then the
 //                           backtrace from that state down to the first pending frame
 // A flush is stream_walk_kernel with the final state (first NaN, otherwise first maximum) in place of the walk.
+// A push with a maximum lag (torbi_hip_stream_push_lag) runs stream_walk_kernel<false, true>: where the walk leaves more than
+// max_lag frames pending, the oldest of them are returned along the backtrace from the final state of the newest row.
 //
 // NaN and +/-inf need no second pass here.  The reference's scan (nonfinite.hpp::faithful_item) starts its running maximum at
 // prev-state 0 and replaces it on a strict '>': a NaN candidate at prev-state 0 wins outright (value NaN, backpointer 0) and a
@@ -221,12 +223,19 @@ __device__ __forceinline__ int wave_final_state(const float *__restrict__ row, i
 // One workgroup per stream.  FLUSH = false: frontier walk + backtrace of the newly decided frames; FLUSH = true: final state +
 // backtrace of every pending frame.  out[b][0 .. count) = the stream's frames base .. base + count - 1; counts[b] = count
 // (-1: the call's info does not fit the ring (info_fits; Tc = frames a push may add) or the output, nothing written).
+// LAG = true (push only): at most max_lag >= 0 frames stay pending.  Where the walk ends -- by any of its exits -- with
+// c < P - 1 - max_lag, frames c + 1 .. P - 1 - max_lag are FORCED: one wave takes the final state of the newest row, follows
+// the backpointers down to frame P - 1 - max_lag without storing and goes on as the backtrace of the whole returned span
+// (every survivor shares the path up to c, so the decided frames come out as they would have).  forced[b] = frames of
+// counts[b] that were forced (0 where counts[b] <= 0); without LAG neither max_lag nor forced is looked at.
 // Dynamic LDS: 2 * S int32.
-template <bool FLUSH>
+template <bool FLUSH, bool LAG = false>
 __global__ __launch_bounds__(kThreads) void stream_walk_kernel(const Info *__restrict__ info, const float *__restrict__ trans,
                                                                const float *__restrict__ ring, int32_t *__restrict__ memo,
                                                                const int32_t *__restrict__ bp, int cap, int32_t *__restrict__ out,
-                                                               int out_cap, int32_t *__restrict__ counts, int Tc, int S) {
+                                                               int out_cap, int32_t *__restrict__ counts, int Tc, int S,
+                                                               int max_lag, int32_t *__restrict__ forced) {
+    static_assert(!(FLUSH && LAG), "a flush returns every pending frame: there is nothing to bound");
     extern __shared__ int32_t lds_i[];
     int32_t *flag = lds_i, *list = lds_i + S;
     __shared__ int32_t count_s, stop_s;
@@ -236,6 +245,7 @@ __global__ __launch_bounds__(kThreads) void stream_walk_kernel(const Info *__res
     const float *r0 = ring + (size_t)b * cap * S;
     int32_t *mb = memo + (size_t)b * cap;
     auto row = [&](int r) { return r0 + (size_t)slot_of(in.base_slot, r, cap) * S; };
+    if (LAG && tid == 0) forced[b] = 0;
     if (in.frames == 0) { if (tid == 0) counts[b] = 0; return; }          // nothing asked of this stream
     if (!info_fits(in, add, FLUSH ? 0 : Tc, cap, min(cap, out_cap))) {
         if (tid == 0) counts[b] = -1;
@@ -280,6 +290,15 @@ __global__ __launch_bounds__(kThreads) void stream_walk_kernel(const Info *__res
         }
     }
     __syncthreads();
+    if (LAG && c < P - 1 - max_lag) {                   // (uniform: c, P and max_lag are the same in every thread)
+        const int target = P - 1 - max_lag;             // >= 0
+        if (tid == 0) forced[b] = target - c;
+        c = target;
+        if (wave == 0) {
+            m = wave_final_state(row(P - 1), S, lane);
+            for (int f = P - 1; f > target; --f) m = wave_backpointer(row(f - 1), trans + (size_t)m * S, S, lane);
+        }
+    }
     if (tid == 0) counts[b] = c + 1;
     if (wave != 0 || c < 0) return;
     // backtrace: frames c, c-1, ..., 0 of the pending span

@@ -2181,9 +2181,19 @@ int torbi_hip_stream_tile(int B, int S, int device) { return stream_tile(B, S, d
 int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info, const float *transition,
                           const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
                           int32_t *indices_out, int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
+    return torbi_hip_stream_push_lag(observation, Tc, info, transition, transition_t, initial, state, state_bytes, capacity,
+                                     indices_out, out_capacity, counts_out, -1, nullptr, B, S, device, stream);
+}
+
+// max_lag = -1: no bound (torbi_hip_stream_push); >= 0: the walk's bounded arm, forced_out[b] of counts_out[b] frames forced
+int torbi_hip_stream_push_lag(const float *observation, int Tc, const int32_t *info, const float *transition,
+                              const float *transition_t, const float *initial, void *state, size_t state_bytes, int capacity,
+                              int32_t *indices_out, int out_capacity, int32_t *counts_out, int max_lag, int32_t *forced_out,
+                              int B, int S, int device, void *stream) {
     int code = stream_args_ok(info, transition, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
     if (code != TORBI_HIP_OK) return code;
     if (Tc < 0 || (Tc > 0 && (!observation || !transition_t || !initial))) return TORBI_HIP_EINVAL;
+    if (max_lag < -1 || (max_lag >= 0 && !forced_out)) return TORBI_HIP_EINVAL;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2209,8 +2219,11 @@ int torbi_hip_stream_push(const float *observation, int Tc, const int32_t *info,
             if ((code = (int)hipGetLastError()) != hipSuccess) return code;
         }
     }
-    hipLaunchKernelGGL(stream::stream_walk_kernel<false>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t), st,
-                       in, transition, ring, memo, bp, capacity, indices_out, out_capacity, counts_out, Tc, S);
+    by_flag(max_lag >= 0, [&](auto lag) {
+        hipLaunchKernelGGL((stream::stream_walk_kernel<false, decltype(lag)::value>), dim3(B), dim3(stream::kThreads),
+                           (size_t)2 * S * sizeof(int32_t), st, in, transition, ring, memo, bp, capacity, indices_out, out_capacity,
+                           counts_out, Tc, S, max_lag, forced_out);
+    });
     return (int)hipGetLastError();
 }
 
@@ -2223,7 +2236,7 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
     const StreamState ss = stream_state(state, B, S, capacity);
     hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
                        static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ss.ring,
-                       ss.memo, ss.bp, capacity, indices_out, out_capacity, counts_out, 0, S);
+                       ss.memo, ss.bp, capacity, indices_out, out_capacity, counts_out, 0, S, -1, nullptr);
     return (int)hipGetLastError();
 }
 

@@ -5,8 +5,12 @@ c: no later observation can change the path up to c any more.  `push` returns, p
 `flush` the rest; concatenated they are bit-identical to `from_probabilities` on the whole sequence (NaN and +/-inf
 included).  The HIP route is csrc/stream.hpp behind torbi_hip_stream_* (include/torbi_hip.h); `gpu=None` runs the same
 decoder on the host with torch CPU ops.  STREAM.md has the layout and the kernels.
+
+`max_lag` bounds the delay and the memory (truncated, or fixed-lag, Viterbi): a push leaves at most `max_lag` frames pending
+and returns the older ones along the path that is best at the newest frame (STREAM.md, "Bounded lag").
 """
 import math
+import operator
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -27,7 +31,18 @@ class StreamDecoder:
 
     Device memory per stream: (4 * states + 4) bytes per pending frame (a posterior row and a word of the frontier walk) plus
     4 * states; the ring grows by doubling, so a stream whose frames never become decided (an identity transition matrix)
-    holds all of them until `flush`.
+    holds all of them until `flush` -- unless `max_lag` is set.
+
+    `max_lag` (None: no bound, the exact decoder above; an integer >= 0): the decision depth.  A stream with n frames that
+    receives at least one frame in a push returns its frames up to max(newest decided frame, n - 1 - max_lag), so that
+    `pending <= max_lag` after every push.  The frames beyond the decided ones are FORCED: their states lie on the backtrace
+    from the final state of the newest row (`flush`'s rule).  Every push's output is therefore the corresponding span of the
+    whole-sequence decode of the stream's first n frames, and `forced` counts the frames that left this way.
+    * A stream whose `forced` count is 0 is still bit-identical to the whole-sequence decode.
+    * A forced span and the span after it may not join into one path: a later observation can move the best path.  That is
+      the price of the bound; nothing is repaired or decoded again.
+    * The device ring (`capacity`) never exceeds the power of two at or above max_lag + (largest Tc pushed) + 1, nor does it
+      fall below INITIAL_CAPACITY; the host route holds at most max_lag + Tc + 1 rows per stream.
 
         dec = StreamDecoder(batch, states, transition, initial)
         out = dec.push(observation)       # (batch, Tc, states) -> `batch` int32 tensors, the frames decided by this push
@@ -35,9 +50,20 @@ class StreamDecoder:
     """
 
     def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
-                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0):
+                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0,
+                 max_lag: Optional[int] = None):
         if batch < 1 or states < 1:
             raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
+        if max_lag is not None:
+            try:
+                if isinstance(max_lag, bool):
+                    raise TypeError
+                max_lag = operator.index(max_lag)
+            except TypeError:
+                raise ValueError(f'max_lag must be None or an integer >= 0, got {max_lag!r}') from None
+            if max_lag < 0:
+                raise ValueError(f'max_lag must be None or an integer >= 0, got {max_lag!r}')
+        self.max_lag = max_lag
         self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
         S = self.states
         self.device = inputs._compute_device(gpu)
@@ -51,9 +77,11 @@ class StreamDecoder:
             raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
         self._frames = np.zeros(self.batch, dtype=np.int64)        # frames pushed
         self._base = np.zeros(self.batch, dtype=np.int64)          # first frame not yet returned
+        self._forced = np.zeros(self.batch, dtype=np.int64)        # frames returned by forced commits (max_lag)
         if gpu is None:
             self._rows = [[] for _ in range(self.batch)]            # posterior rows of frames base-1 .. n-1 (host)
             self._memo = [{} for _ in range(self.batch)]            # frame -> survivor-set size of an earlier walk
+            self._held = 0                                          # most rows any stream has held
         else:
             self._lib = _lib.load()
             self._transposed = self.transition.t().contiguous()
@@ -71,6 +99,16 @@ class StreamDecoder:
     def pending(self) -> torch.Tensor:
         """(batch,) int64: frames pushed and not yet returned."""
         return torch.from_numpy(self._frames - self._base)
+
+    @property
+    def forced(self) -> torch.Tensor:
+        """(batch,) int64: frames of each stream returned by forced commits (`max_lag`) since it started."""
+        return torch.from_numpy(self._forced.copy())
+
+    @property
+    def capacity(self) -> int:
+        """Ring slots per stream on the device; on the host the most rows a stream has held."""
+        return self._held if self.gpu is None else self._capacity
 
     def push(self, observation: torch.Tensor, frames: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """Append frames to the streams and return what became decided.
@@ -105,7 +143,7 @@ class StreamDecoder:
         else:
             rest = self._flush_device(sorted(set(items)))
         for k in set(items):
-            self._frames[k] = self._base[k] = 0
+            self._frames[k] = self._base[k] = self._forced[k] = 0
         return [rest[k] for k in items]
 
     # ------------------------------------------------------------------ host route
@@ -147,6 +185,7 @@ class StreamDecoder:
             for t in range(int(f[b])):
                 rows.append(obs[b, t] + self.initial if self._frames[b] == 0 else self._row(rows[-1], obs[b, t]))
                 self._frames[b] += 1
+            self._held = max(self._held, len(rows))
             n, base = int(self._frames[b]), int(self._base[b])
             c, state = -1, 0
             if f[b] > 0 and S == 1:
@@ -166,6 +205,15 @@ class StreamDecoder:
                     memo[t - 1] = k
                     if same:
                         break
+            if self.max_lag is not None and f[b] > 0 and n - 1 - self.max_lag > max(c, base - 1):
+                # more than max_lag frames would stay: the oldest leave along the path that is best at the newest frame
+                # (the decided frames lie on it as on every survivor)
+                target, first = n - 1 - self.max_lag, n - len(rows)
+                self._forced[b] += target - max(c, base - 1)
+                state = self._final_state(rows[-1])
+                for t in range(n - 1, target, -1):
+                    state = int(self._backpointers(rows[t - 1 - first], torch.tensor([state]))[0])
+                c = target
             if c >= 0:
                 result.append(self._backtrace_host(b, c, state))
                 self._base[b] = c + 1
@@ -222,6 +270,7 @@ class StreamDecoder:
         return torch.from_numpy(info.astype(np.int32)).to(self.device)
 
     def _results(self, out: torch.Tensor, counts: torch.Tensor, what: str) -> np.ndarray:
+        """`counts` (B,) or, from a push with a maximum lag, (2, B): counts and forced counts, read back in one copy."""
         got = counts.cpu().numpy().astype(np.int64)           # (the one host synchronisation of the call)
         if (got < 0).any():
             raise _lib.TorbiHipError(f'{what}: stream state does not match the call (counts {got.tolist()})')
@@ -235,14 +284,24 @@ class StreamDecoder:
             self._grow(need)
         info = self._info(pending, f)
         out = torch.empty((B, max(1, need)), dtype=torch.int32, device=self.device)
-        counts = torch.empty(B, dtype=torch.int32, device=self.device)
         _, index, stream = _lib.launch(self.device)
         Tc = int(obs.shape[1])
-        _lib.check(self._lib.torbi_hip_stream_push(
-            obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
-            self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
-            counts.data_ptr(), B, S, index, stream), 'torbi_hip_stream_push')
-        got = self._results(out, counts, 'torbi_hip_stream_push')
+        if self.max_lag is None:
+            counts = torch.empty(B, dtype=torch.int32, device=self.device)
+            _lib.check(self._lib.torbi_hip_stream_push(
+                obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
+                self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+                counts.data_ptr(), B, S, index, stream), 'torbi_hip_stream_push')
+            got = self._results(out, counts, 'torbi_hip_stream_push')
+        else:
+            counts = torch.empty((2, B), dtype=torch.int32, device=self.device)      # counts, then forced counts
+            _lib.check(self._lib.torbi_hip_stream_push_lag(
+                obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
+                self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+                counts[0].data_ptr(), min(self.max_lag, 2 ** 31 - 1), counts[1].data_ptr(), B, S, index, stream),
+                'torbi_hip_stream_push_lag')
+            got, forced = self._results(out, counts, 'torbi_hip_stream_push_lag')
+            self._forced += forced
         self._frames += f
         self._base += got
         return [out[b, :got[b]] for b in range(B)]

@@ -43,7 +43,8 @@ def check_counts(X, I, rX, rI, frames, T):
 
 
 SHAPES = [(1, 1, 3), (1, 500, 1440), (3, 50, 200), (17, 64, 65), (64, 100, 256), (512, 40, 1440), (4, 20, 4096),
-          (5, 30, 1441), (9, 12, 37), (520, 8, 1441), (700, 6, 999)]
+          (5, 30, 1441), (9, 12, 37), (520, 8, 1441), (700, 6, 999),
+          (2, 4, 5), (3, 5, 8), (4, 3, 31)]           # few items, few states: the direct step with KS = 1 (below 16 states), 2
 
 
 @pytest.mark.parametrize('B,T,S', SHAPES)

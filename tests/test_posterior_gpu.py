@@ -45,7 +45,8 @@ def check(got, want, frames):
 
 
 @pytest.mark.parametrize('B,T,S', [(1, 1, 3), (1, 500, 1440), (3, 50, 200), (17, 64, 65), (64, 100, 256), (512, 40, 1440),
-                                   (4, 20, 4096), (5, 30, 1441), (9, 12, 37), (520, 8, 1441), (700, 6, 999)])
+                                   (4, 20, 4096), (5, 30, 1441), (9, 12, 37), (520, 8, 1441), (700, 6, 999),
+                                   (2, 4, 5), (3, 5, 8), (4, 3, 31)])       # few items, few states: the direct step with KS = 1 (< 16), 2
 def test_dense_shapes_against_float64(B, T, S):
     obs, trans, init = synth.problem(B, T, S, seed=B + T + S)
     frames = np.clip(synth.lengths(B, 1, T, seed=S), 1, T).astype(np.int32)

@@ -106,6 +106,13 @@ inline Plan make_plan(int B, int S, int num_cus) {
     best.NCH = (S + best.KC - 1) / best.KC;
     best.Kp = best.NCH * best.KC;
     best.RB = n_bt >= 2 ? (n_bt + 1) / 2 : 1;
+    {   // step_dense_kernel gives each XCD an RB x RJ rectangle of tiles when eight of them divide the grid (its `rect`).  With
+        // fewer state tiles than regions along that axis (n_jt 1, 2, 3, 6 or 9 under an even n_bt) they divide it and do not
+        // TILE it: nrj * RJ > n_jt, the rectangles hold more tiles than the grid launches workgroups, and batch tiles are left
+        // without one (6400 x 3 x 96: 3200 items never computed).  Such a grid gets an RB that divides nothing: linear order.
+        const int nrb = (n_bt + best.RB - 1) / best.RB, nrj = (8 + nrb - 1) / nrb, RJ = (best.n_jt + nrj - 1) / nrj;
+        if (nrb * best.RB != n_bt || nrj * RJ != best.n_jt) best.RB = n_bt + 1;
+    }
     return best;
 }
 
@@ -345,6 +352,8 @@ void step_dense_kernel(const float *__restrict__ obs, const int32_t *__restrict_
         const int nrb = (n_bt + RB - 1) / RB;                 // regions along the batch axis
         const int nrj = (8 + nrb - 1) / nrb;                  // regions along the state axis
         const int RJ = (n_jt + nrj - 1) / nrj;
+        // (eight rectangles that do not tile the grid EXACTLY would leave tiles without a workgroup: make_plan hands such a
+        // grid an RB that does not divide n_bt, which sends it to the linear order)
         const bool rect = nrb * nrj == 8 && n_bt % RB == 0 && n_jt % RJ == 0;
         if (rect) {
             const int kb = k % RB, kj = k / RB;

@@ -229,17 +229,28 @@ struct GatherWalker {
     const float *__restrict__ rowmax;     // [T] their maxima
     const float2 *__restrict__ sorted;
     int SpP, shift, S, lane;
-    // first argmax of posterior row t (the final state when t = frames - 1: viterbi.cpp:218)
+    // first argmax of posterior row t (the final state when t = frames - 1: viterbi.cpp:218).
+    // Streamed, one float4 in flight and a running (maximum, first index) per lane -- NOT the whole row in registers as
+    // wave_first_argmax4 takes it: this runs once per path, and NQ float4 set the register count of kernels whose step
+    // loop needs half as many (35, allocated as 40: eight too many to run beside the time-resident forward kernel's three
+    // 160-register waves per SIMD).  Same answer: a NaN compares false and is passed over as fmaxf passes it
+    // over, indices ascend within a lane, and the wave takes the lowest index among the lanes that hold the maximum; a row
+    // of NaNs leaves kSentinel -> 0.
     __device__ __forceinline__ int first_state(int t) const {
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 last[NQ];
         const float *row = h + (size_t)t * S;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = 4 * lane + 256 * q;
-            last[q] = i < S ? *reinterpret_cast<const float4 *>(row + i) : zero;
+        float bv = -INFINITY;
+        int bi = kSentinel;
+#pragma unroll 1
+        for (int i = 4 * lane; i < S; i += 256) {
+            const float4 v = *reinterpret_cast<const float4 *>(row + i);
+            if (v.x > bv || (v.x == bv && i < bi)) { bv = v.x; bi = i; }
+            if (v.y > bv || (v.y == bv && i + 1 < bi)) { bv = v.y; bi = i + 1; }
+            if (v.z > bv || (v.z == bv && i + 2 < bi)) { bv = v.z; bi = i + 2; }
+            if (v.w > bv || (v.w == bv && i + 3 < bi)) { bv = v.w; bi = i + 3; }
         }
-        return wave_first_argmax4<NQ>(last, lane, S);
+        const float m = wavered::wave_reduce_f32(bv, wavered::MaxOp());
+        const int k = wavered::wave_min_i32(bv == m ? bi : kSentinel);
+        return k < S ? k : 0;
     }
     // the state at timestep tt - 1 of the path that is in state j at timestep tt
     __device__ __forceinline__ int step(int j, int tt) const {

@@ -109,47 +109,64 @@ __global__ __launch_bounds__(256) void sort_rows_kernel(const float *__restrict_
 // lists with RG = 4, ~1.4 after this pass).  The maximum is order independent and position 0 (the block's
 // largest t, used by the termination test) stays put, so results do not change.  One thread per (row group,
 // block); grid covers S/RG * SpP/16 threads.
+//
+// The block of the row being arranged and the counters of the sixteen positions live in the LDS (12 KB a workgroup, a column
+// per thread: no bank conflicts whatever entry a thread picks) and the residues of the block in one 64-bit register, four
+// bits an entry; a picked entry goes straight to its place in the list.  Held in per-thread arrays (ent[16], out[16],
+// present[16]) the same selection took 72 registers and 272 bytes of scratch a lane, which kept the kernel out of the
+// registers the time-resident forward kernel of another stream leaves free.  Same picks, same lists.
 // ---------------------------------------------------------------------------------------
 template <int RG>
 __global__ __launch_bounds__(64) void arrange_blocks_kernel(float2 *__restrict__ sorted, int S, int SpP) {
     constexpr int SHIFT = RG == 4 ? 6 : 5;     // log2(bytes of a posterior row)
-    typedef unsigned long long u64;            // RG x 8-bit counters
+    typedef unsigned long long u64;
+    __shared__ float2 s_ent[kBlk][64];         // the block of the row being arranged
+    __shared__ unsigned s_present[kBlk][64];   // per position: counts of the residues placed so far, RG x 4 bits (<= RG <= 8)
     const int nblk = SpP / kBlk;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    const int tid = threadIdx.x;
+    const int id = blockIdx.x * blockDim.x + tid;
     if (id >= (S / RG) * nblk) return;
     const int q = id / nblk, kb = id % nblk;
-    u64 present[kBlk];                      // per position: counts of the residues placed so far
     {
         const float2 *r0 = sorted + (size_t)(RG * q) * SpP + kb * kBlk;
-        for (int p = 0; p < kBlk; ++p) present[p] = (u64)1 << (8 * ((__float_as_int(r0[p].y) >> SHIFT) & (RG - 1)));
+#pragma unroll 2
+        for (int p = 0; p < kBlk; ++p) s_present[p][tid] = 1u << (4 * ((__float_as_int(r0[p].y) >> SHIFT) & (RG - 1)));
     }
+#pragma unroll 1
     for (int r = 1; r < RG; ++r) {
         float2 *row = sorted + (size_t)(RG * q + r) * SpP + kb * kBlk;
-        float2 ent[kBlk], out[kBlk];
-        u64 remaining = 0;                  // counts of the residues still to place
-        for (int e = 0; e < kBlk; ++e) {
-            ent[e] = row[e];
-            if (e) remaining += (u64)1 << (8 * ((__float_as_int(ent[e].y) >> SHIFT) & (RG - 1)));
+        u64 residue = 0;                    // 4 bits per entry of the block
+        unsigned remaining = 0;             // counts of the residues still to place, RG x 4 bits (<= 15 entries)
+#pragma unroll 2
+        for (int e = 0; e < kBlk; e += 2) {         // (two 16-byte loads in flight)
+            const float4 v = *reinterpret_cast<const float4 *>(row + e);
+            s_ent[e][tid] = make_float2(v.x, v.y);
+            s_ent[e + 1][tid] = make_float2(v.z, v.w);
+            const int r0 = (__float_as_int(v.y) >> SHIFT) & (RG - 1), r1 = (__float_as_int(v.w) >> SHIFT) & (RG - 1);
+            residue |= ((u64)r0 << (4 * e)) | ((u64)r1 << (4 * e + 4));
+            if (e) remaining += 1u << (4 * r0);
+            remaining += 1u << (4 * r1);
         }
-        out[0] = ent[0];
-        present[0] += (u64)1 << (8 * ((__float_as_int(ent[0].y) >> SHIFT) & (RG - 1)));
+        s_present[0][tid] += 1u << (4 * (int)(residue & 15u));
         unsigned used = 1u;
+#pragma unroll 1
         for (int p = 1; p < kBlk; ++p) {
+            const unsigned present = s_present[p][tid];
             int pick = -1, key = 1 << 30;
+#pragma unroll 1
             for (int e = 1; e < kBlk; ++e) {
                 if ((used >> e) & 1u) continue;
-                const int res = (__float_as_int(ent[e].y) >> SHIFT) & (RG - 1);
+                const int res = (int)(residue >> (4 * e)) & 15;
                 // fewest equal residues already at this position; then the residue with most entries left
-                const int k = (int)((present[p] >> (8 * res)) & 0xffu) * 64 - (int)((remaining >> (8 * res)) & 0xffu);
+                const int k = (int)((present >> (4 * res)) & 15u) * 64 - (int)((remaining >> (4 * res)) & 15u);
                 if (k < key) { key = k; pick = e; }
             }
-            const int res = (__float_as_int(ent[pick].y) >> SHIFT) & (RG - 1);
+            const int res = (int)(residue >> (4 * pick)) & 15;
             used |= 1u << pick;
-            remaining -= (u64)1 << (8 * res);
-            present[p] += (u64)1 << (8 * res);
-            out[p] = ent[pick];
+            remaining -= 1u << (4 * res);
+            s_present[p][tid] = present + (1u << (4 * res));
+            row[p] = s_ent[pick][tid];
         }
-        for (int p = 1; p < kBlk; ++p) row[p] = out[p];
     }
 }
 

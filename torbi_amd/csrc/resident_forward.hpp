@@ -157,22 +157,37 @@ struct OrderJobs { OrderJob job[kMaxBatches]; int ascending; int n; int tiles; i
                    unsigned *flags; int nflags;         // cluster form: the flag / ticket words to zero (else nflags = 0)
                    int ni; };                           // items per tile (16, or 8 above kMaxS16 states)
 
+// (The clamped lengths are staged in the LDS, kOrderChunk at a time, and every thread ranks its item against the chunk from
+// there, four lengths a read: a thread that read frames[o] from memory for every o took 35 us for 512 items.)
+constexpr int kOrderChunk = 2048;
 __global__ __launch_bounds__(256) void order_items_kernel(OrderJobs jobs) {
+    __shared__ __align__(16) int s_len[kOrderChunk];
     const OrderJob &jb = jobs.job[blockIdx.y];
     const int b = blockIdx.x * 256 + threadIdx.x;
     const int B = jb.B, T = jb.T;
     if (b == 0 && jb.route_record) *jb.route_record = jb.route;      // the route this batch's decode takes (torbi_hip.hip)
-    if (b >= B) return;
+    if ((int)blockIdx.x * 256 >= B) return;          // (the whole block: nobody is missed at the barriers below)
     if (B > kMaxOrdered) return;                     // order_large_* rank this batch
-    int f = jb.frames[b];
+    int f = b < B ? jb.frames[b] : 1;
     f = f < 1 ? 1 : (f > T ? T : f);
     int rank = 0;
-    for (int o = 0; o < B; ++o) {
-        int g = jb.frames[o];
-        g = g < 1 ? 1 : (g > T ? T : g);
-        rank += (g > f) || (g == f && o < b);
+    for (int o0 = 0; o0 < B; o0 += kOrderChunk) {
+        const int n = min(kOrderChunk, B - o0), n4 = (n + 3) / 4 * 4;
+        if (o0) __syncthreads();
+        for (int o = threadIdx.x; o < n4; o += 256) {
+            int g = o < n ? jb.frames[o0 + o] : 0;   // (length 0 ranks behind every item: the chunk's padding counts nothing)
+            s_len[o] = o < n ? (g < 1 ? 1 : (g > T ? T : g)) : 0;
+        }
+        __syncthreads();
+        for (int o = 0; o < n4; o += 4) {
+            const int4 g = *reinterpret_cast<const int4 *>(&s_len[o]);
+            rank += (g.x > f) || (g.x == f && o0 + o < b);
+            rank += (g.y > f) || (g.y == f && o0 + o + 1 < b);
+            rank += (g.z > f) || (g.z == f && o0 + o + 2 < b);
+            rank += (g.w > f) || (g.w == f && o0 + o + 3 < b);
+        }
     }
-    jb.order[jobs.ascending ? B - 1 - rank : rank] = b;
+    if (b < B) jb.order[jobs.ascending ? B - 1 - rank : rank] = b;
 }
 
 // Batches above kMaxOrdered items: hist[f] = items of (clamped) length f (zeroed by the host), turned into the first rank
@@ -223,11 +238,20 @@ __global__ __launch_bounds__(256) void order_large_place_kernel(OrderJob jb) {
 // behind it starts until those finish (measured: 28.3 ms for a ragged 16-batch group that has 16.5 ms of work per CU).
 // Ranked across the whole group, every engine holds an even spread of lengths and frees a CU early.
 // One thread per tile; grid = ceil(tiles / 256); O(tiles^2) compares.  Runs after order_items_kernel.
+// (Every tile's length is two dependent loads, frames[order[.]]: the block fetches them once, kOrderChunk tiles at a time,
+// into the LDS and ranks from there -- a thread that fetched all of them itself took 60 us for 256 tiles.)
 __global__ __launch_bounds__(256) void order_tiles_kernel(OrderJobs jobs) {
+    __shared__ __align__(16) int s_len[kOrderChunk];
     const int w = blockIdx.x * 256 + threadIdx.x;
     if (w < 128) jobs.stats[w] = 0u;                 // the forward launch that follows accumulates into them
     for (int k = w; k < jobs.nflags; k += gridDim.x * 256) jobs.flags[k] = 0u;     // cluster flags and tickets start at zero
-    if (w >= jobs.tiles) return;
+    if ((int)blockIdx.x * 256 >= jobs.tiles) return;          // (the whole block)
+    auto batch_of_tile = [&](int v) {
+        int k = 0;
+        for (int q = 1; q < jobs.n; ++q)
+            if (v >= jobs.job[q].tile0) k = q;
+        return k;
+    };
     auto tile_length = [&](int k, int j) {
         const OrderJob &jb = jobs.job[k];
         // the longest item of tile j: its first in descending order, its last (within the batch) in ascending order
@@ -235,21 +259,28 @@ __global__ __launch_bounds__(256) void order_tiles_kernel(OrderJobs jobs) {
         int f = jb.frames[jb.order[jobs.ascending ? last : jobs.ni * j]];
         return f < 1 ? 1 : (f > jb.T ? jb.T : f);
     };
-    int k = 0;
-    for (int q = 1; q < jobs.n; ++q)
-        if (w >= jobs.job[q].tile0) k = q;
+    const bool live = w < jobs.tiles;
+    const int k = live ? batch_of_tile(w) : 0;
     const int j = w - jobs.job[k].tile0;
-    const int mine = tile_length(k, j);
+    const int mine = live ? tile_length(k, j) : 1;
     int rank = 0;
-    for (int q = 0; q < jobs.n; ++q) {
-        const int nt = (jobs.job[q].B + jobs.ni - 1) / jobs.ni;
-        for (int t = 0; t < nt; ++t) {
-            const int other = tile_length(q, t);
-            const int ow = jobs.job[q].tile0 + t;
-            rank += (other > mine) || (other == mine && ow < w);
+    for (int v0 = 0; v0 < jobs.tiles; v0 += kOrderChunk) {
+        const int n = min(kOrderChunk, jobs.tiles - v0), n4 = (n + 3) / 4 * 4;
+        if (v0) __syncthreads();
+        for (int v = threadIdx.x; v < n4; v += 256) {
+            const int kv = v < n ? batch_of_tile(v0 + v) : 0;
+            s_len[v] = v < n ? tile_length(kv, v0 + v - jobs.job[kv].tile0) : 0;      // (0: behind every tile, counts nothing)
+        }
+        __syncthreads();
+        for (int v = 0; v < n4; v += 4) {
+            const int4 g = *reinterpret_cast<const int4 *>(&s_len[v]);
+            rank += (g.x > mine) || (g.x == mine && v0 + v < w);
+            rank += (g.y > mine) || (g.y == mine && v0 + v + 1 < w);
+            rank += (g.z > mine) || (g.z == mine && v0 + v + 2 < w);
+            rank += (g.w > mine) || (g.w == mine && v0 + v + 3 < w);
         }
     }
-    jobs.tile_map[jobs.ascending ? jobs.tiles - 1 - rank : rank] = (k << 20) | j;
+    if (live) jobs.tile_map[jobs.ascending ? jobs.tiles - 1 - rank : rank] = (k << 20) | j;
 }
 
 // every word of the exchange slots a cluster launch will use := kAbsentBits (grid-stride, 16 bytes per thread and step)

@@ -347,6 +347,19 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void *base, un
 #ifndef RESIDENT_EXTRA_VALU
 #define RESIDENT_EXTRA_VALU 0
 #endif
+// RESIDENT_HORIZON: which of the termination tests -- all valid, one behind every block -- a wave pass evaluates.  A pass
+// walks max(1, n - RESIDENT_HORIZON_SLACK) blocks before its first test, n = the blocks the same row group's scan walked at
+// the previous timestep (1 at t = 1), and tests behind every block from there on.  A row group's depth moves little from one
+// timestep to the next and no pass of the benchmark ends before block 9: the tests in front of the horizon decide nothing
+// (tools/scan_horizon_sim.py, profiles/scan_horizon_sim.txt: slack 2 walks 0.7 % more blocks and leaves 2.7 of 11.8 tests).
+// A scan that overshoots stops at its first test and lowers the next horizon by the slack.  Results do not depend on it:
+// examining more entries never changes a maximum, and a scan still stops only behind a test that says so.
+#ifndef RESIDENT_HORIZON
+#define RESIDENT_HORIZON 1
+#endif
+#ifndef RESIDENT_HORIZON_SLACK
+#define RESIDENT_HORIZON_SLACK 2
+#endif
 
 #ifdef RESIDENT_STAMP
 // build-time instrumentation (tools/resident_stamps.py): per-wave cycle sums of the phases of a timestep
@@ -543,6 +556,10 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     // scan statistics for adaptive path selection (every 16th timestep): how many 16-entry list blocks a wave pass
     // walks.  The benchmark needs 10.6 of the 90 a row holds; near 90 nothing is being pruned and the dense kernel wins.
     unsigned stat_blocks = 0, stat_passes = 0;
+    // RESIDENT_HORIZON: blocks each of this wave's passes walks before its first termination test (wave-uniform)
+    int horizon[MAXP];
+#pragma unroll
+    for (int p = 0; p < MAXP; ++p) horizon[p] = 1;
 
     // publish the largest entries of the row the tile holds (decoded; states as offsets into tt) and empty the
     // running lists for the next row's outputs
@@ -713,8 +730,10 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
 #pragma unroll
                         for (int r = 0; r < kR; ++r) best[it] = fmaxf(best[it], seedv[it][r] + seedt[it][r]);
                 };
+                const int first_test = RESIDENT_HORIZON ? horizon[p] : 1;
                 auto more = [&](const ListBlock<EPL> &blk) {
                     if (RESIDENT_ABL & 1) return nblk < 11;
+                    if (RESIDENT_HORIZON && nblk < first_test) return true;
                     const float tn = group_bcast<G, 0>(blk.e[0].x);
                     return (bool)__any(jv && ((tn + thr[0] > best[0]) | (tn + thr[1] > best[1]) | (tn + thr[2] > best[2]) |
                                               (tn + thr[3] > best[3])));
@@ -735,6 +754,8 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     load_list_block(cur, row, kk + 3 * kBlk);
                 }
                 if ((t & 15) == 1) { stat_blocks += (unsigned)nblk; stat_passes += 1u; }
+                if (RESIDENT_HORIZON)
+                    horizon[p] = __builtin_amdgcn_readfirstlane(max(1, nblk - RESIDENT_HORIZON_SLACK));
                 RSTAMP(3);
                 // the four items' list thresholds are read together (one LDS round trip, not four in a row)
                 u64 last4[4];

@@ -533,6 +533,41 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
                                     int T, int S, int device, void *stream);
 
 /*
+ * Expected counts on a band (added within ABI 17): torbi_hip_forward_backward_band on the same inputs, which writes
+ * posterior_out and loglik_out bit for bit as that call does, and in addition the counts of
+ * torbi_hip_forward_backward_counts inside the band, diagonal by diagonal, and the initial counts:
+ *     band_counts_out[k][j] = X[j][j - reach_left + k]      (W, S) fp32, W = reach_left + reach_right + 1 with the reaches
+ *                                                            clamped to S - 1; 0 where the matrix clips the diagonal
+ *     initial_counts_out[j] = sum_b g_b gamma_0^b[j]        (S,) fp32
+ * with X[j][i] = sum_b g_b sum_{1 <= t < F_b} xi_t(j, i), item_weights (B,) fp32 (null: all ones).  An item with g_b == 0 or a
+ * non-finite L_b is skipped, not multiplied.  The counts are gathered inside the backward pass of the one launch that runs
+ * all frames (one fp32 plane [W][S] in LDS per workgroup, at most 512 workgroups, each over its tiles in order) and summed
+ * over the workgroups in order: the summation order is fixed, so the bits depend on the inputs (and the device's compute
+ * unit count, which sets the tile) only; no float atomics.  Where the promise about the band is broken, every entry of both
+ * outputs is NaN as well.
+ *
+ * A finite background puts mass outside the band: X[j][i] = exp(background) * sum_b g_b sum_t w_t[j] a_{t-1}[i] / c_{t-1}
+ * there.  That is a dense product of rank sum_b F_b and is NOT computed: the call returns the in-band counts only.  The
+ * total outside the band is sum_b g_b (F_b - 1) over the counted items minus the band's total.
+ *
+ * torbi_hip_forward_backward_counts_band_covers: 1 where torbi_hip_forward_backward_band_covers answers 1 AND the plane fits
+ * beside the rows of one item, 4 W S + the rows' bytes <= 160 KB (the pitch band, 23 diagonals of 1440 states: 144 KB), else
+ * 0.  It and _workspace_bytes answer without a device.  workspace: the band route's plus min(B, 512) planes [W][S up to 64]
+ * fp32, torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation.
+ * Six launches per call whatever T is, no host synchronisation: with a caller-owned workspace a call can be captured into a
+ * graph.  Errors as torbi_hip_forward_backward_band, TORBI_HIP_EINVAL also for a null band_counts_out or
+ * initial_counts_out, TORBI_HIP_EUNSUPPORTED where _covers answers 0.
+ */
+int torbi_hip_forward_backward_counts_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                  int device);
+size_t torbi_hip_forward_backward_counts_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_counts_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                           const float *initial, int reach_left, int reach_right, float background,
+                                           const float *item_weights, float *posterior_out, float *loglik_out,
+                                           float *band_counts_out, float *initial_counts_out, void *workspace,
+                                           size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
+/*
  * k-best Viterbi decoding (added within ABI 17): the k best state sequences of every item with their exact scores, on the
  * model torbi_hip_viterbi_decode decodes (torbi_amd/k_best.py, KBEST.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log; 1 <= k <= 32.

@@ -11,6 +11,12 @@ line.
   accuracy: errors of the counts against the float64 host route on the shapes of tests/test_counts_gpu.py, with the share
       of the test bounds they use
 Every time is the median of --repeats calls with its min and max, device synchronised around each call.
+
+  --band: the band counts route (torbi_amd.forward_backward_counts_banded, csrc/counts_band.hpp) instead: on the pitch
+      matrix (synth.banded_transition(1440, 12), peaked rows) the band counts call against the dense counts call and
+      against forward_backward_banded (what the counting adds), the three alternated call by call, at 512 x T x 1440 with
+      -inf and with log(tiny) outside the band, 1 x T x 1440 and 8 x 120 x 1440; expected_counts through both routes;
+      workspace bytes (tests/test_counts_band_gpu.py prints the share of every accuracy bound it uses)
 """
 import argparse
 import json
@@ -126,14 +132,69 @@ def accuracy(dev):
     return rows
 
 
+def peaked(B, T, S, half_width, seed, dev):
+    """Posteriorgram rows peaked around a pitch track that moves inside the band (log of a normalised row), made on the
+    device 16 items at a time."""
+    rng = np.random.default_rng(seed)
+    track = np.clip(np.cumsum(rng.integers(-half_width + 1, half_width, size=(B, T)), axis=1)
+                    + rng.integers(S // 4, 3 * S // 4, size=(B, 1)), 0, S - 1)
+    track = torch.from_numpy(track).to(dev)
+    x = torch.arange(S, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    obs = torch.empty((B, T, S), dtype=torch.float32, device=dev)
+    for b in range(0, B, 16):
+        rows = torch.exp(-0.5 * ((x - track[b:b + 16, :, None]) / 3.) ** 2)
+        rows += 1e-3 * torch.rand(rows.shape, device=dev, generator=gen)
+        obs[b:b + 16] = torch.log(rows / rows.sum(-1, keepdim=True))
+    return obs
+
+
+def band_case(B, T, S, half_width, tiny, repeats, dev):
+    reach = half_width - 1
+    background = float(np.log(np.finfo(np.float32).tiny)) if tiny else -np.inf
+    obs = peaked(B, T, S, half_width, 1, dev)
+    trans = torch.from_numpy(synth.banded_transition(S, half_width, tiny=tiny)).to(dev)
+    init = torch.full((S,), float(np.log(np.float32(1. / S))), device=dev)
+    frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(torbi_amd.expected_counts_workspace_bytes(B, T, S),
+                         torbi_amd.expected_counts_banded_workspace_bytes(B, T, S, reach, reach)), dtype=torch.uint8, device=dev)
+    dense = lambda: torbi_amd.forward_backward_counts(obs, frames, trans, init, workspace=ws)
+    band = lambda: torbi_amd.forward_backward_counts_banded(obs, frames, trans, init, reach, reach, background, workspace=ws)
+    post = lambda: torbi_amd.forward_backward_banded(obs, frames, trans, init, reach, reach, background, workspace=ws)
+    fns = [dense, band, post]
+    if not tiny:
+        fns += [lambda: torbi_amd.expected_counts(obs, frames, trans, init, log_probs=True, gpu=0, route='dense'),
+                lambda: torbi_amd.expected_counts(obs, frames, trans, init, log_probs=True, gpu=0, route='band')]
+    t = alternated(fns, repeats)
+    out = {'shape': [B, T, S], 'reach': reach, 'background': 'log(tiny)' if tiny else '-inf', 'dense_counts_ms': t[0],
+           'band_counts_ms': t[1], 'forward_backward_banded_ms': t[2], 'dense_over_band': t[0]['median'] / t[1]['median'],
+           'band_counts_over_banded': t[1]['median'] / t[2]['median'],
+           'band_workspace_bytes': torbi_amd.expected_counts_banded_workspace_bytes(B, T, S, reach, reach),
+           'dense_workspace_bytes': torbi_amd.expected_counts_workspace_bytes(B, T, S),
+           'auto_route': torbi_amd.counts_route(trans, B, T, S, gpu=0, log_probs=True)}
+    if not tiny:
+        out.update(expected_counts_dense_ms=t[3], expected_counts_band_ms=t[4])
+        Xd, Xb = dense()[2], torbi_amd.band_counts_to_dense(band()[2], reach, reach)
+        out['max_abs_band_minus_dense_over_max'] = float((Xd - Xb).abs().max() / Xd.abs().max())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--T', type=int, default=500)
     ap.add_argument('--no-accuracy', action='store_true')
+    ap.add_argument('--band', action='store_true', help='measure the band counts route on the pitch matrix')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     out = {'device': torch.cuda.get_device_name(0)}
+    if args.band:
+        out['band_512_ninf'] = band_case(512, args.T, 1440, 12, False, args.repeats, dev)
+        out['band_512_tiny'] = band_case(512, args.T, 1440, 12, True, args.repeats, dev)
+        out['band_1'] = band_case(1, args.T, 1440, 12, False, args.repeats, dev)
+        out['band_8x120'] = band_case(8, 120, 1440, 12, False, args.repeats, dev)
+        print(json.dumps(out))
+        return
     out['a_dense_512'] = dense_case(512, args.T, 1440, args.repeats, dev, baseline=True)
     out['b_dense_1'] = dense_case(1, args.T, 1440, args.repeats, dev, baseline=False)
     out['e_workspace_bytes'] = torbi_amd.expected_counts_workspace_bytes(512, args.T, 1440)

@@ -20,7 +20,8 @@ from .core import release_job_memory
 from .stream import StreamDecoder
 from .posterior import (forward_backward, forward_backward_banded, forward_backward_banded_workspace_bytes,
                         forward_backward_workspace_bytes, posterior_route, state_posteriors)
-from .training import (expected_counts, expected_counts_workspace_bytes, forward_backward_counts,
+from .training import (band_counts_to_dense, counts_route, expected_counts, expected_counts_banded_workspace_bytes,
+                       expected_counts_workspace_bytes, forward_backward_counts, forward_backward_counts_banded,
                        log_likelihood)
 from .k_best import best_paths, decode_k_best, decode_k_best_workspace_bytes
 
@@ -30,4 +31,5 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'StreamDecoder', 'state_posteriors', 'forward_backward', 'forward_backward_workspace_bytes',
            'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood',
            'best_paths', 'decode_k_best', 'decode_k_best_workspace_bytes', 'forward_backward_banded',
-           'forward_backward_banded_workspace_bytes', 'posterior_route']
+           'forward_backward_banded_workspace_bytes', 'posterior_route', 'forward_backward_counts_banded',
+           'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route']

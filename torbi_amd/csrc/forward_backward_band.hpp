@@ -111,6 +111,9 @@ __global__ __launch_bounds__(64) void fb_band_verify_kernel(const float *__restr
 }
 
 // ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, S, halo) ----
+// (counts_band.hpp's fb_band_counts_kernel repeats the passes below and promises the same bits of gamma, c_t and L: a change
+// to the ownership, the reductions or the order of the arithmetic here has to be made there too;
+// tests/test_counts_band_gpu.py compares the two bit for bit)
 template <int G>
 __global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
                                                            const float *__restrict__ initial, const float *__restrict__ Df,

@@ -42,6 +42,7 @@
 #include "stream.hpp"
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
+#include "counts_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
 
@@ -2475,6 +2476,83 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
         hipLaunchKernelGGL(kernel, grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, Df, Db, m, cbuf, flag,
                            posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S);
     });
+    return (int)hipGetLastError();
+}
+
+// ---- expected counts on a band (counts_band.hpp) ----
+
+// Items per workgroup of fb_band_counts_kernel<G>: fb_band_tile's rule with the plane beside the rows.
+static int fb_band_counts_tile(int B, int S, int halo, int W, int cus) {
+    return items_per_workgroup(fbb::kMaxGroup, B, 1, cus, [&](int G) {
+        const size_t rows = fbb::lds_bytes(G, S, halo);
+        return rows <= (size_t)fbb::kMaxLdsBytes && rows + fbb::plane_bytes(W, S) <= (size_t)fbb::kCountsLdsBytes;
+    });
+}
+
+int torbi_hip_forward_backward_counts_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                  int device) {
+    if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device)) return 0;
+    const int left = fbb::clamp_reach(reach_left, S), right = fbb::clamp_reach(reach_right, S);
+    return fbb::lds_bytes(1, S, std::max(left, right)) + fbb::plane_bytes(left + right + 1, S) <= (size_t)fbb::kCountsLdsBytes
+               ? 1 : 0;
+}
+
+size_t torbi_hip_forward_backward_counts_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbb::counts_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_counts_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                           const float *initial, int reach_left, int reach_right, float background,
+                                           const float *item_weights, float *posterior_out, float *loglik_out,
+                                           float *band_counts_out, float *initial_counts_out, void *workspace,
+                                           size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !band_counts_out ||
+        !initial_counts_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
+    if (!torbi_hip_forward_backward_counts_band_covers(B, T, S, reach_left, reach_right, background, device))
+        return TORBI_HIP_EUNSUPPORTED;
+    if (workspace_bytes < torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right))
+        return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbb::CountsLayout l = fbb::counts_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    hipError_t e;
+    const size_t cells = (size_t)l.W * l.Sd;
+    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
+                       transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
+                       l.reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int halo = std::max(l.reach_left, l.reach_right);
+    const int G = fb_band_counts_tile(B, S, halo, l.W, cu_count(device));
+    const int grid = std::min((B + G - 1) / G, fbb::kCountsWorkgroups);           // (<= l.planes)
+    const size_t lds = fbb::lds_bytes(G, S, halo) + fbb::plane_bytes(l.W, S);
+    e = by_value<8, 4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbb::fb_band_counts_kernel<decltype(g)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, l.Df, l.Db, l.m,
+                           l.c, l.flag, item_weights, posterior_out, loglik_out, l.partial, ebg, l.reach_left, l.reach_right,
+                           l.W, l.Sd, B, T, S);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_initial_counts_kernel, dim3((S + 255) / 256), dim3(256), 0, st, item_weights, loglik_out,
+                       posterior_out, initial_counts_out, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fbb::fb_band_counts_finalize_kernel, dim3((unsigned)(((size_t)l.W * S + 255) / 256)), dim3(256), 0, st,
+                       transition, l.partial, l.flag, band_counts_out, initial_counts_out, grid, l.reach_left, l.W, l.Sd, S);
     return (int)hipGetLastError();
 }
 

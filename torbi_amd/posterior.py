@@ -131,6 +131,40 @@ def _run_band(observation, frames, transition, initial, reach_left, reach_right,
     return post, loglik
 
 
+def _counts_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_forward_backward_counts_band_covers: the band counts route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_forward_backward_counts_band_covers(B, T, S, int(reach_left), int(reach_right),
+                                                                          ctypes.c_float(background), index))
+
+
+def _run_band_counts(observation, frames, transition, initial, reach_left, reach_right, background, item_weights=None,
+                     workspace=None):
+    """One call of the band counts route (torbi_hip_forward_backward_counts_band) on the device of `observation` (float32,
+    contiguous, log space) and (B,) int32 `frames` there: (posterior, log_likelihood, band_counts (W, S), initial_counts),
+    the counts weighted by `item_weights` (None = all ones)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    device = observation.device
+    lib = _lib.load()
+    W = min(reach_left, S - 1) + min(reach_right, S - 1) + 1
+    out = (torch.empty((B, T, S), dtype=torch.float32, device=device),
+           torch.empty((B,), dtype=torch.float32, device=device),
+           torch.zeros((W, S), dtype=torch.float32, device=device),
+           torch.zeros((S,), dtype=torch.float32, device=device))
+    if B == 0:
+        return out
+    need = lib.torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
+    init = initial.to(device=device, dtype=torch.float32).contiguous()
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    weights = None if item_weights is None else item_weights.to(device=device, dtype=torch.float32).contiguous()
+    _lib.check(lib.torbi_hip_forward_backward_counts_band(
+        observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(), reach_left, reach_right,
+        ctypes.c_float(background), None if weights is None else weights.data_ptr(), *(t.data_ptr() for t in out),
+        workspace.data_ptr(), workspace.numel(), B, T, S, index, stream), 'torbi_hip_forward_backward_counts_band')
+    return out
+
+
 def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
                             initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
                             workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:

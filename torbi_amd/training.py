@@ -8,8 +8,10 @@ given), A indexed [next, prev]:
 
 so `log_likelihood(...).sum().backward()` gives gamma, X and I, and one Baum-Welch step normalises X over its columns (next
 states of one previous state).  The HIP route is csrc/counts.hpp behind torbi_hip_forward_backward_counts
-(include/torbi_hip.h), fed by the passes of `forward_backward`; `gpu=None` and CPU tensors run the same scaled recurrence in
-float64 with torch CPU ops.  POSTERIOR.md ("Expected counts") has the contract, the kernels and the numbers.
+(include/torbi_hip.h), fed by the passes of `forward_backward`, and for a matrix that is -inf outside a band
+csrc/counts_band.hpp behind torbi_hip_forward_backward_counts_band, which gathers the counts of the band's diagonals inside
+the one launch of `forward_backward_banded`; `gpu=None` and CPU tensors run the same scaled recurrence in float64 with torch
+CPU ops.  POSTERIOR.md ("Expected counts", "Band counts") has the contract, the kernels and the numbers.
 """
 import math
 from typing import Optional, Tuple
@@ -17,7 +19,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib, inputs
-from .posterior import _host, _operands, _run
+from .posterior import _band, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts
+
+ROUTES = ('auto', 'dense', 'band')
 
 
 def expected_counts_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -47,23 +51,138 @@ def forward_backward_counts(observation: torch.Tensor, batch_frames: Optional[to
     return _run(obs, frames, transition, None, initial, workspace, counts=True, item_weights=item_weights)
 
 
+def expected_counts_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_counts_banded` needs for a (B, T, S) problem with this band."""
+    return int(_lib.load().torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, int(reach_left),
+                                                                                  int(reach_right)))
+
+
+def forward_backward_counts_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor],
+                                   transition: torch.Tensor, initial: torch.Tensor, reach_left: int, reach_right: int,
+                                   background: float = -math.inf, item_weights: Optional[torch.Tensor] = None,
+                                   workspace: Optional[torch.Tensor] = None):
+    """`forward_backward_banded` plus the weighted expected counts inside the band, at the cost of the band alone.
+
+    The band, the promise about `background` and what a broken promise gives (NaN, here in the counts too) are
+    `forward_backward_banded`'s.  With a finite background the model has mass outside the band; those counts are a dense
+    product and are not computed: the call returns the in-band counts only.
+
+    Args:
+        observation, batch_frames, transition, initial, reach_left, reach_right, background: as `forward_backward_banded`
+        item_weights: (B,) weights g_b; None = all ones.  An item with g_b == 0 or a non-finite log-likelihood is skipped.
+        workspace: optional uint8 device tensor of >= `expected_counts_banded_workspace_bytes(B, T, S, reach_left,
+            reach_right)` bytes (then the call allocates nothing but its outputs and can be captured into a graph)
+
+    Returns:
+        (posterior (B, T, S), log_likelihood (B,), band_counts (W, S), initial_counts (S,)), float32 on the device.
+        band_counts[k, j] = X[j, j - reach_left + k] with X [next, prev] the counts of `forward_backward_counts` and
+        W = reach_left + reach_right + 1 (the reaches clamped to S - 1); 0 where the matrix clips the diagonal
+        (`band_counts_to_dense` gives X).  posterior and log_likelihood are bit for bit those of `forward_backward_banded`.
+
+    Raises where the band counts route does not cover the call (torbi_hip_forward_backward_counts_band_covers: what
+    `forward_backward_banded` covers and 4 W S bytes plus one item's rows within 160 KB of LDS).
+    """
+    if transition is None or initial is None:
+        raise RuntimeError('forward_backward_counts_banded needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
+    if reach_left < 0 or reach_right < 0:
+        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
+    if B > 0 and not _counts_covered(B, T, S, reach_left, reach_right, background):
+        raise RuntimeError(f'forward_backward_counts_banded does not cover B={B}, T={T}, S={S}, reach '
+                           f'{reach_left}/{reach_right}, background {background} (forward_backward_counts takes any matrix)')
+    obs, frames = _operands('forward_backward_counts_banded', observation, batch_frames, transition, initial, item_weights)
+    return _run_band_counts(obs, frames, transition, initial, reach_left, reach_right, background, item_weights, workspace)
+
+
+def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right: int) -> torch.Tensor:
+    """The (S, S) matrix [next, prev] of the (W, S) `band_counts` of `forward_backward_counts_banded`: dense[j, j - reach_left
+    + k] = band_counts[k, j], zeros outside the band.  On the tensor's device."""
+    W, S = band_counts.shape
+    left, right = min(int(reach_left), S - 1), min(int(reach_right), S - 1)
+    if W != left + right + 1:
+        raise RuntimeError(f'band_counts must have {left + right + 1} rows for reach {reach_left}/{reach_right} and {S} '
+                           f'states; got {W}')
+    j = torch.arange(S, device=band_counts.device)[None, :]
+    i = j - left + torch.arange(W, device=band_counts.device)[:, None]
+    inside = (i >= 0) & (i < S)
+    dense = torch.zeros((S, S), dtype=band_counts.dtype, device=band_counts.device)
+    dense[j.expand(W, S)[inside], i[inside]] = band_counts[inside]
+    return dense
+
+
+def _auto_takes(B, W) -> bool:
+    """The classes of (items, diagonals) route='auto' sends to the band counts route; route='band' takes whatever is
+    covered.  Measured on the pitch band (W = 23 at 1440 states, close to the largest plane that is covered) at 1, 8 and 512
+    items, the band route beat the dense one 3.0 to 8.1 times with a spread below 2.2 % (POSTERIOR.md "Band counts"), so no
+    class is excluded; one that is found to lose goes here."""
+    return True
+
+
+def _counts_band(trans, original, B, T, S, index, route):
+    """(reach_left, reach_right) when `route` sends the counts of the prepared device matrix `trans` to the band route, else
+    None: `posterior._band` finds a band, the matrix is -inf outside it (so the dense (S, S) result is exactly zero there),
+    torbi_hip_forward_backward_counts_band_covers takes it and, for 'auto', the class was measured faster."""
+    if route == 'dense':
+        return None
+    band = _band(trans, original, B, T, S, index)
+    if band is not None and band[2] == -math.inf and _counts_covered(B, T, S, band[0], band[1], band[2], index) \
+            and (route == 'band' or _auto_takes(B, band[0] + band[1] + 1)):
+        return band[0], band[1]
+    if route == 'band':
+        raise RuntimeError("route='band': the transition matrix has no band with -inf outside it that "
+                           'forward_backward_counts_banded covers')
+    return None
+
+
+def _check_route(route):
+    if route not in ROUTES:
+        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+
+
+def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
+                 log_probs: bool = False) -> str:
+    """The route `expected_counts(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
+    (batch, frames, states) observation: 'band' (`forward_backward_counts_banded`) or 'dense'
+    (`forward_backward_counts`)."""
+    if transition is None:
+        return 'dense'
+    if tuple(transition.shape) != (states, states):
+        raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
+    device = inputs._compute_device(gpu)
+    if device.type == 'cpu':
+        return 'dense'
+    trans = inputs._prepared_transition(transition, log_probs, device)
+    return 'dense' if _counts_band(trans, transition, int(batch), int(frames), states, device.index, 'auto') is None else 'band'
+
+
 def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
                     transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None,
-                    log_probs: bool = False, gpu: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                    log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto'
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Expected transition and initial-state counts (the E-step of Baum-Welch) and log P(observations) of every item.
 
     Arguments mean what they mean to `state_posteriors` (and `from_probabilities`), defaults and preprocessing included;
     `transition=None` runs the dense route on a matrix filled with fl(log(1/S)).  `gpu` is a HIP device index; None
     computes in float64 on the CPU.  An item whose log-likelihood is not finite adds nothing to the counts.
 
+    route: which device route a given matrix takes.  'auto': the band route where the matrix is -inf outside a band that
+        `forward_backward_counts_banded` covers (`counts_route` answers which), else the dense one; 'dense': always the
+        dense route; 'band': the band route, raising where auto would go dense.  The result is the same (S, S) matrix
+        either way, exactly zero outside the band; the roundings differ.  Ignored by `gpu=None`.  'auto' and 'band' look at
+        the matrix (`viterbi.band_over`: one small kernel and a host synchronisation the first time a tensor version is
+        seen, for a dense matrix too when S % 4 == 0 and 64 <= S <= 3072); 'dense' does not.
+
     Returns:
         (transition_counts (S, S) [next, prev], initial_counts (S,), log_likelihood (B,)), float32 on the compute device.
         transition_counts[j, i] is the expected number of steps from state i to state j; one M-step divides each column by
         its sum.
     """
+    _check_route(route)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
+    original = transition
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
     if transition is None:
         transition = torch.full((S, S), uniform, dtype=torch.float32, device=device)
@@ -71,6 +190,15 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     if gpu is None:
         _, L, X, I = _host_counts(obs, frames, transition.to(torch.float32), initial.to(torch.float32), None)
         return X.to(torch.float32), I.to(torch.float32), L.to(torch.float32)
+    if original is None:
+        if route == 'band':
+            raise RuntimeError("route='band': a uniform transition matrix has no band")
+        band = None
+    else:
+        band = _counts_band(transition, original, B, T, S, device.index, route)
+    if band is not None:
+        _, L, Xb, I = _run_band_counts(obs, frames, transition, initial, band[0], band[1], -math.inf)
+        return band_counts_to_dense(Xb, band[0], band[1]), I, L
     _, L, X, I = _run(obs, frames, transition, None, initial, counts=True)
     return X, I, L
 
@@ -83,17 +211,22 @@ def _host_counts(obs, frames, transition, initial, weights, counts=True):
 
 class _LogLikelihood(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, observation, batch_frames, transition, initial):
+    def forward(ctx, observation, batch_frames, transition, initial, route):
         B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
         ctx.dtypes = (observation.dtype, transition.dtype, initial.dtype)
         ctx.devices = (observation.device, transition.device, initial.device)
+        ctx.band = None
         if observation.is_cuda:
             device = observation.device
             frames = inputs.frames(batch_frames, B, T, device)
             obs = observation.detach().to(dtype=torch.float32).contiguous()
             trans = transition.detach().to(device=device, dtype=torch.float32).contiguous()
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
-            gamma, L = _run(obs, frames, trans, None, init)
+            ctx.band = _counts_band(trans, transition, B, T, S, device.index, route)
+            if ctx.band is not None:
+                gamma, L = _run_band(obs, frames, trans, init, ctx.band[0], ctx.band[1], -math.inf)
+            else:
+                gamma, L = _run(obs, frames, trans, None, init)
             ctx.save_for_backward(obs, frames, trans, init, gamma, L)
             return L
         frames = inputs.frames(batch_frames, B, T, torch.device('cpu'))
@@ -106,14 +239,18 @@ class _LogLikelihood(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
         obs, frames, trans, init, gamma, L = ctx.saved_tensors
-        need_o, _, need_t, need_i = ctx.needs_input_grad
+        need_o, _, need_t, need_i, _ = ctx.needs_input_grad
         g = grad.to(device=gamma.device, dtype=gamma.dtype)
         d_obs = d_trans = d_init = None
         if need_o:
             d_obs = g[:, None, None] * gamma                                        # rows t >= F are 0 in gamma
         if need_t or need_i:
             if need_t:
-                if obs.is_cuda:
+                if ctx.band is not None:
+                    left, right = ctx.band
+                    _, _, Xb, I = _run_band_counts(obs, frames, trans, init, left, right, -math.inf, g.contiguous())
+                    X = band_counts_to_dense(Xb, left, right)
+                elif obs.is_cuda:
                     _, _, X, I = _run(obs, frames, trans, None, init, counts=True, item_weights=g.contiguous())
                 else:
                     _, _, X, I = _host_counts(obs, frames, trans, init, g)
@@ -130,11 +267,11 @@ class _LogLikelihood(torch.autograd.Function):
             d_init = None if not need_i else I
         dtypes, devices = ctx.dtypes, ctx.devices
         cast = lambda v, k: None if v is None else v.to(device=devices[k], dtype=dtypes[k])
-        return cast(d_obs, 0), None, cast(d_trans, 1), cast(d_init, 2)
+        return cast(d_obs, 0), None, cast(d_trans, 1), cast(d_init, 2), None
 
 
 def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
-                   initial: torch.Tensor) -> torch.Tensor:
+                   initial: torch.Tensor, route: str = 'auto') -> torch.Tensor:
     """log P(observations) of every item, differentiable in observation, transition and initial (log inputs, the operator
     level, like `forward_backward`).
 
@@ -144,9 +281,17 @@ def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tenso
     Gradients: d/dobservation = g gamma (rows t >= F_b are 0), d/dtransition = X(g), d/dinitial = I(g); a non-finite L_b
     with g_b != 0 makes the transition and initial gradients NaN.  First order only.
 
+    route: as `expected_counts` -- where a device matrix is -inf outside a band the band routes cover, 'auto' and 'band'
+    make the forward one `forward_backward_banded` call and the backward one `forward_backward_counts_banded` call (the
+    transition gradient is the (S, S) matrix either way, zero outside the band).  Ignored by CPU tensors.  'auto' and 'band'
+    look at the matrix in the forward (`viterbi.band_over`: one small kernel and a host synchronisation per new tensor
+    version, so once per step of a training loop that updates the matrix); `route='dense'` keeps the forward free of
+    host synchronisation.
+
     Returns:
         (B,) log-likelihoods
     """
     if transition is None or initial is None:
         raise RuntimeError('log_likelihood needs a transition matrix and an initial distribution')
-    return _LogLikelihood.apply(observation, batch_frames, transition, initial)
+    _check_route(route)
+    return _LogLikelihood.apply(observation, batch_frames, transition, initial, route)

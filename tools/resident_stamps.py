@@ -48,6 +48,14 @@ print(f'rc {rc}; forward {prof[0]:.3f} ms for {n} batches x {T} frames; {tot / s
 for i, name in enumerate(names):
     v = acc[:, :, i].mean() / steps
     print(f'{name:38s} {v:9.0f} ticks/step  {100 * v * steps / tot:5.1f} %')
+if PATH != 'cluster':
+    # per wave of a workgroup (mean over workgroups): when it reaches barrier B (phases 0-4) and how long it waits there --
+    # the spread of finishing times RESIDENT_PRIO is meant to close
+    reach = acc[:, :, :5].sum(axis=2).mean(axis=0) / steps
+    wait = acc[:, :, 5].mean(axis=0) / steps
+    print('reaches barrier B, ticks into the timestep, waves 0-11:', ' '.join(f'{v:.0f}' for v in reach),
+          f'(spread {reach.max() - reach.min():.0f})')
+    print('waits at barrier B, ticks, waves 0-11:                 ', ' '.join(f'{v:.0f}' for v in wait))
 if PATH == 'cluster':
     # (round 5's exchange: self-validating 16-byte pieces, no store drain, no flag -- the load that finds a piece is the hand-off)
     for i, name in zip((8, 10, 11), ('own row slices -> the other members (stores issued)',

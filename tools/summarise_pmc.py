@@ -15,7 +15,8 @@ summary = {k: {c: {'mean_per_dispatch': sum(v) / len(v), 'dispatches': len(v)} f
 meta = {'units': 'FETCH_SIZE / WRITE_SIZE in KiB per dispatch', 'git': os.environ.get('GIT_HASH') or None,
         'command': os.environ.get('PROFILE_CMD') or 'python3 bench.py --full --steps 8 --warmup 8 --no-cpu-baseline --no-secondary '
                                                     '--no-single-call --pipeline 1',
-        'passes': 'one rocprofv3 --kernel-trace --pmc pass per counter group (tools/collect_profiles.sh)'}
+        'passes': os.environ.get('PROFILE_PASSES') or 'one rocprofv3 --kernel-trace --pmc pass per counter group '
+                                                     '(tools/collect_profiles.sh)'}
 try:
     line = json.load(open(os.path.join(out, 'bench_under_trace.json')))
     meta['batches_per_forward_launch'] = int(line['config']['launch_groups'][0])

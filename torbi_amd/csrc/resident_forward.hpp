@@ -361,6 +361,43 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void *base, un
 #define RESIDENT_HORIZON_SLACK 2
 #endif
 
+// RESIDENT_PRIO: wave priorities of the whole-tile form (not CLUSTER, not REPAIR; 0 = none).  Co-resident waves of a SIMD
+// issue by priority, then age: with none set the oldest wave of a SIMD runs ahead, parks at the timestep's second barrier and
+// leaves the youngest to finish alone.  1: every pass sets the wave's priority from the passes it still has in this timestep
+// (>= 6 -> 3, 4-5 -> 2, 2-3 -> 1, <= 1 -> 0), so a wave that lags outranks one that leads and a wave with one pass more than
+// its neighbours is a level ahead of them at the same pass index; 0 from the last pass through the barriers and the
+// write-back.  2: priority 1 for the whole time loop for the waves with the larger pass count, 0 for the others.
+// RESIDENT_PRIO_CAP: the highest level of form 1 (the kernels of the other stream that run inside this launch stay at 0).
+#ifndef RESIDENT_PRIO
+#define RESIDENT_PRIO 1
+#endif
+#ifndef RESIDENT_PRIO_CAP
+#define RESIDENT_PRIO_CAP 3
+#endif
+__device__ __forceinline__ int prio_level(int left) {
+    const int level = left >= 6 ? 3 : left >= 4 ? 2 : left >= 2 ? 1 : 0;
+    return level < RESIDENT_PRIO_CAP ? level : RESIDENT_PRIO_CAP;
+}
+// RESIDENT_DEPTH: entry pairs of posterior reads (two ds_read_b128 each) a wave keeps requested ahead of the pair it
+// evaluates.  2: pairs h + 1 and h + 2, also across a block boundary -- the first TWO pairs of the next block are requested
+// before the termination test decides whether they are needed (that block is loaded, and its entries name rows of the tile,
+// padding included).  Eight more registers: only the instances scan_depth() names take it.
+#ifndef RESIDENT_DEPTH
+#define RESIDENT_DEPTH 1
+#endif
+// RESIDENT_SPLIT_ADDS: the eight adds of an entry pair go to eight temporaries before the four maxima read them (left to
+// itself the compiler funnels a pair's first four candidates through one register, every v_max3 behind its own add)
+#ifndef RESIDENT_SPLIT_ADDS
+#define RESIDENT_SPLIT_ADDS 0
+#endif
+// The instances whose register allocation takes the third pair in flight: at most 168 registers allocated and no more
+// scratch than at depth 1 (tools/kernel_registers.py, profiles/scan_pipeline_kernel_registers.txt).  One seed per item: all
+// but the 8-item form with eleven passes and the cluster form with six; three seeds: the one-pass cluster forms only.
+constexpr int scan_depth(int MAXP, int KR, bool CLUSTER, int NI) {
+    const bool fits = KR == 1 ? !(MAXP == 11 && NI == 8) && !(MAXP == 6 && CLUSTER) : MAXP == 1;
+    return RESIDENT_DEPTH >= 2 && fits ? 2 : 1;
+}
+
 #ifdef RESIDENT_STAMP
 // build-time instrumentation (tools/resident_stamps.py): per-wave cycle sums of the phases of a timestep
 constexpr int kPhases = 12;     // 0..6 timestep phases, 7 extra list blocks, 8..11 cluster: drain, flag wait, slices, barrier
@@ -585,6 +622,14 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     unsigned long long last = __builtin_readcyclecounter();
 #endif
 
+    // RESIDENT_PRIO: passes this wave makes per timestep (wave-uniform).  Not with eleven passes: the levels are made for
+    // eight, and with the extra code the eleven-pass loop is past what the compiler unrolls (pend[] would go to scratch)
+    constexpr int kPrio = (CLUSTER || REPAIR || MAXP > 8) ? 0 : RESIDENT_PRIO;
+    const int npass = __builtin_amdgcn_readfirstlane(wave < nrg ? (nrg - wave + KW - 1) / KW : 0);
+    if constexpr (kPrio == 2) {
+        if (npass > nrg / KW) __builtin_amdgcn_s_setprio(1);
+    }
+
     for (int t = 1; t < fmax; ++t) {
         __syncthreads();      // tile = posterior row t-1, mtop = its largest entries, `top` is empty
         RSTAMP(0);
@@ -623,6 +668,16 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         for (int p = 0; p < MAXP; ++p) {
             const int rg = rg_lo + wave + KW * p + opaque;  // wave-uniform
             if (rg < rg_hi) {
+                if constexpr (kPrio == 1) {
+                    const int left = npass - p;         // this pass included
+                    const int level = prio_level(left);
+                    if (p == 0 || level != prio_level(left + 1)) {
+                        if (level == 3) __builtin_amdgcn_s_setprio(3);
+                        else if (level == 2) __builtin_amdgcn_s_setprio(2);
+                        else if (level == 1) __builtin_amdgcn_s_setprio(1);
+                        else if (p != 0) __builtin_amdgcn_s_setprio(0);
+                    }
+                }
                 const int jj = kRowGroup * rg + jl;
                 const bool jv = jj < S;
                 const int jr = jv ? jj : S - 1;
@@ -681,15 +736,46 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
 #pragma unroll
                     for (int x = 0; x < RESIDENT_EXTRA_VALU; ++x) asm volatile("v_add_f32 %0, %0, %1" : "+v"(dummy[x & 3]) : "v"(d.t0));
 #endif
+                    if (RESIDENT_SPLIT_ADDS) {
+                        float a0 = d.t0 + d.p0.x, a1 = d.t0 + d.p0.y, a2 = d.t0 + d.p0.z, a3 = d.t0 + d.p0.w;
+                        float b0 = d.t1 + d.p1.x, b1 = d.t1 + d.p1.y, b2 = d.t1 + d.p1.z, b3 = d.t1 + d.p1.w;
+                        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
+                        best[0] = fmaxf(fmaxf(best[0], a0), b0);
+                        best[1] = fmaxf(fmaxf(best[1], a1), b1);
+                        best[2] = fmaxf(fmaxf(best[2], a2), b2);
+                        best[3] = fmaxf(fmaxf(best[3], a3), b3);
+                        return;
+                    }
                     best[0] = fmaxf(fmaxf(best[0], d.t0 + d.p0.x), d.t1 + d.p1.x);
                     best[1] = fmaxf(fmaxf(best[1], d.t0 + d.p0.y), d.t1 + d.p1.y);
                     best[2] = fmaxf(fmaxf(best[2], d.t0 + d.p0.z), d.t1 + d.p1.z);
                     best[3] = fmaxf(fmaxf(best[3], d.t0 + d.p0.w), d.t1 + d.p1.w);
                 };
                 PairData ahead;            // PIPE: pair 0 of the block `consume` is about to be called on
+                PairData ahead1;           // ... and its pair 1 (depth 2)
+                constexpr int kDepth = PIPE ? scan_depth(MAXP, KR, CLUSTER, NI) : 1;
                 // all 8 pairs of `blk`; PIPE: pair 0 is already in `ahead`, and pair 0 of `after` is left there
+                // (depth 2: pairs 0 and 1, in `ahead` and `ahead1`)
                 auto consume = [&](const ListBlock<EPL> &blk, const ListBlock<EPL> &after) {
-                    if (PIPE) {
+                    if constexpr (kDepth == 2) {
+                        PairData fresh;
+#define TORBI_STAGE(H_, BLK_)                                                                  \
+                        issue(std::integral_constant<int, (H_ + 2) % 8>(), BLK_, fresh);       \
+                        __builtin_amdgcn_sched_barrier(0);                                     \
+                        math(ahead);                                                           \
+                        __builtin_amdgcn_sched_barrier(0);                                     \
+                        ahead = ahead1;                                                        \
+                        ahead1 = fresh;
+                        TORBI_STAGE(0, blk)
+                        TORBI_STAGE(1, blk)
+                        TORBI_STAGE(2, blk)
+                        TORBI_STAGE(3, blk)
+                        TORBI_STAGE(4, blk)
+                        TORBI_STAGE(5, blk)
+                        TORBI_STAGE(6, after)
+                        TORBI_STAGE(7, after)
+#undef TORBI_STAGE
+                    } else if (PIPE) {
                         PairData other;
 #define TORBI_STAGE(H_, CUR_, NXT_)                                                   \
                         issue(std::integral_constant<int, H_ + 1>(), blk, NXT_);      \
@@ -721,6 +807,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     }
                 };
                 if (PIPE) issue(std::integral_constant<int, 0>(), cur, ahead);
+                if constexpr (kDepth == 2) issue(std::integral_constant<int, 1>(), cur, ahead1);
                 int nblk = 1;                              // wave-uniform
                 consume(cur, nxt);
                 load_list_block(cur, row, 2 * kBlk);
@@ -927,6 +1014,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         publish_top(t);
         RSTAMP(6);
     }
+    if constexpr (kPrio == 2) __builtin_amdgcn_s_setprio(0);
     if constexpr (CLUSTER) {
         if (tid == 0 && smisc[1]) {
             atomicAdd(&grp.stats[127], 1u);     // workgroups that gave up waiting (0 on any sane run)

@@ -3,11 +3,11 @@ forward instance.
 
 Compiles the device code only (hipcc --cuda-device-only -Rpass-analysis=kernel-resource-usage, the flags of
 torbi_amd._lib.build; no GPU needed) and reads the compiler's remarks.  A SIMD of gfx950 has 512 vector registers, handed
-out in steps of 8 per wave.  The headline instance keeps `--waves` (3) of its waves on every SIMD -- one workgroup of twelve
+out in steps of 8 per wave.  The headline instance keeps `--waves` (4) of its waves on every SIMD -- one workgroup of sixteen
 per compute unit, which its LDS tile allows -- so a kernel of another stream gets a wave in only if its own allocation fits
 what those leave, and it has to do without scratch to stay there at any speed.
 
-    python tools/kernel_registers.py [--only REGEX] [--headline REGEX] [--waves 3] > profiles/<name>_kernel_registers.txt
+    python tools/kernel_registers.py [--only REGEX] [--headline REGEX] [--waves 4] > profiles/<name>_kernel_registers.txt
 """
 import argparse
 import os
@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 FILE_REGISTERS = 512        # vector registers of a SIMD (gfx950: unified VGPR + AGPR file, per lane)
 GRANULE = 8                 # allocation step per wave
-HEADLINE = r'resident_forward_kernel<12, 8, true, 1, false, 16, false>'
+HEADLINE = r'resident_forward_kernel<16, 6, true, 1, false, 16, false>'
 
 FIELDS = {
     'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'SGPRs': 'sgprs', 'ScratchSize [bytes/lane]': 'scratch',
@@ -80,7 +80,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--only', default=None, help='print only the kernels whose name matches this regular expression')
     ap.add_argument('--headline', default=re.escape(HEADLINE), help='the forward instance the others have to fit beside')
-    ap.add_argument('--waves', type=int, default=3, help='waves per SIMD the headline instance keeps resident')
+    ap.add_argument('--waves', type=int, default=4, help='waves per SIMD the headline instance keeps resident')
     ap.add_argument('--remarks', default=None, help='read the compiler remarks from this file instead of compiling')
     args = ap.parse_args()
     remarks = open(args.remarks).read() if args.remarks else compile_remarks()

@@ -390,6 +390,14 @@ __device__ __forceinline__ int prio_level(int left) {
 #ifndef RESIDENT_SPLIT_ADDS
 #define RESIDENT_SPLIT_ADDS 0
 #endif
+// RESIDENT_RELOAD_ITEMS: the whole-tile instances of more than twelve waves do not hold their lanes' four item numbers in
+// registers: a pass reads them from the LDS (one ds_read_b128) where it forms its observation addresses and again where it
+// forms its history addresses.  With sixteen waves (four a SIMD) the one-seed instance then takes 111 registers instead of
+// the 128 its launch bound caps it at: 4 x 112 allocated leave 64 of a SIMD's 512 for the other stream's backtrace and
+// preparation kernels, which otherwise wait for the whole forward launch (HISTORY.md).
+#ifndef RESIDENT_RELOAD_ITEMS
+#define RESIDENT_RELOAD_ITEMS 1
+#endif
 // The instances whose register allocation takes the third pair in flight: at most 168 registers allocated and no more
 // scratch than at depth 1 (tools/kernel_registers.py, profiles/scan_pipeline_kernel_registers.txt).  One seed per item: all
 // but the 8-item form with eleven passes and the cluster form with six; three seeds: the one-pass cluster forms only.
@@ -553,9 +561,22 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     const unsigned xbytes = (unsigned)cluster_slot_bytes(S);
     static_assert(kTop <= kMaxTop, "a member publishes at most kMaxTop list entries per item");
     // items of this lane: tile items 4g .. 4g+3; items past the batch read a valid one's observations and store nothing
+    // (RESIDENT_RELOAD_ITEMS: the instances of more than twelve waves read them from `sitem` pass by pass instead)
+    constexpr bool kReloadItems = RESIDENT_RELOAD_ITEMS && KW > 12 && !CLUSTER;
     int ib[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) ib[it] = sitem[4 * g + it];
+    auto items_now = [&](int (&now)[4]) {
+        if constexpr (kReloadItems) {
+            int at = 4 * g;
+            asm volatile("" : "+v"(at));        // (read here, not ahead of the pass and kept)
+            const int4 v = *reinterpret_cast<const int4 *>(sitem + at);
+            now[0] = v.x; now[1] = v.y; now[2] = v.z; now[3] = v.w;
+        } else {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) now[it] = ib[it];
+        }
+    };
 
     float pend[MAXP][4];
     // CLUSTER: the 16-byte pieces of the other members' slices (every row but this member's own), thread by thread
@@ -692,9 +713,11 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                 } else {
                     load_list_block(cur, row, 0);
                     load_list_block(nxt, row, kBlk);
+                    int in[4];
+                    items_now(in);
 #pragma unroll
                     for (int it = 0; it < 4; ++it)
-                        ob[it] = (RESIDENT_ABL & 32) ? 0.5f * it : obs[((size_t)ib[it] * T + t) * S + jr];
+                        ob[it] = (RESIDENT_ABL & 32) ? 0.5f * it : obs[((size_t)in[it] * T + t) * S + jr];
                 }
                 float seedt[4][kR ? kR : 1];
 #pragma unroll
@@ -848,6 +871,8 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                 u64 last4[4];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) last4[it] = top[(4 * g + it) * kTop + kTop - 1];
+                int out[4];
+                items_now(out);
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
 #if RESIDENT_EXTRA_VALU
@@ -856,7 +881,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     const float o = ob[it] + best[it];                     // post'[j] = obs[t,j] + max
                     odd = odd || nonfinite::odd(o);
                     pend[p][it] = o;
-                    if (jv && live[it] && !(RESIDENT_ABL & 8)) hist[((size_t)ib[it] * T + t) * S + jr] = o;
+                    if (jv && live[it] && !(RESIDENT_ABL & 8)) hist[((size_t)out[it] * T + t) * S + jr] = o;
                     const u64 key = top_key(o, jr);
                     if (jv && key > last4[it] && !(RESIDENT_ABL & 16)) top_insert<kTop>(top + (4 * g + it) * kTop, key);
                 }

@@ -1192,10 +1192,33 @@ hipError_t launch_resident_kernel(const resident::Group &grp, const resident::Cl
     return hipGetLastError();
 }
 
+// waves per workgroup of the whole-tile, one-seed, 16-item instance at 73 .. 96 row groups (1153 .. 1536 states).  Twelve
+// waves of eight passes hold 137 registers each, three to a SIMD; sixteen waves of six passes hold 111, FOUR to a SIMD, and
+// still leave 64 of its 512 registers to the other stream's backtrace and preparation (resident_forward.hpp,
+// RESIDENT_RELOAD_ITEMS): a launch group's forward pass 13.6 -> 13.1 ms at 8 x 512 x 200 x 1440 (HISTORY.md).  Taken where
+// the launch's tiles fill more than half the compute units -- the condition under which AUTO picks whole tiles; launches of
+// fewer tiles keep twelve waves.  Fifteen waves (up to 90 row groups: every wave six passes at 1440 states, three waves on
+// one SIMD) measured between the two and are reachable through the switch only.
+// TORBI_HIP_WHOLE_TILE_WAVES=12|15|16 names the instance whatever the tile count (read per launch: the tests switch it); a
+// count that does not cover the launch's row groups is ignored, as is any for three seeds or 8-item tiles.
+#ifndef TORBI_WHOLE_TILE_WAVES
+#define TORBI_WHOLE_TILE_WAVES 16
+#endif
+inline int whole_tile_waves(int nrg, int tiles, int cus) {
+    if (nrg <= 72 || nrg > 96) return 12;
+    int waves = 2 * tiles > cus ? TORBI_WHOLE_TILE_WAVES : 12;
+    if (const char *e = getenv("TORBI_HIP_WHOLE_TILE_WAVES")) {
+        const int asked = atoi(e);
+        if (asked == 12 || asked == 15 || asked == 16) waves = asked;
+    }
+    if (waves == 15 && nrg > 90) waves = 12;       // (fifteen waves x six passes)
+    return waves;
+}
+
 // every workgroup owns a whole tile (resident_forward_kernel without clusters)
 template <int KR, int NI>
 hipError_t launch_whole_tiles(const resident::Group &grp, const resident::Cluster &clu, int tiles, const ResidentWorkspace &w,
-                              const float *init, int S, hipStream_t s) {
+                              const float *init, int S, int cus, hipStream_t s) {
     const int nrg = (S + resident::pass_rows(S) - 1) / resident::pass_rows(S);
     if constexpr (NI != resident::kNI) {       // 8-item tiles (2048 < S <= 4096)
         // (eight waves x 16 passes with 256 registers each measured slower than twelve x 8-11 at 168: 197 against 183 us per
@@ -1204,6 +1227,11 @@ hipError_t launch_whole_tiles(const resident::Group &grp, const resident::Cluste
         return launch_resident_kernel<12, 11, KR, false, NI>(grp, clu, tiles, w, init, S, s);
     } else {
         if (nrg <= 72) return launch_resident_kernel<12, 6, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+        if constexpr (KR == 1) {               // (three seeds spill at 128 registers: they stay on twelve waves)
+            const int waves = whole_tile_waves(nrg, tiles, cus);
+            if (waves == 16) return launch_resident_kernel<16, 6, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+            if (waves == 15) return launch_resident_kernel<15, 6, KR, false, NI>(grp, clu, tiles, w, init, S, s);
+        }
         if (nrg <= 96) return launch_resident_kernel<12, 8, KR, false, NI>(grp, clu, tiles, w, init, S, s);
         return launch_resident_kernel<12, 11, KR, false, NI>(grp, clu, tiles, w, init, S, s);
     }
@@ -1371,7 +1399,7 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
     const bool small = resident::tile_items(S) != resident::kNI;       // 8-item tiles (2048 < S <= 4096)
     e = by_flag(few, [&](auto few_) { return by_flag(small, [&](auto small_) {
         constexpr int KR = decltype(few_)::value ? 1 : 3, NI = decltype(small_)::value ? 8 : resident::kNI;
-        if (R <= 1) return launch_whole_tiles<KR, NI>(grp, clu, tiles, w, init, S, s);
+        if (R <= 1) return launch_whole_tiles<KR, NI>(grp, clu, tiles, w, init, S, cus, s);
         {       // the slots this launch uses start out absent (resident_forward.hpp, cluster_slot_bytes)
             const size_t granules = (size_t)tiles * resident::kSlots * resident::cluster_slot_bytes(S) / 16;
             hipLaunchKernelGGL(resident::absent_kernel, dim3((unsigned)std::min<size_t>((granules + 255) / 256, 2048)), dim3(256),

@@ -464,6 +464,54 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
 int torbi_hip_stream_tile(int B, int S, int device);
 
 /*
+ * (added within ABI 17) The band route of streaming decode: the decoder above, bit for bit (NaN, +-inf and ties included),
+ * for a transition matrix that holds ONE value outside a band -- transition[j][i] == background (bit for bit) unless
+ * j - reach_left <= i <= j + reach_right -- at the cost of the band: W = reach_left + reach_right + 1 candidates per state
+ * and frame plus two scans of the previous row for the candidates outside it (csrc/stream_band.hpp, STREAM.md "Band
+ * route").  The forward keeps each frame's backpointers, so the frontier walk, the forced frames of a decision depth and
+ * the backtrace follow stored pointers and read neither scores nor the matrix: a push is two launches, a flush one.
+ *
+ * State: the same torbi_hip_stream_state_bytes(B, S, capacity) bytes, laid out
+ *     ring    [B][capacity][S] int32  backpointers of the pending frames (frame base + r in slot (base_slot + r) % capacity;
+ *                                     the row of the first pending frame is never read)
+ *     memo    [B][capacity]    int32  as above
+ *     carried [B][S]           fp32   the newest posterior row
+ * A state that grows takes the pointer rows of the pending frames in their new slots, the carried rows and a zeroed memo.
+ * A state belongs to ONE route: the two layouts are not interchangeable.
+ *
+ * torbi_hip_stream_band_covers answers 1 where the route takes a call, else 0, without touching a device: S % 4 == 0,
+ * 64 <= S <= 3072, reach_left, reach_right >= 0, reach_left + reach_right + 4 <= 512 (what torbi_hip_band_reach_over's
+ * callers can be told about a matrix; the rows with their halos and the scans of one stream,
+ * (6 S + 2 (reach_left + reach_right)) * 4 bytes, then fit the 160 KB of LDS with room to spare) and a background that is
+ * neither NaN nor +inf (-inf and every finite value are taken by the same kernels).
+ * torbi_hip_stream_band_tile reports how many streams share one workgroup of a push's forward kernel
+ * (stream_band_forward_kernel<G>: 1, 2 or 4 -- the largest whose LDS, (6 S + 2 (reach_left + reach_right)) * 4 G bytes, fits
+ * 159 KB, halved while there are fewer workgroups than compute units); the choice the push itself makes.  EINVAL /
+ * EUNSUPPORTED for a shape the push turns down; without a usable device it answers for 256 compute units.
+ *
+ * torbi_hip_stream_band_prepare, once per matrix: diagonals_out [W][S] fp32 (torbi_hip_stream_band_diagonals_bytes; 0 for an
+ * argument < 0) receives diag[k][j] = transition[j][j - reach_left + k], and ok_out[0] (int32, device) 1 where every entry
+ * outside the band equals `background` bit for bit, else 0: the caller reads it before it trusts the diagonals.
+ *
+ * torbi_hip_stream_band_push: torbi_hip_stream_push_lag with `diagonals` in place of the two matrices (max_lag = -1: no
+ * bound, forced_out may be NULL); info, indices_out, counts_out (-1: info does not fit, the stream's state and output row
+ * untouched), forced_out and the argument rules as there -- EINVAL, ERANGE (S > 8000), EWORKSPACE, then the entry's own:
+ * EINVAL for a negative reach, EUNSUPPORTED where _covers answers 0.  torbi_hip_stream_band_flush: torbi_hip_stream_flush
+ * on such a state (EUNSUPPORTED for an S the route does not take).  Every argument is checked before any device work.
+ */
+int torbi_hip_stream_band_covers(int B, int S, int reach_left, int reach_right, float background, int device);
+int torbi_hip_stream_band_tile(int B, int S, int reach_left, int reach_right, int device);
+size_t torbi_hip_stream_band_diagonals_bytes(int S, int reach_left, int reach_right);
+int torbi_hip_stream_band_prepare(const float *transition, int S, int reach_left, int reach_right, float background,
+                                  float *diagonals_out, int32_t *ok_out, int device, void *stream);
+int torbi_hip_stream_band_push(const float *observation, int Tc, const int32_t *info, const float *diagonals, const float *initial,
+                               int reach_left, int reach_right, float background, void *state, size_t state_bytes, int capacity,
+                               int32_t *indices_out, int out_capacity, int32_t *counts_out, int max_lag, int32_t *forced_out,
+                               int B, int S, int device, void *stream);
+int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_bytes, int capacity, int32_t *indices_out,
+                                int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+
+/*
  * (ABI 17) Forward-backward: per-frame state posteriors and the sequence log-likelihood of the HMM that
  * torbi_hip_viterbi_decode decodes (torbi_amd/posterior.py, POSTERIOR.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.  For t < F_b:

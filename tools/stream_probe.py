@@ -15,6 +15,9 @@ Every figure of (a)-(c) is the median of --repeats runs with its min and max, de
       state bytes once the bound binds (from push N + 2 on), and the time per push of the first and of the last hundred
       forcing pushes
 --only-single skips the timed batches (a), (b) and (d); the input of (c) stays the same.
+--route auto|dense|band builds every decoder with that route (StreamDecoder(route=...); 'band' only where the matrix has a
+band: case (a) keeps 'auto'); every case reports the route its decoder took and, on the band route, the streams per
+workgroup of its forward kernel.  --half-width W replaces the pitch band of (b), (c), (e): 87.2 gives 175 diagonals, 12 gives 23.
 """
 import argparse
 import json
@@ -44,14 +47,28 @@ def peaked(B, T, S, dev):
     return torch.log_softmax(logits, dim=-1).clamp_(min=math.log(torch.finfo(torch.float32).tiny))
 
 
-def batch_case(obs, trans, init, push, repeats):
+ROUTE = {}            # the `route` argument of every decoder ({}: the constructor's default)
+
+
+def route_of(dec):
+    """{'route': ..., 'streams_per_workgroup': ...} of a decoder."""
+    found = {'route': getattr(dec, 'route', 'dense')}
+    band = getattr(dec, '_band', None)
+    if band is not None:
+        found['reach'] = [band[0], band[1]]
+        found['streams_per_workgroup'] = dec._lib.torbi_hip_stream_band_tile(dec.batch, dec.states, band[0], band[1], 0)
+    return found
+
+
+def batch_case(obs, trans, init, push, repeats, route=None):
     B, T, S = obs.shape
+    route = ROUTE if route is None else route
     dev = obs.device
     frames = torch.full((B,), T, dtype=torch.int32, device=dev)
     stream_s, decode_s, pending_max = [], [], 0
     viterbi.decode(obs, frames, trans, init)                # warm-up (library load, path choice)
     for _ in range(repeats + 1):
-        dec = torbi_amd.StreamDecoder(B, S, trans, init, log_probs=True, gpu=0)
+        dec = torbi_amd.StreamDecoder(B, S, trans, init, log_probs=True, gpu=0, **route)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for t in range(0, T, push):
@@ -69,7 +86,7 @@ def batch_case(obs, trans, init, push, repeats):
     td = [B * T / s for s in decode_s]
     return {'stream_timesteps_per_s': spread(ts), 'decode_timesteps_per_s': spread(td),
             'ratio': spread([a / b for a, b in zip(ts, td)]), 'push_frames': push,
-            'state_bytes_per_stream': dec._state_bytes // B, 'pending_max': pending_max}
+            'state_bytes_per_stream': dec._state_bytes // B, 'pending_max': pending_max, **route_of(dec)}
 
 
 def single_case(one, trans, init, repeats, max_lag=None):
@@ -77,7 +94,8 @@ def single_case(one, trans, init, repeats, max_lag=None):
     S = one.shape[2]
     runs, outputs, forced_pushes = [], [], 0
     for _ in range(repeats):
-        dec = torbi_amd.StreamDecoder(1, S, trans, init, log_probs=True, gpu=0, **({} if max_lag is None else {'max_lag': max_lag}))
+        dec = torbi_amd.StreamDecoder(1, S, trans, init, log_probs=True, gpu=0, **({} if max_lag is None else {'max_lag': max_lag}),
+                                      **ROUTE)
         outputs, forced_pushes = [], 0
         for t in range(20):                                  # warm-up pushes (ring growth)
             outputs.append(dec.push(one[:, t:t + 1])[0])
@@ -93,7 +111,8 @@ def single_case(one, trans, init, repeats, max_lag=None):
         outputs = [o.cpu().numpy() for o in outputs]
         dec.flush()
         runs.append((np.percentile(times, 50) * 1e3, np.percentile(times, 99) * 1e3))
-    return {'p50': spread([r[0] for r in runs]), 'p99': spread([r[1] for r in runs])}, outputs, forced_pushes / len(times)
+    return ({'p50': spread([r[0] for r in runs]), 'p99': spread([r[1] for r in runs]), **route_of(dec)}, outputs,
+            forced_pushes / len(times))
 
 
 def backpointers(seq, trans, init):
@@ -124,7 +143,7 @@ def identity_case(S, pushes, max_lag):
     eye = torch.full((S, S), -math.inf, device=dev).fill_diagonal_(0.)
     flat = torch.full((S,), math.log(1. / S), dtype=torch.float32, device=dev)
     obs = peaked(1, pushes, S, dev)
-    dec = torbi_amd.StreamDecoder(1, S, eye, flat, log_probs=True, gpu=0, max_lag=max_lag)
+    dec = torbi_amd.StreamDecoder(1, S, eye, flat, log_probs=True, gpu=0, max_lag=max_lag, **ROUTE)
     times, capacity, nbytes = [], [], []
     for t in range(pushes):
         torch.cuda.synchronize()
@@ -137,7 +156,7 @@ def identity_case(S, pushes, max_lag):
     first, last = np.array(times[warm:warm + 100]) * 1e3, np.array(times[-100:]) * 1e3      # (both force every push)
     return {'pushes': pushes, 'capacity': [min(capacity[warm:]), max(capacity[warm:])],
             'state_bytes': [min(nbytes[warm:]), max(nbytes[warm:])],
-            'pending': int(dec.pending[0]), 'forced': int(dec.forced[0]),
+            'pending': int(dec.pending[0]), 'forced': int(dec.forced[0]), **route_of(dec),
             'first_hundred_ms': spread(first.tolist()), 'last_hundred_ms': spread(last.tolist())}
 
 
@@ -152,18 +171,24 @@ def main():
     ap.add_argument('--max-lag', type=int, nargs='*', default=[], help='decision depths to measure: cases (e) and (f)')
     ap.add_argument('--identity-pushes', type=int, default=1000)
     ap.add_argument('--only-single', action='store_true', help='skip the timed batches (a), (b), (d)')
+    ap.add_argument('--route', choices=['auto', 'dense', 'band'], default=None, help='StreamDecoder(route=...) of every decoder')
+    ap.add_argument('--half-width', type=float, default=87.2, help='half width of the pitch band of (b), (c), (e)')
     args = ap.parse_args()
+    if args.route is not None:
+        ROUTE['route'] = args.route
     dev = torch.device('cuda:0')
     B, T, S = args.batch, args.frames, args.states
-    result = {'device': torch.cuda.get_device_name(0), 'B': B, 'T': T, 'S': S}
+    result = {'device': torch.cuda.get_device_name(0), 'B': B, 'T': T, 'S': S, 'route_asked': args.route or 'default',
+              'half_width': args.half_width}
 
     _, trans, init = synth.problem(1, 1, S, seed=0)
     trans, init = torch.from_numpy(trans).to(dev), torch.from_numpy(init).to(dev)
     obs = viterbi.fill_synthetic((B, T, S), synth.STREAM_OBSERVATION, seed=0, device=dev)
     if not args.only_single:
-        result['a_dense'] = batch_case(obs, trans, init, args.push, args.repeats)
+        result['a_dense'] = batch_case(obs, trans, init, args.push, args.repeats,      # (a dense matrix has no band to force)
+                                       route={} if args.route == 'band' else None)
     del obs
-    band = torch.from_numpy(synth.banded_transition(S, 87.2)).to(dev)
+    band = torch.from_numpy(synth.banded_transition(S, args.half_width)).to(dev)
     flat = torch.full((S,), math.log(1. / S), dtype=torch.float32, device=dev)
     obs = peaked(B, T, S, dev)
     if not args.only_single:

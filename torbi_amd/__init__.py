@@ -17,7 +17,7 @@ from . import timer
 from .pipeline import DecodePipeline
 from .state import reset as reset_path_state
 from .core import release_job_memory
-from .stream import StreamDecoder
+from .stream import StreamDecoder, stream_route
 from .posterior import (forward_backward, forward_backward_banded, forward_backward_banded_workspace_bytes,
                         forward_backward_workspace_bytes, posterior_route, state_posteriors)
 from .training import (band_counts_to_dense, counts_route, expected_counts, expected_counts_banded_workspace_bytes,
@@ -32,4 +32,4 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'expected_counts', 'expected_counts_workspace_bytes', 'forward_backward_counts', 'log_likelihood',
            'best_paths', 'decode_k_best', 'decode_k_best_workspace_bytes', 'forward_backward_banded',
            'forward_backward_banded_workspace_bytes', 'posterior_route', 'forward_backward_counts_banded',
-           'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route']
+           'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route', 'stream_route']

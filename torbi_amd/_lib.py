@@ -87,6 +87,17 @@ SYMBOLS = {
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
         _c.c_int, _c.c_void_p]),
     'torbi_hip_stream_tile': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_stream_band_covers': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int]),
+    'torbi_hip_stream_band_tile': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_stream_band_diagonals_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_stream_band_prepare': (_c.c_int, [
+        _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_band_push': (_c.c_int, [
+        _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_band_flush': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+        _c.c_void_p]),
     'torbi_hip_forward_backward_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     'torbi_hip_forward_backward': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,

@@ -40,6 +40,7 @@
 #include "band_forward.hpp"
 #include "band_tile_forward.hpp"
 #include "stream.hpp"
+#include "stream_band.hpp"
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
 #include "counts_band.hpp"
@@ -2266,6 +2267,119 @@ int torbi_hip_stream_flush(const int32_t *info, const float *transition, void *s
     hipLaunchKernelGGL(stream::stream_walk_kernel<true>, dim3(B), dim3(stream::kThreads), (size_t)2 * S * sizeof(int32_t),
                        static_cast<hipStream_t>(stream), reinterpret_cast<const stream::Info *>(info), transition, ss.ring,
                        ss.memo, ss.bp, capacity, indices_out, out_capacity, counts_out, 0, S, -1, nullptr);
+    return (int)hipGetLastError();
+}
+
+// ---- streaming decode on a band with one constant outside it (stream_band.hpp) ----
+
+// the band route's view of the same bytes: backpointers [B][capacity][S], memo [B][capacity], the carried rows [B][S]
+struct StreamBandState { int32_t *ring, *memo; float *carried; };
+static StreamBandState stream_band_state(void *state, int B, int S, int capacity) {
+    Scratch a(state);
+    StreamBandState st;
+    st.ring = a.take<int32_t>((size_t)B * capacity * S, 4);
+    st.memo = a.take<int32_t>((size_t)B * capacity, 4);
+    st.carried = a.take<float>((size_t)B * S, 4);
+    return st;
+}
+
+// the shapes and bands the band route takes (no wider than what torbi_hip_band_reach_over's callers ask about)
+static bool stream_band_shape(int S, int reach_left, int reach_right) {
+    return S % 4 == 0 && S >= stream_band::kMinStates && S <= stream_band::kMaxStates && reach_left >= 0 && reach_right >= 0 &&
+           (long long)reach_left + reach_right + 4 <= stream_band::kMaxWindow &&
+           stream_band::lds_bytes(1, S, reach_left, reach_right) <= (size_t)stream_band::kMaxLdsBytes;
+}
+
+int torbi_hip_stream_band_covers(int B, int S, int reach_left, int reach_right, float background, int device) {
+    (void)device;
+    if (B < 1 || !stream_band_shape(S, reach_left, reach_right)) return 0;
+    return background != background || background == INFINITY ? 0 : 1;
+}
+
+// Streams per workgroup of stream_band_forward_kernel<G>: stream_tile's rule with the band kernel's LDS (rows with halos,
+// double-buffered, and the two scans of every stream)
+int torbi_hip_stream_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (!stream_band_shape(S, reach_left, reach_right)) return TORBI_HIP_EUNSUPPORTED;
+    return items_per_workgroup(stream_band::kMaxGroup, B, 1, cu_count(device), [&](int G) {
+        return stream_band::lds_bytes(G, S, reach_left, reach_right) <= (size_t)stream_band::kMaxLdsBytes;
+    });
+}
+
+size_t torbi_hip_stream_band_diagonals_bytes(int S, int reach_left, int reach_right) {
+    if (S < 1 || reach_left < 0 || reach_right < 0) return 0;
+    return ((size_t)reach_left + reach_right + 1) * S * sizeof(float);
+}
+
+int torbi_hip_stream_band_prepare(const float *transition, int S, int reach_left, int reach_right, float background,
+                                  float *diagonals_out, int32_t *ok_out, int device, void *stream) {
+    if (S < 1 || reach_left < 0 || reach_right < 0 || !transition || !diagonals_out || !ok_out) return TORBI_HIP_EINVAL;
+    if (!torbi_hip_stream_band_covers(1, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(stream_band::stream_band_verdict_kernel, dim3(1), dim3(1), 0, st, ok_out);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(stream_band::stream_band_prepare_kernel, dim3(S), dim3(stream_band::kThreads), 0, st, transition,
+                       diagonals_out, ok_out, background, reach_left, reach_right, S);
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_stream_band_push(const float *observation, int Tc, const int32_t *info, const float *diagonals, const float *initial,
+                               int reach_left, int reach_right, float background, void *state, size_t state_bytes, int capacity,
+                               int32_t *indices_out, int out_capacity, int32_t *counts_out, int max_lag, int32_t *forced_out,
+                               int B, int S, int device, void *stream) {
+    // torbi_hip_stream_push_lag's argument rules, the diagonals standing where its matrix stands; then the band's own
+    int code = stream_args_ok(info, diagonals, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    if (Tc < 0 || (Tc > 0 && (!observation || !initial))) return TORBI_HIP_EINVAL;
+    if (max_lag < -1 || (max_lag >= 0 && !forced_out)) return TORBI_HIP_EINVAL;
+    if (reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (!torbi_hip_stream_band_covers(B, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const stream::Info *in = reinterpret_cast<const stream::Info *>(info);
+    const StreamBandState ss = stream_band_state(state, B, S, capacity);
+    int32_t *const ring = ss.ring, *const memo = ss.memo;
+    float *const carried = ss.carried;
+    if (Tc > 0) {
+        const int G = torbi_hip_stream_band_tile(B, S, reach_left, reach_right, device);
+        const int room = capacity < out_capacity ? capacity : out_capacity;
+        const dim3 grid((B + G - 1) / G);
+        const size_t lds = stream_band::lds_bytes(G, S, reach_left, reach_right);
+        hipError_t e = by_value<4, 2, 1>(G, [&](auto g) {
+            auto *kernel = &stream_band::stream_band_forward_kernel<decltype(g)::value>;
+            const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+            if (granted != hipSuccess) return granted;
+            hipLaunchKernelGGL(kernel, grid, dim3(stream_band::kForwardThreads), lds, st, observation, Tc, in, diagonals, initial, background,
+                               reach_left, reach_right, ring, memo, carried, capacity, room, B, S);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return (int)e;
+    }
+    by_flag(max_lag >= 0, [&](auto lag) {
+        hipLaunchKernelGGL((stream_band::stream_band_walk_kernel<false, decltype(lag)::value>), dim3(B), dim3(stream_band::kThreads),
+                           (size_t)2 * S * sizeof(int32_t), st, in, ring, memo, carried, capacity, indices_out, out_capacity,
+                           counts_out, Tc, S, max_lag, forced_out);
+    });
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_bytes, int capacity, int32_t *indices_out,
+                                int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
+    // (the flush reads no matrix: `info` stands in for torbi_hip_stream_flush's)
+    const int code = stream_args_ok(info, info, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    if (S % 4 != 0 || S < stream_band::kMinStates || S > stream_band::kMaxStates) return TORBI_HIP_EUNSUPPORTED;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const StreamBandState ss = stream_band_state(state, B, S, capacity);
+    hipLaunchKernelGGL(stream_band::stream_band_walk_kernel<true>, dim3(B), dim3(stream_band::kThreads),
+                       (size_t)2 * S * sizeof(int32_t), static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const stream::Info *>(info), ss.ring, ss.memo, ss.carried, capacity, indices_out, out_capacity,
+                       counts_out, 0, S, -1, nullptr);
     return (int)hipGetLastError();
 }
 

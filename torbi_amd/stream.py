@@ -6,20 +6,62 @@ c: no later observation can change the path up to c any more.  `push` returns, p
 included).  The HIP route is csrc/stream.hpp behind torbi_hip_stream_* (include/torbi_hip.h); `gpu=None` runs the same
 decoder on the host with torch CPU ops.  STREAM.md has the layout and the kernels.
 
+A matrix that holds ONE value outside a band (the reference's pitch matrix: 175 diagonals of 1440 states) takes the band
+route on the device (csrc/stream_band.hpp behind torbi_hip_stream_band_*; STREAM.md, "Band route"): a frame costs the band
+and two scans, and the backpointers are stored, not recomputed.  `route` chooses; the outputs are the same bits either way.
+
 `max_lag` bounds the delay and the memory (truncated, or fixed-lag, Viterbi): a push leaves at most `max_lag` frames pending
 and returns the older ones along the path that is best at the newest frame (STREAM.md, "Bounded lag").
 """
+import ctypes
 import math
 import operator
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, inputs
+from . import _lib, inputs, viterbi
 
 # ring slots of a new decoder; the ring doubles when a push needs more
 INITIAL_CAPACITY = 16
+
+ROUTES = ('auto', 'dense', 'band')
+
+
+def _band_plan(trans: torch.Tensor, original: torch.Tensor, batch: int, states: int, index: int
+               ) -> Tuple[Optional[Tuple[int, int, float]], str]:
+    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
+    (`original`: the tensor the look is remembered with), else (None, the reason).  The structure is what
+    `viterbi.band_over` answers, the shape what torbi_hip_stream_band_covers takes."""
+    over = viterbi.band_over(trans, original, states)
+    if over is None:
+        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
+                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
+                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or a finite value below every entry of the band)')
+    if not _lib.load().torbi_hip_stream_band_covers(int(batch), states, over[0], over[1], ctypes.c_float(over[2]), index):
+        return None, (f'torbi_hip_stream_band_covers turns down batch={batch}, states={states}, reach {over[0]}/{over[1]}, '
+                      f'background {over[2]}')
+    return over, ''
+
+
+def stream_route(transition: Optional[torch.Tensor], batch: int, states: int, gpu: Optional[int] = 0,
+                 log_probs: bool = False) -> str:
+    """The route `StreamDecoder(batch, states, transition, log_probs=log_probs, gpu=gpu, route='auto')` takes: 'band' (one
+    value outside a band the band kernels cover), 'dense', or 'host' for `gpu=None`.  `transition=None` is asked about as
+    the constant matrix it stands for."""
+    if gpu is None:
+        return 'host'
+    states = int(states)
+    if transition is not None and tuple(transition.shape) != (states, states):
+        raise ValueError(f'transition must be ({states}, {states})')
+    device = inputs._compute_device(gpu)
+    original = transition
+    transition, uniform, _ = inputs.model(transition, None, log_probs, states, device)
+    if transition is None:
+        original = transition = torch.full((states, states), uniform, dtype=torch.float32, device=device)
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    return 'dense' if _band_plan(trans, original, batch, states, device.index or 0)[0] is None else 'band'
 
 
 class StreamDecoder:
@@ -47,13 +89,23 @@ class StreamDecoder:
         dec = StreamDecoder(batch, states, transition, initial)
         out = dec.push(observation)       # (batch, Tc, states) -> `batch` int32 tensors, the frames decided by this push
         rest = dec.flush()                # the remaining frames of every stream; the streams start afresh
+
+    `route` ('auto', 'dense' or 'band'; ignored with `gpu=None`): which device route the decoder takes.  'band' is the
+    band route for a matrix that holds one value outside a band (`viterbi.band_over` finds the band,
+    torbi_hip_stream_band_covers says whether the kernels take it, and the constructor extracts the diagonals from a private
+    copy of the matrix and reads the device's verdict on it back once); it raises RuntimeError, naming the reason, where
+    any of these says no.  'auto' takes the band route where all of them say yes and the dense route otherwise
+    (`torbi_amd.stream_route` answers which); 'dense' is the route for any matrix.  `dec.route` tells: 'band', 'dense' or
+    'host'.  Outputs, `pending`, `forced` and the memory per pending frame are the same on every route, bit for bit.
     """
 
     def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
                  initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0,
-                 max_lag: Optional[int] = None):
+                 max_lag: Optional[int] = None, route: str = 'auto'):
         if batch < 1 or states < 1:
             raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
+        if route not in ROUTES:
+            raise ValueError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
         if max_lag is not None:
             try:
                 if isinstance(max_lag, bool):
@@ -68,9 +120,10 @@ class StreamDecoder:
         S = self.states
         self.device = inputs._compute_device(gpu)
         # the model of from_probabilities (torbi_amd/inputs.py): chunking cannot change a bit
+        original = transition
         transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
         if transition is None:
-            transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
+            original = transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
         self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
         self.transition = transition.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(self.transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
@@ -82,9 +135,13 @@ class StreamDecoder:
             self._rows = [[] for _ in range(self.batch)]            # posterior rows of frames base-1 .. n-1 (host)
             self._memo = [{} for _ in range(self.batch)]            # frame -> survivor-set size of an earlier walk
             self._held = 0                                          # most rows any stream has held
+            self.route = 'host'
         else:
             self._lib = _lib.load()
-            self._transposed = self.transition.t().contiguous()
+            self._band = None if route == 'dense' else self._prepare_band(original, route == 'band')
+            self.route = 'dense' if self._band is None else 'band'
+            if self._band is None:
+                self._transposed = self.transition.t().contiguous()
             self._capacity = 0
             self._state = None
             self._grow(INITIAL_CAPACITY)
@@ -234,9 +291,33 @@ class StreamDecoder:
         return out
 
     # ------------------------------------------------------------------ HIP route
+    def _prepare_band(self, original: torch.Tensor, must: bool):
+        """(reach_left, reach_right, background, diagonals) where the band route takes the decoder's matrix, else None --
+        or, with `must`, a RuntimeError that names the reason.  The diagonals come from a private copy of the matrix, so that
+        the look, the extraction and the device's verdict all speak of the same values whatever the caller later writes."""
+        index = self.device.index or 0
+        over, reason = _band_plan(self.transition, original, self.batch, self.states, index)
+        if over is not None:
+            left, right, background = over
+            private = self.transition.clone()
+            diagonals = torch.empty(self._lib.torbi_hip_stream_band_diagonals_bytes(self.states, left, right) // 4,
+                                    dtype=torch.float32, device=self.device)
+            ok = torch.empty(1, dtype=torch.int32, device=self.device)
+            _, index, stream = _lib.launch(self.device)
+            _lib.check(self._lib.torbi_hip_stream_band_prepare(private.data_ptr(), self.states, left, right,
+                                                               ctypes.c_float(background), diagonals.data_ptr(), ok.data_ptr(),
+                                                               index, stream), 'torbi_hip_stream_band_prepare')
+            if int(ok.item()) == 1:                             # (the one read-back of the constructor)
+                return left, right, background, diagonals
+            reason = f'an entry outside the band of reach {left}/{right} differs from the background {background}'
+        if must:
+            raise RuntimeError(f"StreamDecoder(route='band'): {reason}")
+        return None
+
     def _grow(self, capacity: int) -> None:
         """Ring of `capacity` slots (at least double the old one); pending rows and the newest row move to their new
-        slots by one device copy, the walk memo starts empty."""
+        slots by one device copy, the walk memo starts empty.  On the band route the rows are the pending frames' pointer
+        rows (moved through an int32 view) and the newest row is the carried row behind the memo."""
         B, S = self.batch, self.states
         capacity = max(int(capacity), 2 * self._capacity)
         capacity = 1 << (capacity - 1).bit_length()
@@ -246,7 +327,16 @@ class StreamDecoder:
         state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         ring = state[:B * capacity * S * 4].view(torch.float32).view(B, capacity, S)
         state[B * capacity * S * 4:B * capacity * (S + 1) * 4].zero_()
-        if self._state is not None:
+        if self._state is not None and self._band is not None:
+            old = self._state[:B * self._capacity * S * 4].view(torch.int32).view(B, self._capacity, S)
+            items = [np.full(int(self._frames[b] - self._base[b]), b, dtype=np.int64) for b in range(B)]
+            frames = [np.arange(int(self._base[b]), int(self._frames[b]), dtype=np.int64) for b in range(B)]
+            bi = torch.from_numpy(np.concatenate(items)).to(self.device)
+            fr = torch.from_numpy(np.concatenate(frames)).to(self.device)
+            if bi.numel():
+                ring.view(torch.int32)[bi, fr % capacity] = old[bi, fr % self._capacity]
+            state[B * capacity * (S + 1) * 4:nbytes] = self._state[B * self._capacity * (S + 1) * 4:self._state_bytes]
+        elif self._state is not None:
             items, frames = [], []
             for b in range(B):
                 n = int(self._frames[b])
@@ -286,7 +376,20 @@ class StreamDecoder:
         out = torch.empty((B, max(1, need)), dtype=torch.int32, device=self.device)
         _, index, stream = _lib.launch(self.device)
         Tc = int(obs.shape[1])
-        if self.max_lag is None:
+        if self._band is not None:
+            left, right, background, diagonals = self._band
+            lag = self.max_lag is not None
+            counts = torch.empty((2, B) if lag else (B,), dtype=torch.int32, device=self.device)
+            _lib.check(self._lib.torbi_hip_stream_band_push(
+                obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), diagonals.data_ptr(), self.initial.data_ptr(), left, right,
+                ctypes.c_float(background), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+                counts.data_ptr(), min(self.max_lag, 2 ** 31 - 1) if lag else -1, counts[1].data_ptr() if lag else None,
+                B, S, index, stream), 'torbi_hip_stream_band_push')
+            got = self._results(out, counts, 'torbi_hip_stream_band_push')
+            if lag:
+                got, forced = got
+                self._forced += forced
+        elif self.max_lag is None:
             counts = torch.empty(B, dtype=torch.int32, device=self.device)
             _lib.check(self._lib.torbi_hip_stream_push(
                 obs.data_ptr() if Tc > 0 else None, Tc, info.data_ptr(), self.transition.data_ptr(), self._transposed.data_ptr(),
@@ -315,9 +418,14 @@ class StreamDecoder:
         out = torch.empty((B, max(1, int(pending.max()))), dtype=torch.int32, device=self.device)
         counts = torch.empty(B, dtype=torch.int32, device=self.device)
         _, index, stream = _lib.launch(self.device)
-        _lib.check(self._lib.torbi_hip_stream_flush(
-            info.data_ptr(), self.transition.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity,
-            out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, index, stream),
-            'torbi_hip_stream_flush')
+        if self._band is not None:
+            _lib.check(self._lib.torbi_hip_stream_band_flush(
+                info.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+                counts.data_ptr(), B, S, index, stream), 'torbi_hip_stream_band_flush')
+        else:
+            _lib.check(self._lib.torbi_hip_stream_flush(
+                info.data_ptr(), self.transition.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity,
+                out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, index, stream),
+                'torbi_hip_stream_flush')
         got = self._results(out, counts, 'torbi_hip_stream_flush')
         return {k: out[k, :got[k]] for k in items}

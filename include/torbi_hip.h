@@ -646,6 +646,35 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
                              const float *initial, int32_t *indices_out, float *scores_out, void *workspace,
                              size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream);
 
+/*
+ * The band route of k-best decoding (added within ABI 17): torbi_hip_k_best's indices and scores, bit for bit, for a matrix
+ * with transition[j][i] == `background` (bit for bit; -inf or finite) wherever i < j - reach_left or i > j + reach_right, at
+ * the cost of the band (csrc/k_best_band.hpp, KBEST.md "Band route").  State j builds its list from its in-band prev-states;
+ * where the list is full and its k-th value is strictly greater than the largest out-of-band candidate any state could
+ * see, fl(max_i L(i)[0] + background), it is the answer, otherwise the state repeats the scan over all S prev-states.
+ * Every frame of a call runs in one launch, G items per workgroup.
+ *
+ * torbi_hip_k_best_band_covers answers 1 where the route takes a call, else 0, without touching a device: S % 4 == 0,
+ * 64 <= S <= 3072, reach_left + reach_right + 4 <= 512 (what torbi_hip_band_reach_over's callers ask about), 1 <= k <= 32,
+ * the two list buffers of one item within the LDS -- 8 k (S + reach_left + reach_right) <= 159 * 1024 bytes (k <= 12 at
+ * 1440 states and reach 87 / 87) --, and a background that is neither NaN nor +inf.
+ * G = min(4, 16 / KMAX) (KMAX: k rounded up to a power of two), halved while 8 G k (S + reach_left + reach_right) exceeds
+ * 159 * 1024 and then while ceil(B / G) < 256.
+ *
+ * torbi_hip_k_best_band_workspace_bytes: torbi_hip_k_best_workspace_bytes's layout with the diagonals,
+ * (reach_left + reach_right + 1) * S floats, in place of the transposed matrix, and one verdict word.
+ *
+ * torbi_hip_k_best_band: arguments as torbi_hip_k_best plus the band.  The promise about the entries outside the band is
+ * checked on the device and nothing is read back: where it is broken every item gets NaN scores and -1 indices.
+ * EINVAL for a negative reach (and torbi_hip_k_best's cases), EUNSUPPORTED where _covers answers 0.  No host
+ * synchronisation and no allocation: a call can be captured into a graph.
+ */
+int torbi_hip_k_best_band_covers(int B, int T, int S, int k, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_k_best_band_workspace_bytes(int B, int T, int S, int k, int reach_left, int reach_right);
+int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                          int reach_left, int reach_right, float background, int32_t *indices_out, float *scores_out,
+                          void *workspace, size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

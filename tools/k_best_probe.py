@@ -3,7 +3,10 @@
 Cases (timesteps/s = B * T / seconds per call):
   dense_k{1,4,16}     B=512, T=500, S=1440, dense synthetic matrix (synth.problem's streams, filled on the device)
   uniform_k{1,4,16}   the same observation, transition=None (uniform route)
-  band_tiny_k4        synth.banded_transition(1440, 87.2, tiny=True): the matrix the reference's evaluation decodes
+  band_{inf,tiny}_k{1,4,8}, band23_{inf,tiny}_k{1,4,8}   (--band-ks) the same observation on banded_transition(1440, 87.2)
+                      (175 diagonals; with tiny the matrix the reference's evaluation decodes) and banded_transition(1440, 12)
+                      (23 diagonals), -inf or log(tiny) outside the band; each holds {'dense': ..., 'band': ...}, the two
+                      device routes (--routes) on the same input.  Every other case runs route='dense'.
   small_states_k4     B=4096, T=500, S=64, dense
   decode              torbi_amd.decode on the dense case, for scale
 Every call owns its workspace; each time is taken from device events around one call after --warmup calls, and reported
@@ -38,11 +41,14 @@ def timed(fn, warmup, repeats):
     return {'median': float(np.median(ms)), 'min': float(ms[0]), 'max': float(ms[-1]), 'runs': len(ms)}
 
 
-def case(obs, frames, trans, init, k, warmup, repeats):
+def case(obs, frames, trans, init, k, warmup, repeats, route='dense'):
     B, T, S = obs.shape
-    ws = torch.empty(torbi_amd.decode_k_best_workspace_bytes(B, T, 1 if trans is None else S, k), dtype=torch.uint8,
-                     device=obs.device)
-    t = timed(lambda: torbi_amd.decode_k_best(obs, frames, trans, init, k, workspace=ws), warmup, repeats)
+    need = torbi_amd.decode_k_best_workspace_bytes(B, T, 1 if trans is None else S, k)
+    if route == 'band':
+        left, right, _ = viterbi.band_over(trans, trans, S)
+        need = torbi_amd.decode_k_best_banded_workspace_bytes(B, T, S, k, left, right)
+    ws = torch.empty(need, dtype=torch.uint8, device=obs.device)
+    t = timed(lambda: torbi_amd.decode_k_best(obs, frames, trans, init, k, workspace=ws, route=route), warmup, repeats)
     out = {'shape': [B, T, S], 'k': k, 'ms': t, 'timesteps_per_s': B * T / (t['median'] * 1e-3),
            'workspace_bytes': ws.numel()}
     del ws
@@ -57,6 +63,8 @@ def main():
     ap.add_argument('--B', type=int, default=512)
     ap.add_argument('--T', type=int, default=500)
     ap.add_argument('--ks', default='1,4,16')
+    ap.add_argument('--band-ks', default='1,4,8')
+    ap.add_argument('--routes', default='dense,band')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     B, T, S = args.B, args.T, 1440
@@ -72,8 +80,13 @@ def main():
         out[f'dense_k{k}'] = case(obs, frames, trans, init, k, args.warmup, args.repeats)
     for k in ks:
         out[f'uniform_k{k}'] = case(obs, frames, None, init, k, args.warmup, args.repeats)
-    band = torch.from_numpy(synth.banded_transition(S, 87.2, tiny=True)).to(dev)
-    out['band_tiny_k4'] = case(obs, frames, band, init, 4, args.warmup, args.repeats)
+    for width, half in (('band', 87.2), ('band23', 12)):
+        for name, tiny in (('inf', False), ('tiny', True)):
+            band = torch.from_numpy(synth.banded_transition(S, half, tiny=tiny)).to(dev)
+            for k in [int(k) for k in args.band_ks.split(',') if k]:
+                out[f'{width}_{name}_k{k}'] = {route: case(obs, frames, band, init, k, args.warmup, args.repeats, route)
+                                               for route in args.routes.split(',')}
+            del band
     del obs
     torch.cuda.empty_cache()
     Bs, Ss = 4096, 64

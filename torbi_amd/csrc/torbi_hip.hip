@@ -46,6 +46,7 @@
 #include "counts_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
+#include "k_best_band.hpp"
 
 namespace {
 
@@ -2794,6 +2795,81 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(kb::kb_walk_kernel<true>, dim3(B), dim3(64), 0, st, batch_frames, ptrs, fin, count, flag, indices_out,
                        scores_out, T, S, k);
+    return (int)hipGetLastError();
+}
+
+// ---- k-best decoding on a band with one constant outside it (k_best_band.hpp) ----
+
+int torbi_hip_k_best_band_covers(int B, int T, int S, int k, int reach_left, int reach_right, float background, int device) {
+    (void)device;
+    if (B < 1 || T < 1 || k < 1 || k > kb::kMaxK || reach_left < 0 || reach_right < 0) return 0;
+    if (S % 4 != 0 || S < kbb::kMinStates || S > kbb::kMaxStates || (long long)reach_left + reach_right + 4 > kbb::kMaxWindow)
+        return 0;
+    if (kbb::lds_bytes(1, S, k, reach_left, reach_right) > (size_t)kbb::kMaxLdsBytes) return 0;
+    return background != background || background == INFINITY ? 0 : 1;
+}
+
+size_t torbi_hip_k_best_band_workspace_bytes(int B, int T, int S, int k, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > kb::kMaxStates || k < 1 || k > kb::kMaxK || reach_left < 0 || reach_right < 0 ||
+        (long long)reach_left + reach_right + 4 > kbb::kMaxWindow)
+        return 256;
+    return kbb::layout(nullptr, B, T, S, k, reach_left, reach_right).total;
+}
+
+// Items per workgroup of kb_band_forward_kernel<KMAX, G>: from min(4, 16 / KMAX) (G * KMAX <= 16 list entries per thread),
+// halved while the lists of G items do not fit the LDS, then while the launch has fewer than kbb::kWorkgroups workgroups.
+// The rule reads the shape, k and the band only, not the device.
+static int kb_band_items(int B, int S, int k, int KMAX, int reach_left, int reach_right) {
+    return items_per_workgroup(std::min(kbb::kMaxGroup, std::max(1, 16 / KMAX)), B, 1, kbb::kWorkgroups, [&](int g) {
+        return kbb::lds_bytes(g, S, k, reach_left, reach_right) <= (size_t)kbb::kMaxLdsBytes;
+    });
+}
+
+int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                          int reach_left, int reach_right, float background, int32_t *indices_out, float *scores_out,
+                          void *workspace, size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream) {
+    if (B < 0 || T < 1 || S < 1 || k < 1 || k > kb::kMaxK || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !indices_out || !scores_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (!torbi_hip_k_best_band_covers(B, T, S, k, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    if ((size_t)B * T * S > (size_t)1 << 40 || (size_t)B * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
+    if (workspace_bytes < torbi_hip_k_best_band_workspace_bytes(B, T, S, k, reach_left, reach_right)) return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const kbb::Layout l = kbb::layout(fb_base(workspace), B, T, S, k, reach_left, reach_right);
+    hipError_t e;
+    if ((e = hipMemsetAsync(l.flag, 0, sizeof(int32_t), st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(stream_band::stream_band_verdict_kernel, dim3(1), dim3(1), 0, st, l.ok);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kbb::kb_band_prepare_kernel, dim3(S), dim3(kbb::kPrepareThreads), 0, st, transition, l.diag, l.ok, l.flag,
+                       background, reach_left, reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    int KMAX = 1;
+    while (KMAX < k) KMAX *= 2;
+    const int G = kb_band_items(B, S, k, KMAX, reach_left, reach_right);
+    const size_t lds = kbb::lds_bytes(G, S, k, reach_left, reach_right);
+    const dim3 grid((B + G - 1) / G), block(kbb::forward_threads(S));
+    e = by_value<1, 2, 4, 8, 16, 32>(KMAX, [&](auto kmax) { return by_value<4, 2, 1>(G, [&](auto g) {
+        // (an instance <KMAX, G> exists only while G * KMAX <= 16; kb_band_items never exceeds that, so the clamp only keeps
+        // the other pairs of the two lists from being compiled)
+        constexpr int KM = decltype(kmax)::value, GI = decltype(g)::value * KM <= 16 ? decltype(g)::value : 1;
+        auto *kernel = &kbb::kb_band_forward_kernel<KM, GI>;
+        const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+        if (granted != hipSuccess) return granted;
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, l.diag, initial, background, reach_left,
+                           reach_right, l.vals, l.ptrs, B, T, S, k);
+        return hipGetLastError();
+    }); });
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_final_kernel, dim3(B), dim3(kb::kThreads), 0, st, observation, batch_frames, initial, l.vals,
+                       l.final_, l.count, l.flag, B, T, S, k);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kbb::kb_band_verdict_kernel, dim3((B + 255) / 256), dim3(256), 0, st, l.ok, l.count, l.flag, B);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kb::kb_walk_kernel<false>, dim3(B), dim3(64), 0, st, batch_frames, l.ptrs, l.final_, l.count, l.flag,
+                       indices_out, scores_out, T, S, k);
     return (int)hipGetLastError();
 }
 

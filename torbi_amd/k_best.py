@@ -12,6 +12,11 @@ indexed [next, prev]:
 Rank 0 is the existing decoder's path and its score the maximum of the decoder's last posterior row.  The HIP route is
 csrc/k_best.hpp behind torbi_hip_k_best / _uniform (include/torbi_hip.h); `gpu=None` and host tensors run the same
 recurrence with torch CPU ops.  KBEST.md has the contract, the kernels and the numbers.
+
+A matrix that holds ONE value outside a band (the reference's pitch matrix: 175 diagonals of 1440 states) takes the band
+route on the device (csrc/k_best_band.hpp behind torbi_hip_k_best_band*; KBEST.md, "Band route"): every frame in one
+launch, a state's list from its in-band prev-states unless an out-of-band candidate could enter it.  `route` chooses; the
+outputs are the same bits either way.
 """
 import ctypes
 import math
@@ -19,9 +24,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs
+from . import _lib, inputs, state, viterbi
 
 MAX_K = 32
+ROUTES = ('auto', 'dense', 'band')
 # candidates per chunk of next-states on the host route (4-byte values, 8-byte sort indices)
 _HOST_CHUNK_ELEMENTS = 1 << 25
 
@@ -39,8 +45,14 @@ def _check_k(k) -> int:
     return k
 
 
+def _check_route(route) -> str:
+    if route not in ROUTES:
+        raise ValueError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+    return route
+
+
 def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: Optional[torch.Tensor],
-                  initial: torch.Tensor, k: int, workspace: Optional[torch.Tensor] = None
+                  initial: torch.Tensor, k: int, workspace: Optional[torch.Tensor] = None, route: str = 'auto'
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """k-best Viterbi decoding on log inputs: the operator level, like `decode`.  Runs on the HIP device of `observation`,
     or on the host for a host tensor.
@@ -53,7 +65,15 @@ def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor
         k: paths per item, 1 <= k <= 32
         workspace: optional uint8 device tensor of >= `decode_k_best_workspace_bytes(B, T, S, k, uniform=transition is
             None)` bytes (a call that owns its workspace allocates nothing else but its outputs, so it can be captured into
-            a graph)
+            a graph); a call that takes the band route needs `decode_k_best_banded_workspace_bytes` instead, and 'auto'
+            takes that route only where the workspace holds as much
+        route: 'auto', 'dense' or 'band': which device route a given matrix takes.  'band' raises RuntimeError, naming
+            the reason, where the band route cannot take the call.  'auto' here, at the operator level, does what a call
+            that may be captured into a graph can do: it takes the band route only for a matrix whose structure is already
+            known -- `k_best_route`, `best_paths`, a `route='band'` call or `decode` has looked at this tensor version --
+            and never looks itself (a look is a small kernel, a host synchronisation and a first device allocation).
+            The bits are the same on every route.  Ignored on the host; `transition=None` takes the uniform route under
+            'auto' and 'dense', and 'band' raises there too.
 
     Returns:
         (indices (B, k, T) int32, scores (B, k) float32) where the observation lives.  Columns t >= F_b repeat the path's
@@ -61,6 +81,7 @@ def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor
         indices.
     """
     k = _check_k(k)
+    route = _check_route(route)
     if initial is None:
         raise RuntimeError('decode_k_best needs an initial distribution')
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
@@ -69,31 +90,183 @@ def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor
         frames = inputs.frames(batch_frames, B, T, torch.device('cpu'))
         return _host(observation.to(torch.float32), frames, transition, uniform, initial, k)
     frames = inputs.frames(batch_frames, B, T, observation.device)
-    return _run(observation.to(torch.float32).contiguous(), frames, transition, uniform, initial, k, workspace)
+    obs = observation.to(torch.float32).contiguous()
+    return _routed(obs, frames, transition, transition, uniform, initial, k, route, workspace, look=False)
 
 
 def best_paths(observation: torch.Tensor, k: int, batch_frames: Optional[torch.Tensor] = None,
                transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None, log_probs: bool = False,
-               gpu: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               gpu: Optional[int] = None, route: str = 'auto') -> Tuple[torch.Tensor, torch.Tensor]:
     """The k best state sequences of every item and their log scores.
 
     Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
     transition log(1/S)), and the inputs go through the same log() and epsilon round trip (torbi_amd/inputs.py), so rank 0
     is bit for bit the path `from_probabilities` returns.  `gpu` is a HIP device index; None computes on the CPU with the
-    same float32 sums.  The caller's tensors are not written.
+    same float32 sums.  The caller's tensors are not written.  `route` ('auto', 'dense' or 'band') is `decode_k_best`'s:
+    the band route for a matrix that holds one value outside a band, with the same bits; ignored with `gpu=None`;
+    'band' raises RuntimeError where that route cannot take the call, `transition=None` included.
 
     Returns:
         (indices (batch, k, frames) int32, scores (batch, k) float32) on the compute device, as `decode_k_best`.
     """
     k = _check_k(k)
+    route = _check_route(route)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
+    original = transition
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
     obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         return _host(obs, frames, transition, uniform, initial, k)
-    return _run(obs, frames, transition, uniform, initial, k)
+    return _routed(obs, frames, transition, original, uniform, initial, k, route)
+
+
+def decode_k_best_banded_workspace_bytes(B: int, T: int, S: int, k: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `decode_k_best_banded` needs: `decode_k_best_workspace_bytes`'s layout with the
+    (reach_left + reach_right + 1) * S diagonals in place of the transposed matrix, and a verdict word."""
+    return int(_lib.load().torbi_hip_k_best_band_workspace_bytes(B, T, S, k, int(reach_left), int(reach_right)))
+
+
+def _covered(B, T, S, k, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_k_best_band_covers: the band route takes this shape, k, band and background."""
+    return bool(_lib.load().torbi_hip_k_best_band_covers(B, T, S, k, int(reach_left), int(reach_right),
+                                                         ctypes.c_float(background), index))
+
+
+# (k, diagonals of 1440 states) up to which tools/k_best_probe.py measured the band route faster than the dense one by more
+# than the dense route's spread (KBEST.md, "Band route"): k <= 4 up to 175 diagonals, k <= 8 up to 23; at k = 8 and 175
+# diagonals the band route is the slower one
+_AUTO_BAND = ((4, 175), (8, 23))
+_MEASURED_STATES = 1440
+
+
+def _band_pays(k: int, states: int, reach_left: int, reach_right: int) -> bool:
+    """Where 'auto' takes a covered band: for a (k, width) inside what the probe measured faster, the width as the band's
+    share of the matrix.  Anything beyond -- k above 8, a band that holds more than 175 / 1440 of a row -- is not
+    measured and stays dense."""
+    width = reach_left + reach_right + 1
+    return any(k <= top and width * _MEASURED_STATES <= diagonals * states for top, diagonals in _AUTO_BAND)
+
+
+def _band_plan(trans: torch.Tensor, original: torch.Tensor, B: int, T: int, S: int, k: int, index: int, look: bool = True):
+    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
+    (`original`: the tensor the look is remembered with), else (None, the reason).  The structure is what
+    `viterbi.band_over` answers -- one look per tensor version; an unseen matrix while a stream is capturing has no band --,
+    the shape what torbi_hip_k_best_band_covers takes.  Without `look` only a structure that is already known counts: the
+    look is a small kernel, a host synchronisation and, the first time, a device allocation."""
+    if not look:
+        known = state.peek(original)
+        if known is None or ('band_over', S) not in known:
+            return None, 'the structure of the matrix is not known yet'
+    over = viterbi.band_over(trans, original, S)
+    if over is None:
+        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
+                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
+                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or finite)')
+    if not _covered(B, T, S, k, over[0], over[1], over[2], index):
+        return None, (f'torbi_hip_k_best_band_covers turns down batch={B}, frames={T}, states={S}, k={k}, reach '
+                      f'{over[0]}/{over[1]}, background {over[2]}')
+    return over, ''
+
+
+def _routed(obs, frames, transition, original, uniform, initial, k, route, workspace=None, look=True):
+    """The device call of `decode_k_best` / `best_paths` by `route` (prepared inputs; `original`: the caller's matrix;
+    `look`: whether 'auto' may look at a matrix it has not seen)."""
+    B, T, S = obs.shape
+    if uniform is not None and route == 'band':
+        raise RuntimeError("k-best decoding with route='band': there is no transition matrix (the uniform model), which the "
+                           'uniform route decodes; the band route needs a matrix that holds one value outside a band')
+    if uniform is None and route != 'dense' and B > 0:
+        trans = transition.to(device=obs.device, dtype=torch.float32).contiguous()
+        band, why = _band_plan(trans, original, B, T, S, k, obs.device.index or 0, look or route == 'band')
+        if band is None and route == 'band':
+            raise RuntimeError(f"k-best decoding with route='band': {why}")
+        if band is not None and route == 'auto':
+            fits = workspace is None or workspace.numel() >= decode_k_best_banded_workspace_bytes(B, T, S, k, band[0], band[1])
+            if not fits or not _band_pays(k, S, band[0], band[1]):
+                band = None
+        if band is not None:
+            return _run_band(obs, frames, trans, initial, k, band[0], band[1], band[2], workspace)
+    return _run(obs, frames, transition, uniform, initial, k, workspace)
+
+
+def k_best_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, k: int, gpu: Optional[int] = 0,
+                 log_probs: bool = False) -> str:
+    """The route `best_paths(observation, k, transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
+    (batch, frames, states) observation: 'host' (`gpu=None`), 'uniform' (no matrix), 'band' (one value outside a band the
+    band kernels cover: `decode_k_best_banded`) or 'dense'."""
+    k = _check_k(k)
+    if gpu is None:
+        return 'host'
+    if transition is None:
+        return 'uniform'
+    states = int(states)
+    if tuple(transition.shape) != (states, states):
+        raise ValueError(f'transition must be ({states}, {states})')
+    device = inputs._compute_device(gpu)
+    trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
+    band, _ = _band_plan(trans, transition, int(batch), int(frames), states, k, device.index or 0)
+    return 'band' if band is not None and _band_pays(k, states, band[0], band[1]) else 'dense'
+
+
+def decode_k_best_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                         initial: torch.Tensor, k: int, reach_left: int, reach_right: int, background: float = -math.inf,
+                         workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`decode_k_best` on a HIP device for a matrix that holds ONE value outside a band, at the cost of the band.
+
+    The caller states the band -- transition[j, i] ([next, prev]) with j - reach_left <= i <= j + reach_right -- and
+    promises that every entry outside it equals `background` bit for bit (`viterbi.band_over` answers both for a device
+    matrix).  The call checks the promise on the device without waiting for it: where it is broken, every item gets NaN
+    scores and -1 indices.  Otherwise the result is `decode_k_best`'s, bit for bit.
+
+    Args:
+        observation, batch_frames, transition, initial, k: as `decode_k_best`
+        reach_left, reach_right: the band, >= 0
+        background: the value outside the band, finite or -inf
+        workspace: optional uint8 device tensor of >= `decode_k_best_banded_workspace_bytes(B, T, S, k, reach_left,
+            reach_right)` bytes (then the call allocates nothing but its outputs and can be captured into a graph)
+
+    Raises RuntimeError where the band route does not cover the call (torbi_hip_k_best_band_covers: states % 4 == 0,
+    64 .. 3072 states, reach_left + reach_right + 4 <= 512, 8 k (states + reach_left + reach_right) <= 159 * 1024, a
+    background that is neither NaN nor +inf).
+    """
+    k = _check_k(k)
+    if transition is None or initial is None:
+        raise RuntimeError('decode_k_best_banded needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    if not observation.is_cuda:
+        raise RuntimeError('decode_k_best_banded runs on a HIP device; decode_k_best takes host tensors')
+    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
+    if reach_left < 0 or reach_right < 0:
+        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
+    if B > 0 and not _covered(B, T, S, k, reach_left, reach_right, background):
+        raise RuntimeError(f'decode_k_best_banded does not cover B={B}, T={T}, S={S}, k={k}, reach {reach_left}/{reach_right}, '
+                           f'background {background} (decode_k_best takes any matrix)')
+    frames = inputs.frames(batch_frames, B, T, observation.device)
+    return _run_band(observation.to(torch.float32).contiguous(), frames, transition, initial, k, reach_left, reach_right,
+                     background, workspace)
+
+
+def _run_band(observation, frames, transition, initial, k, reach_left, reach_right, background, workspace=None):
+    """One call of the band route on the device of `observation` (float32, contiguous, log space)."""
+    B, T, S = observation.shape
+    device = observation.device
+    lib = _lib.load()
+    indices = torch.empty((B, k, T), dtype=torch.int32, device=device)
+    scores = torch.empty((B, k), dtype=torch.float32, device=device)
+    if B == 0:
+        return indices, scores
+    need = decode_k_best_banded_workspace_bytes(B, T, S, k, reach_left, reach_right)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
+    init = initial.to(device=device, dtype=torch.float32).contiguous()
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    _lib.check(lib.torbi_hip_k_best_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                                         reach_left, reach_right, ctypes.c_float(background), indices.data_ptr(),
+                                         scores.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, k, index, stream),
+               'torbi_hip_k_best_band')
+    return indices, scores
 
 
 def _run(observation, frames, transition, uniform, initial, k, workspace=None):

@@ -675,6 +675,37 @@ int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames,
                           int reach_left, int reach_right, float background, int32_t *indices_out, float *scores_out,
                           void *workspace, size_t workspace_bytes, int B, int T, int S, int k, int device, void *stream);
 
+/*
+ * Posterior path sampling (added within ABI 17): N whole state sequences per item drawn from P(path | observations) of the
+ * model torbi_hip_viterbi_decode decodes, by forward filtering and backward sampling (torbi_amd/sampling.py, SAMPLING.md).
+ * Inputs as torbi_hip_forward_backward, and uniforms (B, N, T) fp32: draw n of item b reads uniforms[b][n][t] at frame t, as
+ * min(max(u, 0), 1 - 2^-24), NaN as 0.  With a_t the unnormalised filtered rows and E = exp(transition) of that call:
+ *     t = F-1:  w[i] = a_{F-1}[i]                 t < F-1:  w[i] = a_t[i] * E[j_{t+1}][i]
+ *     Z = sum_i w[i];  j_t = the smallest i with (w[0] + ... + w[i]) > u * Z and w[i] > 0; if there is none (rounding), the
+ *     largest i with w[i] > 0
+ * The sums run in a fixed tree that depends on S only; a state of weight exactly 0 is never returned.  A draw's bits depend on
+ * its item's data and its own T uniforms only.  indices_out (B, N, T) int32: columns t >= F_b repeat j_{F-1}.  loglik_out
+ * (B,) fp32: the bits of torbi_hip_forward_backward's L (the same launches).  An item whose L is not finite (-inf: total
+ * probability 0; NaN: it reads a NaN or +inf) has -1 in every column of every draw; so has a draw whose Z at some frame is 0
+ * or not finite (underflow of the product).
+ *
+ * workspace: device scratch (no initialisation) of torbi_hip_sample_workspace_bytes(B, T, S, N, uniform) bytes: with
+ * uniform == 0 the layout of torbi_hip_forward_backward followed by the filter rows (B, T, S) fp32, else (B, T) fp64.  The
+ * filter's launches and one sampler launch (uniform: three launches), no allocation and no host synchronisation: a call can
+ * be captured into a graph.
+ * The uniform entry point takes a matrix whose every entry is `uniform_value`: frames are independent, j_0 ~ softmax(initial
+ * + obs_0), j_t ~ softmax(obs_t) under the same rule with w = exp(x - max x), and L as torbi_hip_forward_backward_uniform.
+ * TORBI_HIP_EINVAL for a null pointer or N outside [1, 4096]; TORBI_HIP_ERANGE as torbi_hip_forward_backward and for
+ * B * N * T > 2^32; TORBI_HIP_EWORKSPACE for a workspace that is too small.  B == 0 returns 0.
+ */
+size_t torbi_hip_sample_workspace_bytes(int B, int T, int S, int N, int uniform);
+int torbi_hip_sample(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                     const float *uniforms, int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                     int B, int T, int S, int N, int device, void *stream);
+int torbi_hip_sample_uniform(const float *observation, const int32_t *batch_frames, float uniform_value, const float *initial,
+                             const float *uniforms, int32_t *indices_out, float *loglik_out, void *workspace,
+                             size_t workspace_bytes, int B, int T, int S, int N, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

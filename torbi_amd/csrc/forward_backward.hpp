@@ -415,7 +415,7 @@ __global__ __launch_bounds__(256) void fb_uniform_loglik_kernel(const int32_t *_
         loglik[b] = (L != L || L == INFINITY) ? NAN : (float)L;
     }
     __syncthreads();
-    if (!bad) return;
+    if (!bad || !post) return;              // (path sampling passes no posterior)
     float *rows = post + (size_t)b * T * S;
     for (size_t e = threadIdx.x; e < (size_t)F * S; e += blockDim.x) rows[e] = NAN;
 }

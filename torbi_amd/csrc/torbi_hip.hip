@@ -47,6 +47,7 @@
 #include "counts.hpp"
 #include "k_best.hpp"
 #include "k_best_band.hpp"
+#include "sample.hpp"
 
 namespace {
 
@@ -2437,6 +2438,34 @@ struct FbCounts {
     float *counts, *initial_counts;
 };
 
+// The forward half of the dense route, shared by forward-backward and path sampling: E = exp(A) and its transpose, the row
+// maxima, the unnormalised filtered rows a_t into `rows` ([B][T][S]; their 32-row partial sums into the workspace) and L.
+static int fb_forward(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                      float *rows, float *loglik_out, const fb::Layout &l, int B, int T, int S, bool vec, int cus,
+                      hipStream_t st) {
+    float *const E = l.E, *const Et = l.Et, *const m = l.m, *const cbuf = l.c, *const partial = l.partial;
+    hipError_t e;
+    {
+        const size_t n = (size_t)fb::padded_rows(S) * fb::padded_states(S);
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(fb::fb_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, E, Et, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    const size_t nrows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_forward_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, m,
+                       rows, partial, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    for (int t = 1; t < T; ++t)
+        if ((e = fb_step<false>(observation, batch_frames, E, m, cbuf, partial, loglik_out, rows, rows, nullptr, t, B, T, S, vec,
+                                cus, st)) != hipSuccess)
+            return (int)e;
+    hipLaunchKernelGGL(fb::fb_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, m, partial, cbuf, loglik_out, T, S);
+    return (int)hipGetLastError();
+}
+
 // The dense route.  With `counts`, one fb_counts_kernel launch for pair t + 1 goes in front of backward step t (the
 // kernels that produce posterior and log-likelihood are the same launches with the same arguments either way).
 static int fb_dense(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
@@ -2450,26 +2479,9 @@ static int fb_dense(const float *observation, const int32_t *batch_frames, const
     const size_t wrow = (size_t)B * fb::padded_states(S);
     const int cus = cu_count(device);
     hipError_t e;
-    {
-        const size_t n = (size_t)fb::padded_rows(S) * fb::padded_states(S);
-        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(fb::fb_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, E, Et, S);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    }
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, m, B, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fb::fb_forward_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, m,
-                       posterior_out, partial, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(posterior_out) & 15) == 0;
-    for (int t = 1; t < T; ++t)
-        if ((e = fb_step<false>(observation, batch_frames, E, m, cbuf, partial, loglik_out, posterior_out, posterior_out,
-                                nullptr, t, B, T, S, vec, cus, st)) != hipSuccess)
-            return (int)e;
-    hipLaunchKernelGGL(fb::fb_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, m, partial, cbuf, loglik_out, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int rc = fb_forward(observation, batch_frames, transition, initial, posterior_out, loglik_out, l, B, T, S, vec, cus, st);
+    if (rc != TORBI_HIP_OK) return rc;
     hipLaunchKernelGGL(fb::fb_backward_last_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, batch_frames, m,
                        cbuf, loglik_out, posterior_out, w, B, T, S);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
@@ -2549,6 +2561,96 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
                        posterior_out, loglik_out, T, S);
+    return (int)hipGetLastError();
+}
+
+// ---- posterior path sampling: forward filtering, backward sampling (sample.hpp) ----
+
+// forward_backward's layout, then the filter rows a_t [B][T][S]
+struct SampleLayout {
+    fb::Layout fb;
+    float *rows;
+    size_t total;
+};
+
+static SampleLayout sample_layout(char *base, int B, int T, int S) {
+    SampleLayout l;
+    l.fb = fb::layout(base, B, T, S);
+    Scratch a(base, l.fb.total - 256);
+    l.rows = a.take<float>((size_t)B * T * S);
+    l.total = a.bytes + 256;                 // (room to align the caller's base)
+    return l;
+}
+
+size_t torbi_hip_sample_workspace_bytes(int B, int T, int S, int N, int uniform) {
+    if (B < 1 || T < 1 || S < 1 || S > fb::kMaxStates || N < 1) return 256;
+    if (uniform) return align_up((size_t)B * T * sizeof(double), 256) + 256;
+    return sample_layout(nullptr, B, T, S).total;
+}
+
+static int sample_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *uniforms,
+                          const void *indices, const void *loglik, const void *ws, size_t ws_bytes, int B, int T, int S, int N,
+                          int uniform) {
+    if (B < 0 || T < 1 || S < 1 || N < 1 || N > sample::kMaxDraws) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!obs || !frames || !matrix || !initial || !uniforms || !indices || !loglik || !ws) return TORBI_HIP_EINVAL;
+    if (!fb_shape_in_range(B, T, S) || (size_t)B * N * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
+    if (ws_bytes < torbi_hip_sample_workspace_bytes(B, T, S, N, uniform)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+int torbi_hip_sample(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                     const float *uniforms, int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                     int B, int T, int S, int N, int device, void *stream) {
+    const int rc = sample_args_ok(observation, batch_frames, transition, initial, uniforms, indices_out, loglik_out, workspace,
+                                  workspace_bytes, B, T, S, N, 0);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const SampleLayout l = sample_layout(fb_base(workspace), B, T, S);
+    const bool vec = S % 4 == 0;             // (the rows are 256-byte aligned in the workspace: fb_dense's rule)
+    const int fwd = fb_forward(observation, batch_frames, transition, initial, l.rows, loglik_out, l.fb, B, T, S, vec,
+                               cu_count(device), st);
+    if (fwd != TORBI_HIP_OK) return fwd;
+    // the HELD instance whose blocks cover S (a block: 256 states with float4 loads, 64 with scalar ones), else STREAMED
+    const int block = vec ? 256 : 64, blocks = (S + block - 1) / block;
+    int NB = 0;
+    if (S <= (vec ? sample::kHeldStates : sample::kHeldStatesScalar))
+        for (NB = 1; NB < blocks; NB *= 2) {}
+    const dim3 grid(B, (N + sample::kWaves - 1) / sample::kWaves);
+    auto launch = [&](auto *kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, l.fb.E, batch_frames, loglik_out, uniforms,
+                           indices_out, T, S, N);
+    };
+    if (vec) by_value<1, 2, 4, 8, 16, 0>(NB, [&](auto nb) { launch(&sample::sample_backward_kernel<true, decltype(nb)::value>); });
+    else by_value<1, 2, 4, 8, 16, 32, 0>(NB, [&](auto nb) { launch(&sample::sample_backward_kernel<false, decltype(nb)::value>); });
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_sample_uniform(const float *observation, const int32_t *batch_frames, float uniform_value, const float *initial,
+                             const float *uniforms, int32_t *indices_out, float *loglik_out, void *workspace,
+                             size_t workspace_bytes, int B, int T, int S, int N, int device, void *stream) {
+    const int rc = sample_args_ok(observation, batch_frames, initial /* (no matrix) */, initial, uniforms, indices_out,
+                                  loglik_out, workspace, workspace_bytes, B, T, S, N, 1);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    double *lse = reinterpret_cast<double *>(fb_base(workspace));
+    const size_t rows = (size_t)B * T;
+    const bool vec = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(observation) | reinterpret_cast<uintptr_t>(initial)) & 15) == 0;
+    by_flag(vec, [&](auto vec_) {
+        auto *kernel = &sample::sample_uniform_rows_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames, initial, uniforms,
+                           indices_out, lse, B, T, S, N);
+    });
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_uniform_loglik_kernel, dim3(B), dim3(256), 0, st, batch_frames, lse, uniform_value,
+                       static_cast<float *>(nullptr), loglik_out, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(sample::sample_mask_kernel, dim3(B), dim3(256), 0, st, loglik_out, indices_out, (size_t)N * T);
     return (int)hipGetLastError();
 }
 

@@ -1,0 +1,220 @@
+"""Posterior path sampling: whole state sequences drawn from P(path | observations) of the HMM that `from_probabilities`
+decodes, by forward filtering and backward sampling.
+
+With a_t the unnormalised filtered rows and E = exp(A) ([next, prev]) of POSTERIOR.md ("Scaled recurrence"), draw n of item
+b reads u = uniforms[b, n, t] and goes from the last frame down:
+
+    t = F-1:      w[i] = a_{F-1}[i]
+    t < F-1:      w[i] = a_t[i] * E[j_{t+1}][i]
+    Z = sum_i w[i];  j_t = the smallest i with (w[0] + ... + w[i]) > u * Z  and  w[i] > 0;
+                     if there is none (rounding): the largest i with w[i] > 0
+
+The HIP route is csrc/sample.hpp behind torbi_hip_sample / _uniform (include/torbi_hip.h): the forward half of
+`forward_backward`, then one launch that draws every path, one wave per draw.  `gpu=None` runs the same rule in float64 with
+torch CPU ops.  SAMPLING.md has the contract, the kernels and the numbers.
+"""
+import ctypes
+import math
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib, inputs, posterior
+
+MAX_DRAWS = 4096
+_MAX_UNIFORM = 1. - 2. ** -24
+
+
+def forward_sample_workspace_bytes(B: int, T: int, S: int, draws: int, uniform: bool = False) -> int:
+    """Bytes of device scratch `forward_sample` needs for a (B, T, S) problem and `draws` paths per item: the layout of
+    `forward_backward` and the filter rows (B, T, S) float32 behind it, or with `uniform` (`transition=None` in
+    `sample_paths`) the (B, T) float64 row sums alone."""
+    return int(_lib.load().torbi_hip_sample_workspace_bytes(B, T, S, int(draws), 1 if uniform else 0))
+
+
+def _check_draws(draws) -> int:
+    if isinstance(draws, bool) or not isinstance(draws, int) or not 1 <= draws <= MAX_DRAWS:
+        raise RuntimeError(f'draws must be an integer in [1, {MAX_DRAWS}]; got {draws!r}')
+    return draws
+
+
+def _check_uniforms(uniforms, B, T, draws=None) -> int:
+    """The number of draws of a (B, draws, T) tensor of uniforms; raises on any other shape."""
+    if uniforms.dim() != 3 or uniforms.shape[0] != B or uniforms.shape[2] != T or (
+            draws is not None and uniforms.shape[1] != draws):
+        raise RuntimeError(f"uniforms must have shape ({B}, {'draws' if draws is None else draws}, {T}); "
+                           f'got {tuple(uniforms.shape)}')
+    return _check_draws(int(uniforms.shape[1]))
+
+
+def _run(observation, frames, transition, uniform, initial, uniforms, workspace=None):
+    """One call of the HIP route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
+    there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    N = _check_uniforms(uniforms, B, T)
+    device = observation.device
+    lib = _lib.load()
+    indices = torch.empty((B, N, T), dtype=torch.int32, device=device)
+    loglik = torch.empty((B,), dtype=torch.float32, device=device)
+    if B == 0:
+        return indices, loglik
+    need = lib.torbi_hip_sample_workspace_bytes(B, T, S, N, 1 if uniform is not None else 0)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
+    init = initial.to(device=device, dtype=torch.float32).contiguous()
+    u = uniforms.to(device=device, dtype=torch.float32).contiguous()
+    tail = (init.data_ptr(), u.data_ptr(), indices.data_ptr(), loglik.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            B, T, S, N, index, stream)
+    if uniform is not None:
+        _lib.check(lib.torbi_hip_sample_uniform(observation.data_ptr(), frames.data_ptr(), ctypes.c_float(uniform), *tail),
+                   'torbi_hip_sample_uniform')
+    else:
+        trans = transition.to(device=device, dtype=torch.float32).contiguous()
+        _lib.check(lib.torbi_hip_sample(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), *tail),
+                   'torbi_hip_sample')
+    return indices, loglik
+
+
+def forward_sample(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                   initial: torch.Tensor, uniforms: torch.Tensor, workspace: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Forward filtering, backward sampling on log inputs, on a HIP device: the operator level, like `forward_backward`.
+
+    Args:
+        observation: (B, T, S) float32 log scores
+        batch_frames: (B,) valid frames per item (clamped to [1, T]); None = all T
+        transition: (S, S) float32 log transition matrix [next, prev]
+        initial: (S,) float32 log initial distribution
+        uniforms: (B, draws, T) float32, 1 <= draws <= 4096: the uniform draw n of item b uses at frame t, read as
+            min(max(u, 0), 1 - 2^-24) and NaN as 0
+        workspace: optional uint8 device tensor of >= `forward_sample_workspace_bytes(B, T, S, draws)` bytes (a call that
+            owns its workspace and its uniforms allocates nothing else but its outputs, so it can be captured into a graph)
+
+    Returns:
+        (indices (B, draws, T) int32, log_likelihood (B,) float32) on the device.  Columns t >= F_b repeat the path's last
+        state; the log-likelihood is `forward_backward`'s, bit for bit.  An item whose log-likelihood is not finite, and a
+        draw whose weights underflow to a sum of 0 at some frame, have -1 in every column.
+    """
+    if transition is None or initial is None:
+        raise RuntimeError('forward_sample needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    _check_uniforms(uniforms, B, T)
+    obs, frames = posterior._operands('forward_sample', observation, batch_frames, transition, initial)
+    return _run(obs, frames, transition, None, initial, uniforms, workspace)
+
+
+def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Optional[torch.Tensor] = None,
+                 transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None, log_probs: bool = False,
+                 gpu: Optional[int] = None, uniforms: Optional[torch.Tensor] = None,
+                 generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`draws` state sequences per item from P(path | observations), and log P(observations) of every item.
+
+    Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
+    transition log(1/S)), and the inputs go through the same log() and epsilon round trip (torbi_amd/inputs.py), so the
+    model is bit for bit the one `from_probabilities` decodes.  `transition=None` draws every frame independently from its
+    softmax.  `gpu` is a HIP device index; None computes in float64 on the CPU.  The caller's tensors are not written.
+
+    uniforms: (batch, draws, frames) float32 -- a draw is a function of its item and its own row of uniforms, so equal
+        uniforms give equal paths.  None: `torch.rand` on the compute device with `generator`.
+
+    Returns:
+        (indices (batch, draws, frames) int32, log_likelihood (batch,) float32) on the compute device.  Columns
+        t >= batch_frames[b] repeat the path's last state.  An item of total probability 0 has log-likelihood -inf, an item
+        that reads a NaN or +inf has NaN; both have -1 in every column of every draw.
+    """
+    draws = _check_draws(draws)
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    if uniforms is not None:
+        _check_uniforms(uniforms, B, T, draws)
+    device = inputs._compute_device(gpu)
+    frames = inputs.frames(batch_frames, B, T, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    obs = inputs.observation(observation, log_probs, device)
+    if uniforms is None:
+        uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)
+    if gpu is None:
+        indices, L = _host(obs, frames, transition, uniform, initial.to(torch.float32), uniforms)
+        return indices.to(torch.int32), L.to(torch.float32)
+    return _run(obs, frames, transition, uniform, initial, uniforms)
+
+
+def _filter(obs, frames, transition, uniform, initial):
+    """The forward recurrence of `posterior._host` in float64: (a (B, T, S) unnormalised filtered rows -- with `uniform`
+    the rows exp(x - max x) --, E (S, S) or None, L (B,), F (B,) int64)."""
+    B, T, S = inputs.check_shapes(obs, frames, transition, initial)
+    o = obs.to(torch.float64)
+    pi = initial.to(torch.float64)
+    F = frames.to(torch.int64).clamp(1, T)
+    valid = torch.arange(T)[None, :] < F[:, None]
+    x = o.clone()
+    x[:, 0] += pi
+    m = torch.amax(x, dim=2)                                                        # NaN propagates
+    m = torch.where(m == -math.inf, torch.zeros_like(m), m)
+    e = torch.exp(x - m[..., None])
+    if uniform is not None:
+        lse = m + torch.log(e.sum(dim=2))
+        lse[:, 1:] += float(uniform)
+        L = torch.where(valid, lse, torch.zeros_like(lse)).sum(dim=1)
+        a, E = e, None
+    else:
+        E = torch.exp(transition.to(torch.float64))                                 # [next, prev]
+        a = torch.zeros((B, T, S), dtype=torch.float64)
+        c = torch.zeros((B, T), dtype=torch.float64)
+        a[:, 0] = e[:, 0]
+        c[:, 0] = a[:, 0].sum(dim=1)
+        for t in range(1, T):
+            u = e[:, t] * (a[:, t - 1] @ E.T)
+            prev = c[:, t - 1, None]
+            a[:, t] = torch.where(prev == 0, u * 0., u / prev)
+            c[:, t] = a[:, t].sum(dim=1)
+        L = torch.where(valid, torch.log(c) + m, torch.zeros_like(m)).sum(dim=1)
+    L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
+    return a, E, L, F
+
+
+def read_uniforms(uniforms: torch.Tensor) -> torch.Tensor:
+    """The uniforms as every route reads them: float32 values clamped to [0, 1 - 2^-24], NaN as 0; float64."""
+    u = uniforms.detach().to('cpu', torch.float32).to(torch.float64)
+    u = torch.where(torch.isnan(u), torch.zeros_like(u), u)
+    return u.clamp(0., _MAX_UNIFORM)
+
+
+def draw(w: torch.Tensor, u: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The draw rule on weights w (..., S) and uniforms u (...): (j (...) int64, ok (...) bool).  ok is False where the sum
+    of the weights is 0 or not finite (j is 0 there)."""
+    P = torch.cumsum(w, dim=-1)
+    Z = P[..., -1]
+    ok = torch.isfinite(Z) & (Z > 0)
+    positive = w > 0
+    over = positive & (P > (u * Z)[..., None])
+    S = w.shape[-1]
+    first = torch.argmax(over.to(torch.int8), dim=-1)
+    last = S - 1 - torch.argmax(positive.flip(-1).to(torch.int8), dim=-1)
+    j = torch.where(over.any(dim=-1), first, last)
+    return torch.where(ok, j, torch.zeros_like(j)), ok
+
+
+def _host(obs, frames, transition, uniform, initial, uniforms):
+    """The float64 route with torch CPU ops: the forward recurrence of `posterior._host`, then the draw rule with cumsum.
+    (indices (B, N, T) int64, L (B,) float64)."""
+    a, E, L, F = _filter(obs, frames, transition, uniform, initial)
+    B, T, S = a.shape
+    u = read_uniforms(uniforms)
+    N = u.shape[1]
+    indices = torch.zeros((B, N, T), dtype=torch.int64)
+    good = torch.isfinite(L)[:, None].expand(B, N).clone()
+    j = torch.zeros((B, N), dtype=torch.int64)
+    for t in range(T - 1, -1, -1):
+        w = a[:, t, None, :].expand(B, N, S)
+        if E is not None and t < T - 1:
+            inner = (t < F - 1)[:, None, None]
+            w = torch.where(inner, w * E[j], w)
+        picked, ok = draw(w, u[:, :, t])
+        active = (t <= F - 1)[:, None]
+        good &= ok | ~active
+        j = torch.where(active, picked, j)
+        indices[:, :, t] = j
+    last = torch.gather(indices, 2, (F - 1)[:, None, None].expand(B, N, 1))
+    indices = torch.where(torch.arange(T)[None, None, :] >= F[:, None, None], last, indices)
+    indices = torch.where(good[..., None], indices, torch.full_like(indices, -1))
+    return indices, L

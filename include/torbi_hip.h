@@ -706,6 +706,30 @@ int torbi_hip_sample_uniform(const float *observation, const int32_t *batch_fram
                              const float *uniforms, int32_t *indices_out, float *loglik_out, void *workspace,
                              size_t workspace_bytes, int B, int T, int S, int N, int device, void *stream);
 
+/*
+ * Posterior path sampling on a band (added within ABI 17): torbi_hip_sample for a transition matrix that holds ONE value
+ * outside a band, at the cost of the band (SAMPLING.md, "Band route").  The band, `background` and the promise about the
+ * entries outside the band are torbi_hip_forward_backward_band's; ebg = exp(background), 0 for -inf.  Frame F-1 draws from
+ * the whole row a_{F-1} as torbi_hip_sample does.  Frame t < F-1, with j = j_{t+1}, lo = max(0, j - reach_left) and
+ * hi = min(S - 1, j + reach_right), applies the same draw rule to the concatenated weights
+ *     [ v[lo] .. v[hi],  ebg * a_t[0] .. ebg * a_t[S-1] ]        v[i] = a_t[i] * max(exp(transition[j][i]) - ebg, 0)
+ * and j_t is the state of the chosen slot; Z = sum_i v[i] + ebg * c_t.  loglik_out: the bits of
+ * torbi_hip_forward_backward_band's L.  Where the promise is broken every L is NaN and every index -1.
+ *
+ * torbi_hip_sample_band_covers: 1 where torbi_hip_forward_backward_band_covers answers 1 and 1 <= N <= 4096; it reads no
+ * device.  torbi_hip_sample_band_workspace_bytes: torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left,
+ * reach_right) plus the filter rows (B, T, S) fp32 on the next 256-byte boundary, whatever N.
+ * TORBI_HIP_EINVAL for a null pointer, a negative reach or N outside [1, 4096]; TORBI_HIP_ERANGE as torbi_hip_sample;
+ * TORBI_HIP_EUNSUPPORTED where _covers answers 0; TORBI_HIP_EWORKSPACE for a workspace that is too small.  B == 0 returns 0.
+ * Five launches, no allocation and no host synchronisation: a call can be captured into a graph.
+ */
+int torbi_hip_sample_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_sample_band_workspace_bytes(int B, int T, int S, int N, int reach_left, int reach_right);
+int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                          int reach_left, int reach_right, float background, const float *uniforms, int32_t *indices_out,
+                          float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int N, int device,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,10 @@
   (c) the uniform route (transition=None) at 512 x T x 1440 with 1 and 16 draws: GB/s (observation and uniforms read,
       indices written) against 8 TB/s, beside forward_backward's uniform route (observation read, posterior written)
   (d) workspace bytes
+  --band: instead of (a) - (d), forward_sample against forward_sample_banded on the pitch matrix (1440 states, half-width 12,
+      -inf and log(tiny) outside the band), alternated call by call in one process on the same inputs, at 512 x T x 1440 with 1
+      and 16 draws, 1 x T x 1440 and 8 x 120 x 1440 with 1 draw (SAMPLING.md, "Band route"); with --trace only the kernel times
+      of one call of each (the sampler launches and the filters), a run of its own
 Every time is the median of --repeats calls with its min and max, device synchronised around each call.
 """
 import argparse
@@ -150,13 +154,63 @@ def uniform_case(B, T, S, draws, repeats, dev):
     return out
 
 
+def band_case(B, T, S, draws, tiny, repeats, dev, trace):
+    obs, _, init = (torch.from_numpy(x).to(dev) for x in synth.problem(B, T, S, seed=1))
+    trans = torch.as_tensor(synth.banded_transition(S, 12, tiny=tiny)).to(dev)
+    frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    background = float(np.log(np.finfo(np.float32).tiny)) if tiny else -float('inf')
+    wd = torch.empty(torbi_amd.forward_sample_workspace_bytes(B, T, S, max(draws)), dtype=torch.uint8, device=dev)
+    wb = torch.empty(torbi_amd.forward_sample_banded_workspace_bytes(B, T, S, max(draws), 11, 11), dtype=torch.uint8, device=dev)
+    out = {'shape': [B, T, S], 'background': 'log(tiny)' if tiny else '-inf', 'workspace_bytes': {'dense': wd.numel(), 'band': wb.numel()}}
+    calls, us = {}, {}
+    for n in draws:
+        us[n] = torch.rand((B, n, T), device=dev, generator=torch.Generator(device=dev).manual_seed(n))
+        calls[f'dense_{n}'] = lambda n=n: torbi_amd.forward_sample(obs, frames, trans, init, us[n], workspace=wd)
+        calls[f'band_{n}'] = lambda n=n: torbi_amd.forward_sample_banded(obs, frames, trans, init, us[n], 11, 11, background,
+                                                                        workspace=wb)
+    if trace:
+        for fn in calls.values():
+            fn()
+        torch.cuda.synchronize()
+        out['kernel_ms'] = {}
+        for n in draws:
+            out['kernel_ms'][f'dense_{n}'] = {'sampler': kernel_ms(calls[f'dense_{n}'], 'sample_backward_kernel')}
+            out['kernel_ms'][f'band_{n}'] = {'sampler': kernel_ms(calls[f'band_{n}'], 'sample_band_backward_kernel'),
+                                             'filter': kernel_ms(calls[f'band_{n}'], 'fb_band_filter_kernel')}
+        return out
+    out['ms'] = alternated(calls, repeats)
+    for n in draws:
+        dense, band = out['ms'][f'dense_{n}'], out['ms'][f'band_{n}']
+        out[f'dense_over_band_{n}'] = dense['median'] / band['median']
+        # faster by more than the spread: the slowest band call against the fastest dense call
+        out[f'band_faster_beyond_spread_{n}'] = band['max'] < dense['min']
+    L = [calls[f'{k}_{draws[0]}']()[1] for k in ('dense', 'band')]
+    out['finite_L'] = bool(torch.isfinite(L[0]).all() and torch.isfinite(L[1]).all())
+    out['max_abs_L_difference'] = float((L[0].double() - L[1].double()).abs().max())
+    return out
+
+
+def band_main(args, dev):
+    out = {'device': torch.cuda.get_device_name(0), 'trace': bool(args.trace)}
+    for tiny in (False, True):
+        form = 'tiny' if tiny else 'inf'
+        out[f'band_512_{form}'] = band_case(512, args.T, 1440, (1, 16), tiny, args.repeats, dev, args.trace)
+        out[f'band_1_{form}'] = band_case(1, args.T, 1440, (1,), tiny, args.repeats, dev, args.trace)
+        out[f'band_8_{form}'] = band_case(8, 120, 1440, (1,), tiny, args.repeats, dev, args.trace)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--band', action='store_true', help='forward_sample against forward_sample_banded on the pitch matrix')
+    ap.add_argument('--trace', action='store_true', help='with --band: kernel times of one call each instead of call times')
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--T', type=int, default=500)
     ap.add_argument('--no-torch', action='store_true', help='skip the per-step torch implementation (b)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
+    if args.band:
+        return band_main(args, dev)
     out = {'device': torch.cuda.get_device_name(0)}
     out['a_dense_512'] = dense_case(512, args.T, 1440, (1, 16), args.repeats, dev, not args.no_torch)
     out['a_dense_1'] = dense_case(1, args.T, 1440, (1,), args.repeats, dev, not args.no_torch)

@@ -25,7 +25,8 @@ from .training import (band_counts_to_dense, counts_route, expected_counts, expe
                        log_likelihood)
 from .k_best import (best_paths, decode_k_best, decode_k_best_banded, decode_k_best_banded_workspace_bytes,
                      decode_k_best_workspace_bytes, k_best_route)
-from .sampling import forward_sample, forward_sample_workspace_bytes, sample_paths
+from .sampling import (forward_sample, forward_sample_banded, forward_sample_banded_workspace_bytes,
+                       forward_sample_workspace_bytes, sample_paths, sample_route)
 
 __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 'workspace_bytes', 'set_forward_path', 'forward_path', 'from_probabilities', 'from_file', 'from_file_to_file',
            'from_files_to_files', 'from_dataloader', 'save', 'save_masked', 'data', 'synth',
@@ -36,4 +37,4 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'forward_backward_banded_workspace_bytes', 'posterior_route', 'forward_backward_counts_banded',
            'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route', 'stream_route', 'decode_k_best_banded',
            'decode_k_best_banded_workspace_bytes', 'k_best_route', 'sample_paths', 'forward_sample',
-           'forward_sample_workspace_bytes']
+           'forward_sample_workspace_bytes', 'forward_sample_banded', 'forward_sample_banded_workspace_bytes', 'sample_route']

@@ -212,7 +212,12 @@ struct Streamed {
 
     template <bool VEC, class W>
     __device__ __forceinline__ int pick(W &&weights, float u, int lane) const {
-        const float target = u * Z;
+        return pick_target<VEC>(weights, u * Z, lane);
+    }
+
+    // the same search against a target the caller formed (sample_band.hpp: the residual behind the band part)
+    template <bool VEC, class W>
+    __device__ __forceinline__ int pick_target(W &&weights, float target, int lane) const {
         int qs = -1;
         float resid = INFINITY;
 #pragma unroll

@@ -48,6 +48,7 @@
 #include "k_best.hpp"
 #include "k_best_band.hpp"
 #include "sample.hpp"
+#include "sample_band.hpp"
 
 namespace {
 
@@ -2798,6 +2799,65 @@ int torbi_hip_forward_backward_counts_band(const float *observation, const int32
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(fbb::fb_band_counts_finalize_kernel, dim3((unsigned)(((size_t)l.W * S + 255) / 256)), dim3(256), 0, st,
                        transition, l.partial, l.flag, band_counts_out, initial_counts_out, grid, l.reach_left, l.W, l.Sd, S);
+    return (int)hipGetLastError();
+}
+
+// ---- posterior path sampling on a band (sample_band.hpp) ----
+
+int torbi_hip_sample_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device) {
+    if (N < 1 || N > sample::kMaxDraws) return 0;
+    return torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device);
+}
+
+size_t torbi_hip_sample_band_workspace_bytes(int B, int T, int S, int N, int reach_left, int reach_right) {
+    (void)N;
+    if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbb::sample_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                          int reach_left, int reach_right, float background, const float *uniforms, int32_t *indices_out,
+                          float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int N, int device,
+                          void *stream) {
+    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0 || N < 1 || N > sample::kMaxDraws) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !uniforms || !indices_out || !loglik_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (!fb_shape_in_range(B, T, S) || (size_t)B * N * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
+    if (!torbi_hip_sample_band_covers(B, T, S, N, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    if (workspace_bytes < torbi_hip_sample_band_workspace_bytes(B, T, S, N, reach_left, reach_right)) return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbb::SampleLayout l = fbb::sample_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    hipError_t e;
+    const size_t cells = (size_t)l.W * l.Sd;
+    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
+                       transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
+                       l.reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int halo = std::max(l.reach_left, l.reach_right);
+    const int G = fb_band_tile(B, S, halo, cu_count(device));            // (fb_band_kernel's tile: the same LDS rows)
+    by_value<8, 4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbb::fb_band_filter_kernel<decltype(g)::value>;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(fbb::kThreads), fbb::lds_bytes(G, S, halo), st, observation,
+                           batch_frames, initial, l.Df, l.m, l.c, l.flag, l.rows, loglik_out, ebg, l.reach_left, l.reach_right,
+                           l.W, l.Sd, B, T, S);
+    });
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const dim3 grid(B, (N + sample::kWaves - 1) / sample::kWaves);
+    by_flag(S % 4 == 0, [&](auto vec_) {          // (the rows are 256-byte aligned in the workspace)
+        auto *kernel = &fbb::sample_band_backward_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, transition, l.c, batch_frames, loglik_out,
+                           uniforms, indices_out, ebg, l.reach_left, l.reach_right, T, S, N);
+    });
     return (int)hipGetLastError();
 }
 

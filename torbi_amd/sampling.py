@@ -10,8 +10,10 @@ b reads u = uniforms[b, n, t] and goes from the last frame down:
                      if there is none (rounding): the largest i with w[i] > 0
 
 The HIP route is csrc/sample.hpp behind torbi_hip_sample / _uniform (include/torbi_hip.h): the forward half of
-`forward_backward`, then one launch that draws every path, one wave per draw.  `gpu=None` runs the same rule in float64 with
-torch CPU ops.  SAMPLING.md has the contract, the kernels and the numbers.
+`forward_backward`, then one launch that draws every path, one wave per draw.  For a matrix that holds one value outside a
+band, csrc/sample_band.hpp behind torbi_hip_sample_band (`forward_sample_banded`, `sample_paths(route=)`) draws at the cost of
+the band.  `gpu=None` runs the dense rule in float64 with torch CPU ops.  SAMPLING.md has the contract, the kernels and the
+numbers.
 """
 import ctypes
 import math
@@ -19,7 +21,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs, posterior
+from . import _lib, inputs, posterior, viterbi
 
 MAX_DRAWS = 4096
 _MAX_UNIFORM = 1. - 2. ** -24
@@ -103,10 +105,139 @@ def forward_sample(observation: torch.Tensor, batch_frames: Optional[torch.Tenso
     return _run(obs, frames, transition, None, initial, uniforms, workspace)
 
 
+def forward_sample_banded_workspace_bytes(B: int, T: int, S: int, draws: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_sample_banded` needs: the layout of `forward_backward_banded` for this band and the
+    filter rows (B, T, S) float32 behind it, whatever `draws`."""
+    return int(_lib.load().torbi_hip_sample_band_workspace_bytes(B, T, S, int(draws), int(reach_left), int(reach_right)))
+
+
+def _covered(B, T, S, N, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_sample_band_covers: the band route takes this shape, number of draws, band and background."""
+    return bool(_lib.load().torbi_hip_sample_band_covers(B, T, S, int(N), int(reach_left), int(reach_right),
+                                                         ctypes.c_float(background), index))
+
+
+def _run_band(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
+    """One call of the band route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
+    there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    N = _check_uniforms(uniforms, B, T)
+    device = observation.device
+    lib = _lib.load()
+    indices = torch.empty((B, N, T), dtype=torch.int32, device=device)
+    loglik = torch.empty((B,), dtype=torch.float32, device=device)
+    if B == 0:
+        return indices, loglik
+    need = lib.torbi_hip_sample_band_workspace_bytes(B, T, S, N, reach_left, reach_right)
+    workspace, index, stream = _lib.launch(device, need, workspace)
+    frames = frames.to(device=device, dtype=torch.int32).contiguous()
+    init = initial.to(device=device, dtype=torch.float32).contiguous()
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    u = uniforms.to(device=device, dtype=torch.float32).contiguous()
+    _lib.check(lib.torbi_hip_sample_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                                         reach_left, reach_right, ctypes.c_float(background), u.data_ptr(),
+                                         indices.data_ptr(), loglik.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                         B, T, S, N, index, stream), 'torbi_hip_sample_band')
+    return indices, loglik
+
+
+def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                          initial: torch.Tensor, uniforms: torch.Tensor, reach_left: int, reach_right: int,
+                          background: float = -math.inf, workspace: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_sample` for a matrix that holds ONE value outside a band, at the cost of the band alone.
+
+    The caller states the band -- transition[j, i] ([next, prev]) with j - reach_left <= i <= j + reach_right -- and
+    promises that every entry outside it equals `background` bit for bit, as for `forward_backward_banded`
+    (`viterbi.band_over` answers both for a device matrix).  The matrix itself is never looked at on the host; the promise
+    is checked on the device without waiting for it: where it is broken, every log-likelihood is NaN and every index -1.
+
+    Args:
+        observation, batch_frames, transition, initial, uniforms: as `forward_sample`
+        reach_left, reach_right: the band, >= 0
+        background: the value outside the band, finite or -inf
+        workspace: optional uint8 device tensor of >= `forward_sample_banded_workspace_bytes(B, T, S, draws, reach_left,
+            reach_right)` bytes (with it and its own uniforms the call allocates nothing but its outputs and can be
+            captured into a graph)
+
+    Returns:
+        (indices (B, draws, T) int32, log_likelihood (B,) float32) on the device, as `forward_sample`; the log-likelihood
+        is `forward_backward_banded`'s, bit for bit.  Each draw is exact for the model (SAMPLING.md, "Band route"); for
+        given uniforms its states are not those of `forward_sample`, which orders the weights of a frame differently.
+
+    Raises where the band route does not cover the call (torbi_hip_sample_band_covers: what `forward_backward_banded`
+    covers, and 1 <= draws <= 4096).
+    """
+    if transition is None or initial is None:
+        raise RuntimeError('forward_sample_banded needs a transition matrix and an initial distribution')
+    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    N = _check_uniforms(uniforms, B, T)
+    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
+    if reach_left < 0 or reach_right < 0:
+        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
+    if B > 0 and not _covered(B, T, S, N, reach_left, reach_right, background):
+        raise RuntimeError(f'forward_sample_banded does not cover B={B}, T={T}, S={S}, draws={N}, reach '
+                           f'{reach_left}/{reach_right}, background {background} (forward_sample takes any matrix)')
+    obs, frames = posterior._operands('forward_sample_banded', observation, batch_frames, transition, initial)
+    return _run_band(obs, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace)
+
+
+# Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row, draws) that
+# tools/sample_probe.py --band measured faster than the dense call by more than the spread of the measurement (SAMPLING.md,
+# "Band route", timing).  Each entry: (smallest batch, largest batch, diagonals of 1440 states, most draws).  Measured, all on
+# 23 diagonals of 1440 states in both forms of the background: 1, 8 and 512 items at one draw (3.5 x, 3.4 x, 5.8 x) and 512
+# items at 16 draws (6.0 x).  Anything outside -- a larger batch, a wider band, more draws -- is not measured and stays dense.
+_AUTO_BAND = ((1, 512, 23, 1), (512, 512, 23, 16))
+_MEASURED_STATES = 1440
+
+
+def _band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
+    width = reach_left + reach_right + 1
+    return any(low <= batch <= high and width * _MEASURED_STATES <= diagonals * states and draws <= most
+               for low, high, diagonals, most in _AUTO_BAND)
+
+
+def _band_plan(trans, original, B, T, S, N, index):
+    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
+    (`original`: the caller's tensor, which the look is remembered with), else (None, the reason).  The structure is what
+    `viterbi.band_over` answers -- one look per tensor version; an unseen matrix while a stream is capturing has no band --,
+    the shape what torbi_hip_sample_band_covers takes."""
+    if B < 1:
+        return None, 'the batch is empty'
+    over = viterbi.band_over(trans, original, S)
+    if over is None:
+        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
+                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
+                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or finite)')
+    if not _covered(B, T, S, N, over[0], over[1], over[2], index):
+        return None, (f'torbi_hip_sample_band_covers turns down batch={B}, frames={T}, states={S}, draws={N}, reach '
+                      f'{over[0]}/{over[1]}, background {over[2]}')
+    return over, ''
+
+
+def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, draws: int = 1, gpu: int = 0,
+                 log_probs: bool = False) -> str:
+    """The route `sample_paths(..., draws, transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
+    (batch, frames, states) observation: 'uniform' (no matrix: independent frames), 'band' (one value outside a band, in a
+    class of batch, band width and draws that was measured faster: `forward_sample_banded`) or 'dense' (`forward_sample`)."""
+    draws = _check_draws(draws)
+    if transition is None:
+        return 'uniform'
+    states = int(states)
+    if tuple(transition.shape) != (states, states):
+        raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
+    device = inputs._compute_device(gpu)
+    if device.type == 'cpu':
+        return 'dense'
+    trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
+    band, _ = _band_plan(trans, transition, int(batch), int(frames), states, draws, device.index or 0)
+    return 'band' if band is not None and _band_pays(int(batch), states, band[0], band[1], draws) else 'dense'
+
+
 def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Optional[torch.Tensor] = None,
                  transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None, log_probs: bool = False,
                  gpu: Optional[int] = None, uniforms: Optional[torch.Tensor] = None,
-                 generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 generator: Optional[torch.Generator] = None, route: str = 'dense') -> Tuple[torch.Tensor, torch.Tensor]:
     """`draws` state sequences per item from P(path | observations), and log P(observations) of every item.
 
     Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
@@ -116,25 +247,51 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
 
     uniforms: (batch, draws, frames) float32 -- a draw is a function of its item and its own row of uniforms, so equal
         uniforms give equal paths.  None: `torch.rand` on the compute device with `generator`.
+    route: which device route a given matrix takes.  'dense' (the default): `forward_sample`, which synchronises nothing and
+        whose draws for given uniforms are part of its behaviour.  'band': `forward_sample_banded` on the band
+        `viterbi.band_over` finds (one look, with a host synchronisation, per tensor version), raising with the reason where
+        the matrix has no covered band.  'auto': the band route where such a band is found, the call is covered and its
+        class of batch, band width and draws was measured faster than the dense route (`sample_route` answers which), else
+        the dense one.  Both routes draw exactly from the model; for given uniforms their draws differ.  Ignored by
+        `transition=None`; `gpu=None` is the float64 dense rule and refuses 'band'.
 
     Returns:
         (indices (batch, draws, frames) int32, log_likelihood (batch,) float32) on the compute device.  Columns
         t >= batch_frames[b] repeat the path's last state.  An item of total probability 0 has log-likelihood -inf, an item
         that reads a NaN or +inf has NaN; both have -1 in every column of every draw.
     """
+    if route not in ('auto', 'dense', 'band'):
+        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
     draws = _check_draws(draws)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     if uniforms is not None:
         _check_uniforms(uniforms, B, T, draws)
+    if route == 'band' and gpu is None:
+        raise RuntimeError("sample_paths(route='band') needs a HIP device: gpu=None is the float64 dense rule")
+    if route == 'band' and transition is None:
+        raise RuntimeError("sample_paths(route='band'): there is no transition matrix (the uniform model draws every frame "
+                           'independently); the band route needs a matrix that holds one value outside a band')
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
+    original = transition
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    if gpu is not None and uniform is None and route != 'dense':
+        # (before the observation is prepared: a matrix without a band raises before anything runs)
+        band, why = _band_plan(transition.to(dtype=torch.float32).contiguous(), original, B, T, S, draws, device.index or 0)
+        if band is None and route == 'band':
+            raise RuntimeError(f"sample_paths(route='band'): {why}")
+        if band is not None and route == 'auto' and not _band_pays(B, S, band[0], band[1], draws):
+            band = None
+    else:
+        band = None
     obs = inputs.observation(observation, log_probs, device)
     if uniforms is None:
         uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)
     if gpu is None:
         indices, L = _host(obs, frames, transition, uniform, initial.to(torch.float32), uniforms)
         return indices.to(torch.int32), L.to(torch.float32)
+    if band is not None:
+        return _run_band(obs, frames, transition, initial, uniforms, band[0], band[1], band[2])
     return _run(obs, frames, transition, uniform, initial, uniforms)
 
 
@@ -216,5 +373,52 @@ def _host(obs, frames, transition, uniform, initial, uniforms):
         indices[:, :, t] = j
     last = torch.gather(indices, 2, (F - 1)[:, None, None].expand(B, N, 1))
     indices = torch.where(torch.arange(T)[None, None, :] >= F[:, None, None], last, indices)
+    indices = torch.where(good[..., None], indices, torch.full_like(indices, -1))
+    return indices, L
+
+
+def _host_banded(obs, frames, transition, initial, uniforms, reach_left, reach_right, background):
+    """The band rule (SAMPLING.md, "Band route") in float64 with torch CPU ops: the forward recurrence of `posterior._host`,
+    frame F-1 by the draw rule over the whole row, and every frame t < F-1 by the same rule over the concatenated weights
+        [ v[j - l] .. v[j + r],  ebg a_t[0] .. ebg a_t[S-1] ]        v[i] = a_t[i] max(E[j][i] - ebg, 0), j = j_{t+1}
+    (slots the matrix clips have weight 0, which the rule never returns).  Where an entry outside the band differs from
+    `background` every L is NaN and every index -1.  (indices (B, N, T) int64, L (B,) float64)."""
+    a, E, L, F = _filter(obs, frames, transition, None, initial)
+    B, T, S = a.shape
+    u = read_uniforms(uniforms)
+    N = u.shape[1]
+    left, right = min(int(reach_left), S - 1), min(int(reach_right), S - 1)
+    W = left + right + 1
+    bg = torch.tensor(float(background), dtype=torch.float32)
+    nxt, prv = torch.arange(S)[:, None], torch.arange(S)[None, :]
+    outside = (prv < nxt - left) | (prv > nxt + right)
+    A32 = transition.detach().to('cpu', torch.float32)
+    if bool((outside & (A32.view(torch.int32) != bg.view(torch.int32))).any()):
+        return torch.full((B, N, T), -1, dtype=torch.int64), torch.full_like(L, math.nan)
+    ebg = float(torch.exp(bg.to(torch.float64)))
+    V = (E - ebg).clamp_min(0.)                                                     # [next, prev]
+    offsets = torch.arange(W) - left
+    indices = torch.zeros((B, N, T), dtype=torch.int64)
+    good = torch.isfinite(L)[:, None].expand(B, N).clone()
+    j = torch.zeros((B, N), dtype=torch.int64)
+    for t in range(T - 1, -1, -1):
+        row = a[:, t, None, :].expand(B, N, S)
+        state = j[..., None] + offsets                                              # (B, N, W): the band's slots
+        inside = (state >= 0) & (state < S)
+        at = state.clamp(0, S - 1)
+        v = torch.where(inside, torch.gather(row, 2, at) * V[j[..., None], at], torch.zeros((), dtype=torch.float64))
+        slot, ok_band = draw(torch.cat([v, ebg * row], dim=2), u[:, :, t])
+        in_band = slot < W
+        picked_band = torch.where(in_band, torch.gather(at, 2, slot.clamp(max=W - 1)[..., None])[..., 0], slot - W)
+        picked_last, ok_last = draw(row, u[:, :, t])
+        last = (t == F - 1)[:, None]
+        picked = torch.where(last, picked_last, picked_band)
+        ok = torch.where(last, ok_last, ok_band)
+        active = (t <= F - 1)[:, None]
+        good &= ok | ~active
+        j = torch.where(active, picked, j)
+        indices[:, :, t] = j
+    tail = torch.gather(indices, 2, (F - 1)[:, None, None].expand(B, N, 1))
+    indices = torch.where(torch.arange(T)[None, None, :] >= F[:, None, None], tail, indices)
     indices = torch.where(good[..., None], indices, torch.full_like(indices, -1))
     return indices, L

@@ -52,7 +52,7 @@ extern "C" {
 #define TORBI_HIP_ABI_VERSION 17
 
 #define TORBI_HIP_OK 0
-#define TORBI_HIP_EINVAL (-1)      /* null pointer / non-positive dimension            */
+#define TORBI_HIP_EINVAL (-1)      /* null pointer / non-positive dimension / decode workspace not 256-byte aligned */
 #define TORBI_HIP_EWORKSPACE (-2)  /* workspace smaller than torbi_hip_workspace_bytes */
 #define TORBI_HIP_ERANGE (-3)      /* dimension too large for this build               */
 #define TORBI_HIP_ENODEVICE (-4)   /* no usable HIP device / wrong architecture        */
@@ -161,6 +161,14 @@ int torbi_hip_last_forward_kernel(char *name_out, size_t capacity);
  *   transition    (S,S)   fp32, [next, prev]       initial      (S) fp32
  *   indices_out   (B,T)   int32  -- fully overwritten
  *   workspace     >= torbi_hip_workspace_bytes(B,T,S) bytes, 256-byte aligned
+ *
+ * The decode layouts start at the caller's base, so the alignment is part of the contract of every entry point that takes
+ * a decode workspace -- this one, _ex, _profiled and the torbi_hip_batch tables of _batches, _batches_prepared, _banded and
+ * _banded_over: a workspace pointer that is not a multiple of 256 returns TORBI_HIP_EINVAL before any device is selected
+ * and anything is launched (looked at after the size, so a workspace that is too small is TORBI_HIP_EWORKSPACE wherever it
+ * lies; a batch with B == 0 brings no workspace and is not looked at).  The workspaces of the other models
+ * (forward-backward, counts, k-best, sampling and their band routes) need NO alignment: those entry points round the base
+ * up themselves and their size queries include the room; the streaming state needs 4 bytes (see there).
  */
 int torbi_hip_viterbi_decode(const float *observation, const int32_t *batch_frames,
                              const float *transition, const float *initial,
@@ -522,8 +530,10 @@ int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_b
  * -inf entries are zero probabilities.  An item of total probability 0 gets L = -inf and NaN rows t < F_b; a NaN or +inf in
  * anything an item reads gives it L = NaN and NaN rows; an item's bits never depend on other items' data.
  *
- * workspace: device scratch of torbi_hip_forward_backward_workspace_bytes(B, T, S) bytes (no initialisation; both entry
- * points).  One launch per timestep and pass, no host synchronisation: a call can be captured into a graph.
+ * workspace: device scratch of torbi_hip_forward_backward_workspace_bytes(B, T, S) bytes (no initialisation, no
+ * alignment: the call rounds the base up to 256 bytes itself and the size includes the room; both entry points).  What the
+ * workspace held before never reaches a result.  One launch per timestep and pass, no host synchronisation: a call can be
+ * captured into a graph.
  * The uniform entry point takes a matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))) and computes
  * the same quantities in closed form (beta is constant over states): one elementwise pass and a per-item fp64 sum.
  * TORBI_HIP_ERANGE for S > 16384, more than 65535 * 32 items or more than 2^32 item frames (B * T).
@@ -544,8 +554,8 @@ int torbi_hip_forward_backward_uniform(const float *observation, const int32_t *
  *     initial_counts_out[j] = sum_b g_b gamma_0^b[j]                        (S,) fp32
  * An item with g_b == 0 or a non-finite L_b is skipped, not multiplied: a NaN item adds nothing.  The summation order is
  * fixed (over t from F - 1 down to 1, over items in order), so the bits of both outputs depend on the inputs only; no
- * float atomics.  workspace: torbi_hip_forward_backward_counts_workspace_bytes(B, T, S) bytes.  No host synchronisation:
- * with a caller-owned workspace a call can be captured into a graph.  Errors as torbi_hip_forward_backward, and
+ * float atomics.  workspace: torbi_hip_forward_backward_counts_workspace_bytes(B, T, S) bytes, no alignment.  No host
+ * synchronisation: with a caller-owned workspace a call can be captured into a graph.  Errors as torbi_hip_forward_backward, and
  * TORBI_HIP_EINVAL for a null counts_out or initial_counts_out.
  */
 size_t torbi_hip_forward_backward_counts_workspace_bytes(int B, int T, int S);
@@ -568,7 +578,8 @@ int torbi_hip_forward_backward_counts(const float *observation, const int32_t *b
  * torbi_hip_forward_backward_band_covers: 1 where the entry point takes the call -- 1 <= S <= 4096, at most 64 in-band
  * entries in a matrix row (min(W, S) <= 64 with the reaches clamped to S - 1), a background that is neither NaN nor +inf, B
  * and T within torbi_hip_forward_backward's limits --, else 0.  It and _workspace_bytes answer without a device.
- * workspace: torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation.
+ * workspace: torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation (the
+ * promise flag is reset by every call) and no alignment.
  * Four launches per call whatever T is (the time loop runs inside one launch, a workgroup owns whole items), no host
  * synchronisation: with a caller-owned workspace a call can be captured into a graph.  Errors as
  * torbi_hip_forward_backward (TORBI_HIP_EINVAL also for a negative reach), and TORBI_HIP_EUNSUPPORTED where _covers answers 0.
@@ -601,7 +612,8 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
  * torbi_hip_forward_backward_counts_band_covers: 1 where torbi_hip_forward_backward_band_covers answers 1 AND the plane fits
  * beside the rows of one item, 4 W S + the rows' bytes <= 160 KB (the pitch band, 23 diagonals of 1440 states: 144 KB), else
  * 0.  It and _workspace_bytes answer without a device.  workspace: the band route's plus min(B, 512) planes [W][S up to 64]
- * fp32, torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation.
+ * fp32, torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right) bytes, no initialisation
+ * and no alignment.
  * Six launches per call whatever T is, no host synchronisation: with a caller-owned workspace a call can be captured into a
  * graph.  Errors as torbi_hip_forward_backward_band, TORBI_HIP_EINVAL also for a null band_counts_out or
  * initial_counts_out, TORBI_HIP_EUNSUPPORTED where _covers answers 0.
@@ -630,7 +642,7 @@ int torbi_hip_forward_backward_counts_band(const float *observation, const int32
  * -inf and index -1 in every column.  A NaN or +inf in anything an item reads (initial, the matrix when F_b >= 2, its
  * observation rows t < F_b) gives that item NaN scores and -1 indices.  An item's bits never depend on other items' data.
  *
- * workspace: device scratch (no initialisation) of torbi_hip_k_best_workspace_bytes(B, T, S, k) bytes for
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_k_best_workspace_bytes(B, T, S, k) bytes for
  * torbi_hip_k_best (back-pointers: 4 * B * (T - 1) * k * S bytes) and of torbi_hip_k_best_workspace_bytes(B, T, 1, k)
  * bytes for torbi_hip_k_best_uniform.  One launch per frame (general route) or one per call (uniform route), no host
  * synchronisation: with a caller-owned workspace a call can be captured into a graph.
@@ -662,7 +674,8 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
  * 159 * 1024 and then while ceil(B / G) < 256.
  *
  * torbi_hip_k_best_band_workspace_bytes: torbi_hip_k_best_workspace_bytes's layout with the diagonals,
- * (reach_left + reach_right + 1) * S floats, in place of the transposed matrix, and one verdict word.
+ * (reach_left + reach_right + 1) * S floats, in place of the transposed matrix, and one verdict word.  No initialisation
+ * (flags, counts and the verdict word are set by every call) and no alignment.
  *
  * torbi_hip_k_best_band: arguments as torbi_hip_k_best plus the band.  The promise about the entries outside the band is
  * checked on the device and nothing is read back: where it is broken every item gets NaN scores and -1 indices.
@@ -689,8 +702,8 @@ int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames,
  * probability 0; NaN: it reads a NaN or +inf) has -1 in every column of every draw; so has a draw whose Z at some frame is 0
  * or not finite (underflow of the product).
  *
- * workspace: device scratch (no initialisation) of torbi_hip_sample_workspace_bytes(B, T, S, N, uniform) bytes: with
- * uniform == 0 the layout of torbi_hip_forward_backward followed by the filter rows (B, T, S) fp32, else (B, T) fp64.  The
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_sample_workspace_bytes(B, T, S, N, uniform) bytes:
+ * with uniform == 0 the layout of torbi_hip_forward_backward followed by the filter rows (B, T, S) fp32, else (B, T) fp64.  The
  * filter's launches and one sampler launch (uniform: three launches), no allocation and no host synchronisation: a call can
  * be captured into a graph.
  * The uniform entry point takes a matrix whose every entry is `uniform_value`: frames are independent, j_0 ~ softmax(initial
@@ -718,7 +731,8 @@ int torbi_hip_sample_uniform(const float *observation, const int32_t *batch_fram
  *
  * torbi_hip_sample_band_covers: 1 where torbi_hip_forward_backward_band_covers answers 1 and 1 <= N <= 4096; it reads no
  * device.  torbi_hip_sample_band_workspace_bytes: torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left,
- * reach_right) plus the filter rows (B, T, S) fp32 on the next 256-byte boundary, whatever N.
+ * reach_right) plus the filter rows (B, T, S) fp32 on the next 256-byte boundary, whatever N; no initialisation and no
+ * alignment of the caller's base.
  * TORBI_HIP_EINVAL for a null pointer, a negative reach or N outside [1, 4096]; TORBI_HIP_ERANGE as torbi_hip_sample;
  * TORBI_HIP_EUNSUPPORTED where _covers answers 0; TORBI_HIP_EWORKSPACE for a workspace that is too small.  B == 0 returns 0.
  * Five launches, no allocation and no host synchronisation: a call can be captured into a graph.

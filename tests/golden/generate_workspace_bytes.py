@@ -10,6 +10,9 @@ The grid crosses every condition of the layouts: B 16 | 17 (held-matrix regions,
 63 | 64 | 65, 256 | 257, 2048 | 2049, 4096 | 4097 (small-state kernels, time-resident, 8-item tiles, the routes' limits), 2052
 (a multiple of 4 above 2048: band route with 8-item tiles), 192 and 1440.  The decode query branches on T, so it keeps the whole
 T axis at the batch sizes next to a T condition and two values elsewhere; the others are linear in T and keep one or two.
+The band counts add B 511 | 512 | 513 (one plane per item up to 512 planes), sampling both values of `uniform` and the ends
+of the range of draws (the size does not depend on them), and the band queries a reach of 300 / 5, which clamps at S - 1 for
+every state count up to 257.
 """
 import json
 import os
@@ -27,6 +30,8 @@ STATES = (1, 2, 63, 64, 65, 192, 256, 257, 1440, 2048, 2049, 2052, 4096, 4097)
 CAPACITIES = (1, 64)
 RANKS = (1, 3, 32)
 REACHES = ((0, 0), (10, 3), (87, 87))
+WIDE = REACHES + ((300, 5),)
+DRAWS = (1, 4096)
 
 
 def grid():
@@ -44,6 +49,25 @@ def grid():
     g['torbi_hip_k_best_workspace_bytes'] = (
         [(B, 130, S, k) for B in (1, 17, 8193) for S in STATES for k in RANKS]
         + [(B, 1, S, 3) for B in (1, 17, 8193) for S in STATES])
+    # the queries that stand on the ones above: the counts (the layout of forward_backward), the band counts (planes behind the
+    # band layout: one per item below 512 items, 512 from there on), band k-best (diagonals in place of the matrix, a verdict
+    # word), sampling (filter rows behind forward_backward's layout or the band's; the uniform route's row sums alone) and
+    # the streaming band route's diagonals.  WIDE holds reaches that clamp at S - 1 for the smaller state counts.
+    g['torbi_hip_forward_backward_counts_workspace_bytes'] = (
+        [(B, 129, S) for B in (1, 17, 32, 8193) for S in STATES] + [(17, 2, S) for S in STATES])
+    g['torbi_hip_forward_backward_counts_band_workspace_bytes'] = (
+        [(B, 129, S, l, r) for B in (1, 17, 511, 512, 513, 8193) for S in STATES for (l, r) in WIDE]
+        + [(17, 2, S, 10, 3) for S in STATES])
+    g['torbi_hip_k_best_band_workspace_bytes'] = (
+        [(B, 130, S, k, l, r) for B in (1, 17, 8193) for S in STATES for k in RANKS for (l, r) in WIDE]
+        + [(17, 1, S, 3, 10, 3) for S in STATES])
+    g['torbi_hip_sample_workspace_bytes'] = (
+        [(B, 129, S, N, u) for B in (1, 17, 32, 8193) for S in STATES for N in DRAWS for u in (0, 1)]
+        + [(17, 2, S, 5, u) for S in STATES for u in (0, 1)])
+    g['torbi_hip_sample_band_workspace_bytes'] = (
+        [(B, 129, S, N, l, r) for B in (1, 17, 8193) for S in STATES for N in DRAWS for (l, r) in WIDE]
+        + [(17, 2, S, 5, 10, 3) for S in STATES])
+    g['torbi_hip_stream_band_diagonals_bytes'] = [(S, l, r) for S in STATES for (l, r) in WIDE]
     return g
 
 

@@ -10,13 +10,18 @@ from torbi_amd import _lib
 RECORD = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'workspace_bytes.json')))
 QUERIES = ('torbi_hip_workspace_bytes', 'torbi_hip_preparation_bytes', 'torbi_hip_stream_state_bytes',
            'torbi_hip_forward_backward_workspace_bytes', 'torbi_hip_forward_backward_band_workspace_bytes',
-           'torbi_hip_k_best_workspace_bytes')
+           'torbi_hip_k_best_workspace_bytes', 'torbi_hip_forward_backward_counts_workspace_bytes',
+           'torbi_hip_forward_backward_counts_band_workspace_bytes', 'torbi_hip_k_best_band_workspace_bytes',
+           'torbi_hip_sample_workspace_bytes', 'torbi_hip_sample_band_workspace_bytes',
+           'torbi_hip_stream_band_diagonals_bytes')
 
 
-def test_the_record_holds_the_six_queries_and_nothing_else():
+def test_the_record_holds_every_byte_query_and_nothing_else():
     assert sorted(RECORD) == sorted(QUERIES + ('commit', 'compute_units'))
     assert RECORD['compute_units'] == 256 and len(RECORD['commit']) == 40
     assert all(len(RECORD[name]) > 0 for name in QUERIES)
+    # ... and the record names every export of the library that answers in bytes
+    assert sorted(QUERIES) == sorted(name for name, (restype, _) in _lib.SYMBOLS.items() if name.endswith('_bytes'))
 
 
 @pytest.mark.parametrize('name', QUERIES)

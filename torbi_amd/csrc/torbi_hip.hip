@@ -866,6 +866,7 @@ int check_args(const void *a, const void *b, const void *c, const void *d, const
     if (!a || !b || !c || !d || !e || !ws) return TORBI_HIP_EINVAL;
     if ((size_t)B * T * S > (size_t)1 << 40) return TORBI_HIP_ERANGE;
     if (ws_bytes < need_bytes(B, T, S, cu_count(device))) return TORBI_HIP_EWORKSPACE;
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return TORBI_HIP_EINVAL;     // (the decode layouts start at the caller's base)
     return TORBI_HIP_OK;
 }
 
@@ -1860,7 +1861,7 @@ int torbi_hip_abi_version(void) { return TORBI_HIP_ABI_VERSION; }
 const char *torbi_hip_error_string(int code) {
     switch (code) {
         case TORBI_HIP_OK: return "success";
-        case TORBI_HIP_EINVAL: return "invalid argument (null pointer, non-positive dimension or unknown flag)";
+        case TORBI_HIP_EINVAL: return "invalid argument (null pointer, non-positive dimension, unknown flag or a decode workspace that is not 256-byte aligned)";
         case TORBI_HIP_EWORKSPACE: return "workspace smaller than torbi_hip_workspace_bytes()";
         case TORBI_HIP_ERANGE: return "problem dimensions out of range for this build";
         case TORBI_HIP_ENODEVICE: return "no usable HIP device";

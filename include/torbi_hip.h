@@ -520,6 +520,56 @@ int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_b
                                 int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
 
 /*
+ * (added within ABI 17) Streaming posteriors: online filtering and fixed-lag smoothing of B independent streams whose
+ * frames arrive in pieces (csrc/stream_posterior.hpp, torbi_amd/stream_posterior.py, STREAM.md "Streaming posteriors").  The
+ * quantities are torbi_hip_forward_backward's (the scaled recurrence of POSTERIOR.md, its non-finite rules included).  A
+ * stream holds n frames, the first `base` of them returned; a push of f >= 1 frames returns, with n' = n + f, the rows
+ * gamma_{t|n'} = P(state_t | frames 0 .. n' - 1) for t = base .. n' - 1 - lag: the corresponding rows of the whole-sequence
+ * posteriors of the stream's first n' frames.  A stream with f = 0 returns nothing and keeps its state.  A flush returns the
+ * rows base .. n - 1 as gamma_{t|n}.  A stream whose running log-likelihood is not finite returns NaN rows.
+ *
+ * expa (S, S) fp32 is exp(transition) [next][prev] and expa_t the same matrix transposed ([prev][next]); the caller builds
+ * both once per matrix (there is no prepare kernel; torbi_amd builds them with torch.exp from a private copy).  Where
+ * S % 4 == 0 and the matrix a kernel reads is 16-byte aligned, a thread takes 4 consecutive states per 16-byte load.
+ *
+ * State (caller-owned, device memory, torbi_hip_stream_posterior_state_size(B, S, capacity) bytes -- 0 for a non-positive
+ * argument --, no alignment beyond 4, no initialisation: the `fresh` flag is what starts a stream), 4-byte words, packed:
+ *     L  [B][2]           the fp64 running sum of log c_t + m_t, low word first; log P(frames so far) of a started stream
+ *     a  [B][capacity][S] fp32   a_t of the pending frames (frame base + r in slot (base_slot + r) % capacity)
+ *     e  [B][capacity][S] fp32   e_t
+ *     c  [B][capacity]    fp32   c_t
+ *     m  [B][capacity]    fp32   m_t
+ * The newest frame's a and c are read by the next push in the slot before the first free one, also when nothing is
+ * pending.  A state that grows takes L and the rows of the pending frames and of the newest frame in their new slots.
+ * capacity >= pending + frames of every stream of a push, >= 1; with pending <= lag it never needs more than lag + Tc.
+ *
+ * info [B][4] int32 {pending, base_slot, frames, fresh} as for torbi_hip_stream_push (flush: frames = 1 flushes the stream,
+ * 0 leaves it).  posterior_out [B][out_capacity][S] fp32: row r of stream b is its frame base + r; counts_out [B] int32
+ * (may be NULL) the number of rows, -1 for a stream whose info does not fit -- pending < 0 or above capacity, base_slot
+ * outside 0 .. capacity - 1, fresh with pending != 0, frames outside 0 .. Tc or above capacity - pending, or more rows to
+ * return than out_capacity.  One predicate decides this in every kernel of the call: such a stream keeps its state and its
+ * output rows untouched, the others are processed.  The caller advances base_slot by the count and sets pending to
+ * pending + frames - count.  Neither call synchronises the host or reads anything back.
+ *
+ * torbi_hip_stream_posterior_tile: streams per workgroup of a call's kernels for (B, S) on `device` (sp_forward_kernel<G, J>
+ * and sp_backward_kernel<G, J>: 16, halved while the rows of G streams, 8 G S bytes, and 768 bytes of partial sums exceed
+ * 64 KB of LDS, then while there are fewer workgroups than compute units); EINVAL / ERANGE for a shape the push turns down;
+ * without a usable device it answers for 256 compute units.
+ *
+ * Every argument is checked before any device work: TORBI_HIP_EINVAL (a null pointer -- counts_out may always be null,
+ * observation / expa_t / initial when Tc = 0 --; B, S, capacity or out_capacity < 1; Tc < 0; lag < 0), TORBI_HIP_ERANGE for
+ * S > 8000 (the double-buffered rows of one stream in 64 KB of LDS), TORBI_HIP_EWORKSPACE for a state_bytes below the size.
+ */
+size_t torbi_hip_stream_posterior_state_size(int B, int S, int capacity);
+int torbi_hip_stream_posterior_tile(int B, int S, int device);
+int torbi_hip_stream_posterior_push(const float *observation, int Tc, const int32_t *info, const float *expa, const float *expa_t,
+                                    const float *initial, void *state, size_t state_bytes, int capacity, float *posterior_out,
+                                    int out_capacity, int32_t *counts_out, int lag, int B, int S, int device, void *stream);
+int torbi_hip_stream_posterior_flush(const int32_t *info, const float *expa, void *state, size_t state_bytes, int capacity,
+                                     float *posterior_out, int out_capacity, int32_t *counts_out, int B, int S, int device,
+                                     void *stream);
+
+/*
  * (ABI 17) Forward-backward: per-frame state posteriors and the sequence log-likelihood of the HMM that
  * torbi_hip_viterbi_decode decodes (torbi_amd/posterior.py, POSTERIOR.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.  For t < F_b:

@@ -41,6 +41,7 @@
 #include "band_tile_forward.hpp"
 #include "stream.hpp"
 #include "stream_band.hpp"
+#include "stream_posterior.hpp"
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
 #include "counts_band.hpp"
@@ -2385,6 +2386,95 @@ int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_b
                        reinterpret_cast<const stream::Info *>(info), ss.ring, ss.memo, ss.carried, capacity, indices_out, out_capacity,
                        counts_out, 0, S, -1, nullptr);
     return (int)hipGetLastError();
+}
+
+// ---- streaming posteriors: filtering and fixed-lag smoothing (stream_posterior.hpp) ----
+
+namespace sp = stream_posterior;
+
+// the state of B streams: running sums [B][2] words, a and e [B][capacity][S], c and m [B][capacity]; 4-byte words, packed
+struct StreamPosteriorState { int32_t *L; float *a, *e, *c, *m; size_t bytes; };
+static StreamPosteriorState stream_posterior_state(void *state, int B, int S, int capacity) {
+    Scratch s(state);
+    StreamPosteriorState st;
+    st.L = s.take<int32_t>((size_t)B * 2, 4);
+    st.a = s.take<float>((size_t)B * capacity * S, 4);
+    st.e = s.take<float>((size_t)B * capacity * S, 4);
+    st.c = s.take<float>((size_t)B * capacity, 4);
+    st.m = s.take<float>((size_t)B * capacity, 4);
+    st.bytes = s.bytes;
+    return st;
+}
+
+size_t torbi_hip_stream_posterior_state_size(int B, int S, int capacity) {
+    if (B < 1 || S < 1 || capacity < 1) return 0;
+    return stream_posterior_state(nullptr, B, S, capacity).bytes;
+}
+
+// Streams per workgroup of sp_forward_kernel / sp_backward_kernel: stream_tile's rule with this route's LDS
+int torbi_hip_stream_posterior_tile(int B, int S, int device) {
+    if (B < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (S > sp::kMaxStates) return TORBI_HIP_ERANGE;
+    return items_per_workgroup(sp::kMaxGroup, B, 1, cu_count(device), [&](int G) { return sp::fits(G, S); });
+}
+
+static int stream_posterior_args_ok(const void *info, const void *expa, const void *state, size_t state_bytes, int capacity,
+                                    const void *posterior_out, int out_capacity, int lag, int B, int S) {
+    if (B < 1 || S < 1 || capacity < 1 || out_capacity < 1 || lag < 0) return TORBI_HIP_EINVAL;
+    if (!info || !expa || !state || !posterior_out) return TORBI_HIP_EINVAL;
+    if (S > sp::kMaxStates) return TORBI_HIP_ERANGE;
+    if (state_bytes < torbi_hip_stream_posterior_state_size(B, S, capacity)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+// the backward sweep of a push (Tc >= 0) or a flush (Tc < 0)
+static int stream_posterior_sweep(const int32_t *info, int Tc, const float *expa, const StreamPosteriorState &ss, int capacity,
+                                  float *posterior_out, int out_capacity, int32_t *counts_out, int lag, int B, int S, int device,
+                                  hipStream_t st) {
+    const int G = torbi_hip_stream_posterior_tile(B, S, device);
+    const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(expa) & 15) == 0;
+    by_value<16, 8, 4, 2, 1>(G, [&](auto g) { by_flag(vec, [&](auto vec_) {
+        auto *kernel = &sp::sp_backward_kernel<decltype(g)::value, decltype(vec_)::value ? 4 : 1>;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(sp::kThreads), sp::lds_bytes(G, S), st,
+                           reinterpret_cast<const stream::Info *>(info), Tc, expa, ss.L, ss.a, ss.e, ss.c, capacity, posterior_out,
+                           out_capacity, counts_out, lag, B, S);
+    }); });
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_stream_posterior_push(const float *observation, int Tc, const int32_t *info, const float *expa, const float *expa_t,
+                                    const float *initial, void *state, size_t state_bytes, int capacity, float *posterior_out,
+                                    int out_capacity, int32_t *counts_out, int lag, int B, int S, int device, void *stream) {
+    int code = stream_posterior_args_ok(info, expa, state, state_bytes, capacity, posterior_out, out_capacity, lag, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    if (Tc < 0 || (Tc > 0 && (!observation || !expa_t || !initial))) return TORBI_HIP_EINVAL;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const StreamPosteriorState ss = stream_posterior_state(state, B, S, capacity);
+    if (Tc > 0) {
+        const int G = torbi_hip_stream_posterior_tile(B, S, device);
+        const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(expa_t) & 15) == 0;
+        by_value<16, 8, 4, 2, 1>(G, [&](auto g) { by_flag(vec, [&](auto vec_) {
+            auto *kernel = &sp::sp_forward_kernel<decltype(g)::value, decltype(vec_)::value ? 4 : 1>;
+            hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(sp::kThreads), sp::lds_bytes(G, S), st, observation, Tc,
+                               reinterpret_cast<const stream::Info *>(info), expa_t, initial, ss.L, ss.a, ss.e, ss.c, ss.m,
+                               capacity, out_capacity, lag, B, S);
+        }); });
+        if ((code = (int)hipGetLastError()) != hipSuccess) return code;
+    }
+    return stream_posterior_sweep(info, Tc, expa, ss, capacity, posterior_out, out_capacity, counts_out, lag, B, S, device, st);
+}
+
+int torbi_hip_stream_posterior_flush(const int32_t *info, const float *expa, void *state, size_t state_bytes, int capacity,
+                                     float *posterior_out, int out_capacity, int32_t *counts_out, int B, int S, int device,
+                                     void *stream) {
+    const int code = stream_posterior_args_ok(info, expa, state, state_bytes, capacity, posterior_out, out_capacity, 0, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    return stream_posterior_sweep(info, -1, expa, stream_posterior_state(state, B, S, capacity), capacity, posterior_out,
+                                  out_capacity, counts_out, 0, B, S, device, static_cast<hipStream_t>(stream));
 }
 
 // ---- forward-backward: state posteriors and log-likelihood (forward_backward.hpp) ----

@@ -1,0 +1,319 @@
+"""Online filtering and fixed-lag smoothing: the forward-backward recurrence of POSTERIOR.md on frames that arrive in pieces.
+
+A stream holds n frames, the first `base` of them already returned.  A push that brings a stream f >= 1 frames returns, with
+n' = n + f, the rows gamma_{t|n'} = P(state_t = j | frames 0 .. n' - 1) for t = base .. n' - 1 - lag: the corresponding rows of
+`state_posteriors` on the stream's first n' frames (the rule `StreamDecoder(max_lag=...)` follows for indices).  `filtered()`
+is the newest row, `log_likelihood` the running log P(frames so far), `flush` the remaining rows.  The HIP route is
+csrc/stream_posterior.hpp behind torbi_hip_stream_posterior_* (include/torbi_hip.h); `gpu=None` runs the same rule on the
+host in float64 with torch CPU ops.  STREAM.md, "Streaming posteriors", has the layout, the kernels and the numbers.
+"""
+import math
+import operator
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, inputs
+
+# ring slots of a new decoder
+INITIAL_CAPACITY = 16
+
+
+class StreamPosteriors:
+    """State posteriors of `batch` independent streams whose frames arrive in pieces; memory per stream is bounded by `lag`.
+
+    `transition` (states, states) [next, prev], `initial` (states,), `log_probs` and `gpu` mean what they mean to
+    `StreamDecoder` and `state_posteriors`, defaults included, and go through the same preparation (torbi_amd/inputs.py);
+    `transition=None` is the constant matrix it stands for.  `lag` (an integer >= 0, required to be one): how many frames
+    a row waits for before it leaves.
+
+        sp = StreamPosteriors(batch, states, transition, initial, lag=8)
+        rows = sp.push(observation)       # (batch, Tc, states) -> `batch` float32 tensors (k_b, states), oldest frame first
+        now = sp.filtered()               # (batch, states): P(state of the newest frame | frames so far)
+        score = sp.log_likelihood         # (batch,): log P(frames so far)
+        rest, final = sp.flush()          # the remaining rows of every stream and the final log-likelihoods
+
+    * One-frame pushes give exact fixed-lag smoothing, gamma_{t|t+lag}; in a longer push the older frames see more than
+      `lag` frames ahead, never fewer.  Afterwards `pending == min(pending + f, lag)`; a stream with f == 0 returns
+      nothing and does not change.
+    * Non-finite rules are POSTERIOR.md's: a stream whose running log-likelihood is not finite (total probability 0, or a
+      NaN or +inf in anything it has read) gets NaN rows until it is flushed; other streams' bits never change for it.
+    * A stream's bits depend on its own data and on (t, n') only: not on the batch it runs in, the cut into pushes or
+      the ring's size.
+    * Device memory per stream: (8 * states + 8) bytes per ring slot plus 8; `capacity` (a power of two, at least
+      INITIAL_CAPACITY) never exceeds `round_capacity(lag + largest Tc pushed)`.  The host route holds at most lag + Tc
+      rows per stream.
+    * On the device exp(transition) and its transpose are built once, here, with torch.exp from a private copy of the matrix.
+    """
+
+    def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
+                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0, lag: int = 8):
+        if batch < 1 or states < 1:
+            raise ValueError('StreamPosteriors needs batch >= 1 and states >= 1')
+        try:
+            if isinstance(lag, bool):
+                raise TypeError
+            lag = operator.index(lag)
+        except TypeError:
+            raise ValueError(f'lag must be an integer >= 0, got {lag!r}') from None
+        if lag < 0:
+            raise ValueError(f'lag must be an integer >= 0, got {lag!r}')
+        self.lag = lag
+        self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
+        S = self.states
+        self.device = inputs._compute_device(gpu)
+        transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
+        if transition is None:
+            transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
+        self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
+            raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
+        self._frames = np.zeros(self.batch, dtype=np.int64)        # frames pushed
+        self._base = np.zeros(self.batch, dtype=np.int64)          # first frame not yet returned
+        if gpu is None:
+            self._E = torch.exp(transition.to(torch.float32).to(torch.float64))      # [next, prev]
+            self._rows = [[] for _ in range(self.batch)]            # (a_t, e_t, c_t) of the pending frames
+            self._carry = [None] * self.batch                       # (a, c) of the newest frame
+            self._sum = [0.] * self.batch                           # running sums of log c_t + m_t
+            self._held = 0
+        else:
+            self._lib = _lib.load()
+            private = transition.to(device=self.device, dtype=torch.float32).clone()
+            self._expa = torch.exp(private).contiguous()            # [next, prev]
+            self._expa_t = self._expa.t().contiguous()              # [prev, next]
+            self._capacity = 0
+            self._state = None
+            self._grow(INITIAL_CAPACITY)
+
+    # ------------------------------------------------------------------ public
+    @staticmethod
+    def round_capacity(slots: int) -> int:
+        """Ring slots the device route allocates for `slots` rows per stream: the power of two at or above, at least
+        INITIAL_CAPACITY."""
+        return max(INITIAL_CAPACITY, 1 << (max(int(slots), 1) - 1).bit_length())
+
+    @property
+    def frames(self) -> torch.Tensor:
+        """(batch,) int64: frames pushed to each stream since it started."""
+        return torch.from_numpy(self._frames.copy())
+
+    @property
+    def pending(self) -> torch.Tensor:
+        """(batch,) int64: frames pushed and not yet returned."""
+        return torch.from_numpy(self._frames - self._base)
+
+    @property
+    def capacity(self) -> int:
+        """Ring slots per stream on the device; on the host the most rows a stream has held."""
+        return self._held if self.gpu is None else self._capacity
+
+    @property
+    def log_likelihood(self) -> torch.Tensor:
+        """(batch,) float32 on the compute device: log P(frames so far), the fp64 running sum of log c_t + m_t rounded on
+        read; NaN where the sum is NaN or +inf, 0 for a stream without frames.  Reads nothing back."""
+        if self.gpu is None:
+            total = torch.tensor(self._sum, dtype=torch.float64)
+        else:
+            total = self._state[:8 * self.batch].view(torch.float64)
+        started = self._mask(self._frames > 0)
+        total = torch.where(started, total, torch.zeros_like(total))
+        total = torch.where(torch.isnan(total) | (total == math.inf), torch.full_like(total, math.nan), total)
+        return total.to(torch.float32)
+
+    def filtered(self) -> torch.Tensor:
+        """(batch, states) float32 on the compute device: P(state of the newest frame | frames so far), a_{n-1} / c_{n-1}
+        (NaN where the running log-likelihood is not finite); zeros for a stream without frames.  Reads nothing back."""
+        B, S = self.batch, self.states
+        if self.gpu is None:
+            a = torch.stack([torch.zeros(S, dtype=torch.float64) if k is None else k[0] for k in self._carry])
+            c = torch.stack([torch.ones((), dtype=torch.float64) if k is None else k[1] for k in self._carry])
+        else:
+            slot = self._to_device((np.maximum(self._frames, 1) - 1) % self._capacity)
+            item = torch.arange(B, device=self.device)
+            ring_a, _, ring_c, _ = self._rings()
+            a, c = ring_a[item, slot], ring_c[item, slot]
+        row = a / c[:, None]
+        row = torch.where(torch.isfinite(self.log_likelihood)[:, None], row, torch.full_like(row, math.nan))
+        return torch.where(self._mask(self._frames > 0)[:, None], row, torch.zeros_like(row)).to(torch.float32)
+
+    def push(self, observation: torch.Tensor, frames: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """Append frames to the streams and return the rows that reached the lag.
+
+        observation (batch, Tc, states); frames (batch,) valid frames per stream, 0 .. Tc (None = all Tc).  Returns `batch`
+        float32 tensors (k_b, states) on the compute device, oldest frame first: k_b = max(0, pending_b + f_b - lag) for
+        f_b >= 1, else 0.  Performs NO host synchronisation: k_b is a function of values the host already holds, so nothing
+        is read back (the per-call stream table goes to the device through pinned memory).
+        """
+        if observation.dim() != 3 or observation.shape[0] != self.batch or observation.shape[2] != self.states:
+            raise ValueError(f'observation must be ({self.batch}, Tc, {self.states}), got {tuple(observation.shape)}')
+        Tc = int(observation.shape[1])
+        if frames is None:
+            f = np.full(self.batch, Tc, dtype=np.int64)
+        else:
+            f = torch.as_tensor(frames).detach().to('cpu', torch.int64).reshape(-1).numpy().copy()
+            if f.shape[0] != self.batch or (f < 0).any() or (f > Tc).any():
+                raise ValueError(f'frames must hold {self.batch} counts in 0 .. {Tc}')
+        if not f.any():
+            return [torch.empty((0, self.states), dtype=torch.float32, device=self.device) for _ in range(self.batch)]
+        obs = inputs.observation(observation, self.log_probs, self.device)
+        pending = self._frames - self._base
+        counts = np.where(f > 0, np.maximum(pending + f - self.lag, 0), 0)
+        if self.gpu is None:
+            out = self._push_host(obs, f, counts)
+        else:
+            out = self._push_device(obs, f, counts)
+        self._frames += f
+        self._base += counts
+        return out
+
+    def flush(self, items: Optional[Sequence[int]] = None) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """End streams `items` (default: all): (rows, final) with one (pending_k, states) float32 tensor per item, in the
+        order given -- the stream's remaining frames as gamma_{t|n} -- and final (len(items),) float32, their log-likelihoods.
+        The streams are reset: their next push starts from `initial`.  A stream without frames returns a (0, states) tensor
+        and a log-likelihood of 0.  Reads nothing back."""
+        items = list(range(self.batch)) if items is None else [int(k) for k in items]
+        if any(k < 0 or k >= self.batch for k in items):
+            raise IndexError(f'stream index out of range 0 .. {self.batch - 1}')
+        final = self.log_likelihood[self._to_device(np.asarray(items, dtype=np.int64))]
+        chosen = sorted(set(items))
+        if self.gpu is None:
+            rest = {k: self._sweep_host(k, int(self._frames[k] - self._base[k])) for k in chosen}
+            for k in chosen:
+                self._rows[k], self._carry[k], self._sum[k] = [], None, 0.
+        else:
+            rest = self._flush_device(chosen)
+        for k in chosen:
+            self._frames[k] = self._base[k] = 0
+        return [rest[k] for k in items], final
+
+    # ------------------------------------------------------------------ shared
+    def _to_device(self, values: np.ndarray) -> torch.Tensor:
+        """A small host array on the compute device without a host synchronisation (through pinned memory)."""
+        host = torch.from_numpy(np.ascontiguousarray(values))
+        if self.gpu is None:
+            return host
+        return host.pin_memory().to(self.device, non_blocking=True)
+
+    def _mask(self, flags: np.ndarray) -> torch.Tensor:
+        return self._to_device(flags.astype(np.bool_))
+
+    # ------------------------------------------------------------------ host route
+    def _sweep_host(self, b: int, count: int, pending: Optional[int] = None) -> torch.Tensor:
+        """gamma_{t|n} of the oldest `count` of stream b's `pending` newest rows (default: `count`), float32: one
+        backward sweep from the newest row."""
+        rows, S = self._rows[b], self.states
+        if count == 0:
+            return torch.empty((0, S), dtype=torch.float32)
+        pending = rows[len(rows) - (count if pending is None else pending):]
+        total = self._sum[b]
+        out = torch.empty((count, S), dtype=torch.float64)
+        beta = torch.ones(S, dtype=torch.float64)
+        for r in range(len(pending) - 1, -1, -1):
+            a, e, c = pending[r]
+            if r < count:
+                out[r] = a * beta / c
+            beta = (e * beta / c) @ self._E
+        if not math.isfinite(total):
+            out.fill_(math.nan)
+        return out.to(torch.float32)
+
+    def _push_host(self, obs: torch.Tensor, f: np.ndarray, counts: np.ndarray) -> List[torch.Tensor]:
+        result = []
+        pi = self.initial.to(torch.float64)
+        for b in range(self.batch):
+            rows = self._rows[b]
+            n = int(self._frames[b])
+            for t in range(int(f[b])):
+                x = obs[b, t].to(torch.float64)
+                if n + t == 0:
+                    x = x + pi
+                m = torch.amax(x)                                                     # NaN propagates
+                m = torch.zeros_like(m) if m == -math.inf else m
+                e = torch.exp(x - m)
+                if n + t == 0:
+                    a = e
+                else:
+                    prev_a, prev_c = self._carry[b]
+                    u = e * (self._E @ prev_a)
+                    a = u * 0. if prev_c == 0 else u / prev_c
+                c = a.sum()
+                rows.append((a, e, c))
+                self._carry[b] = (a, c)
+                self._sum[b] = self._sum[b] + float(torch.log(c) + m)
+            self._held = max(self._held, len(rows))
+            pending_now = int(self._frames[b] - self._base[b] + f[b])
+            result.append(self._sweep_host(b, int(counts[b]), pending_now))
+            del rows[:int(counts[b])]
+        return result
+
+    # ------------------------------------------------------------------ HIP route
+    def _rings(self, state=None, capacity=None):
+        """(a (B, cap, S), e (B, cap, S), c (B, cap), m (B, cap)) float32 views of the state."""
+        state = self._state if state is None else state
+        cap = self._capacity if capacity is None else capacity
+        B, S = self.batch, self.states
+        at, views = 8 * B, []
+        for shape in ((B, cap, S), (B, cap, S), (B, cap), (B, cap)):
+            size = 4 * int(np.prod(shape))
+            views.append(state[at:at + size].view(torch.float32).view(shape))
+            at += size
+        return views
+
+    def _grow(self, slots: int) -> None:
+        """Ring of round_capacity(slots) slots; the running sums and the rows of the pending frames and of the newest frame
+        move to their new slots by device copies."""
+        B, S = self.batch, self.states
+        capacity = self.round_capacity(slots)
+        nbytes = self._lib.torbi_hip_stream_posterior_state_size(B, S, capacity)
+        if nbytes == 0:
+            raise ValueError('torbi_hip_stream_posterior_state_size rejected the shape')
+        state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self._state is not None:
+            state[:8 * B] = self._state[:8 * B]
+            items, frames = [], []
+            for b in range(B):
+                n = int(self._frames[b])
+                if n == 0:
+                    continue
+                lo = min(int(self._base[b]), n - 1)
+                frames.append(np.arange(lo, n, dtype=np.int64))
+                items.append(np.full(n - lo, b, dtype=np.int64))
+            if items:
+                bi, fr = self._to_device(np.concatenate(items)), np.concatenate(frames)
+                new, old = self._to_device(fr % capacity), self._to_device(fr % self._capacity)
+                for dst, src in zip(self._rings(state, capacity), self._rings()):
+                    dst[bi, new] = src[bi, old]
+        self._state, self._capacity, self._state_bytes = state, capacity, nbytes
+
+    def _info(self, pending: np.ndarray, third: np.ndarray) -> torch.Tensor:
+        info = np.stack([pending, self._base % self._capacity, third, (self._frames == 0).astype(np.int64)], axis=1)
+        return self._to_device(info.astype(np.int32))
+
+    def _push_device(self, obs: torch.Tensor, f: np.ndarray, counts: np.ndarray) -> List[torch.Tensor]:
+        B, S = self.batch, self.states
+        pending = self._frames - self._base
+        need = int((pending + f).max())
+        if need > self._capacity:
+            self._grow(need)
+        info = self._info(pending, f)
+        out = torch.empty((B, max(1, int(counts.max())), S), dtype=torch.float32, device=self.device)
+        _, index, stream = _lib.launch(self.device)
+        _lib.check(self._lib.torbi_hip_stream_posterior_push(
+            obs.data_ptr(), int(obs.shape[1]), info.data_ptr(), self._expa.data_ptr(), self._expa_t.data_ptr(),
+            self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
+            None, min(self.lag, 2 ** 31 - 1), B, S, index, stream), 'torbi_hip_stream_posterior_push')
+        return [out[b, :counts[b]] for b in range(B)]
+
+    def _flush_device(self, items: List[int]) -> dict:
+        B, S = self.batch, self.states
+        pending = self._frames - self._base
+        marks = np.zeros(B, dtype=np.int64)
+        marks[items] = 1
+        info = self._info(pending, marks)
+        out = torch.empty((B, max(1, int(pending[items].max())), S), dtype=torch.float32, device=self.device)
+        _, index, stream = _lib.launch(self.device)
+        _lib.check(self._lib.torbi_hip_stream_posterior_flush(
+            info.data_ptr(), self._expa.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(),
+            out.shape[1], None, B, S, index, stream), 'torbi_hip_stream_posterior_flush')
+        return {k: out[k, :pending[k]] for k in items}

@@ -142,6 +142,7 @@ CASES = [(1, 1, 8, 1, 1, NINF),                    # no pairs: X = 0
          (8, 60, 1440, 11, 11, TINY),              # ... log(tiny) outside
          (4, 10, 4096, 3, 3, NINF),                # plane and rows: 147 KB of LDS
          (515, 4, 65, 2, 1, -6.0),                 # G = 2, partial last tile
+         (1030, 3, 37, 1, 2, NINF),                # G = 4 on 256 compute units, partial last tile
          (2050, 3, 33, 0, 3, NINF),                # G = 8
          (4100, 3, 33, 1, 2, NINF)]                # G = 8, 513 tiles for 512 workgroups: the persistent loop
 

@@ -13,9 +13,10 @@
 //
 // fb_band_counts_kernel<G> is fb_band_kernel<G> with that accumulation and a persistent loop over tiles: the grid is
 // min(tiles, kCountsWorkgroups), workgroup p takes tiles p, p + grid, ... and stores its plane to partial[p] at the end.  It is
-// a second kernel, not a flag of the first, so that the posterior route keeps its instances as they are; gamma, c_t and L of
-// an item are bit for bit fb_band_kernel's (the same ownership, butterflies and order).  fb_band_counts_finalize_kernel sums
-// the planes in order, multiplies by exp(A) and turns the diagonals to the forward layout.
+// a second kernel, not a flag of the first, so that the posterior route keeps its instances as they are; the forward pass and
+// L are fb_band_kernel's own functions (forward_pass, log_likelihood), the backward pass is written out here with the same
+// ownership, butterflies and order, so gamma, c_t and L of an item are bit for bit fb_band_kernel's.
+// fb_band_counts_finalize_kernel sums the planes in order, multiplies by exp(A) and turns the diagonals to the forward layout.
 //
 // An item counts iff g_b != 0 and its L_b is finite (known before the backward pass).  One that does not, or a frame behind
 // an item's last pair, is skipped by selection: q_g and the LDS value are both selected to 0, never multiplied by 0 (the row
@@ -59,21 +60,24 @@ __device__ __forceinline__ float wave_uniform(float x) {
 
 // ---- both passes and the counts of G items per tile; grid min(tiles, kCountsWorkgroups), dynamic LDS lds_bytes(G, S, halo)
 // + plane_bytes(W, S) ----
+// (waves per SIMD: every instance needs more than 64 vector registers, so a compute unit holds one workgroup, four waves per
+// SIMD, whatever else the count is.  Left to itself the compiler plans G = 2 for six waves, 80 registers, and pays with the
+// forward band sum's loads in flight: one at a time, 8 % of the call at 512 x 500 x 1440.  "At most five" leaves it 96.
+// "At most four" is the plain truth and compiles the same sum worse at G = 2 and G = 4: HISTORY.md)
 template <int G>
-__global__ __launch_bounds__(kThreads) void fb_band_counts_kernel(
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 5))) void fb_band_counts_kernel(
     const float *__restrict__ obs, const int32_t *__restrict__ frames, const float *__restrict__ initial,
     const float *__restrict__ Df, const float *__restrict__ Db, const float *__restrict__ m, float *__restrict__ cbuf,
     const int32_t *__restrict__ flag, const float *__restrict__ weights, float *__restrict__ post, float *__restrict__ loglik,
     float *__restrict__ partial, float ebg, int reach_left, int reach_right, int W, int Sd, int B, int T, int S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int halo = reach_left > reach_right ? reach_left : reach_right, stride = row_stride(S, halo);
-    double *lsum = reinterpret_cast<double *>(lds_raw);                 // [G][16]
-    double *Ls = lsum + G * kWaves;                                      // [G] (L as the float the caller gets)
-    float *rows = reinterpret_cast<float *>(Ls + G);                     // [2][G][stride]
-    float *part = rows + (size_t)2 * G * stride;                         // [2][G][16]
-    float *plane = part + 2 * G * kWaves;                                // [W][S]: Cb of this workgroup
+    Tile<G> tile(lds_raw, reach_left, reach_right, S);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int kUnroll = G <= 2 ? 8 : (G <= 4 ? 4 : 2);          // diagonal loads in flight per band sum
+    const int halo = tile.halo, stride = tile.stride;
+    const int *F = tile.F;
+    float *const rows = tile.rows, *const part = tile.part;
+    const double *Ls = tile.Ls;
+    float *plane = part + 2 * G * kWaves;                                // [W][S]: Cb of this workgroup
     constexpr bool kLateObs = G >= 8;       // o_t is loaded behind the band sum, not during it: 8 registers the sum needs
     constexpr int kBatch = G <= 2 ? 4 : (G <= 4 ? 2 : 1);  // diagonals whose LDS loads go out before the plane's stores
 
@@ -81,115 +85,14 @@ __global__ __launch_bounds__(kThreads) void fb_band_counts_kernel(
         for (int i = tid; i < S; i += kThreads) plane[(size_t)k * S + i] = 0.f;
 
     const int tiles = (B + G - 1) / G;
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int b0 = tile * G;
-        int F[G], Fmax = 1;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;   // (0: an item beyond the batch never takes a step)
-            Fmax = F[g] > Fmax ? F[g] : Fmax;
-        }
-        for (int e = tid; e < 2 * G * stride; e += kThreads) rows[e] = 0.f;  // (the halos stay zero for the whole tile)
-        // rows an item does not have
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            if (b0 + g >= B) continue;
-            float *out = post + (size_t)(b0 + g) * T * S;
-            for (size_t e = (size_t)F[g] * S + tid; e < (size_t)T * S; e += kThreads) out[e] = 0.f;
-        }
+    for (int t0 = blockIdx.x; t0 < tiles; t0 += gridDim.x) {
+        tile_begin(tile, frames, t0 * G, B, T);
+        zero_absent_rows(tile, post, B, T, S);
         __syncthreads();
-
-        // c_t of every item of the tile from the wave sums of frame t; thread 0 stores it for the backward pass and L
-        auto row_sums = [&](int t, float *c) {
-            const float *p = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                c[g] = sum16(p[g * kWaves + (lane & 15)]);
-                if (tid == 0 && t < F[g]) cbuf[(size_t)(b0 + g) * T + t] = c[g];
-            }
-        };
-
-        // ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1} ----
-        for (int t = 0; t < Fmax; ++t) {
-            float *cur = rows + (size_t)(t & 1) * G * stride;
-            const float *prev = rows + (size_t)((t & 1) ^ 1) * G * stride;
-            float cprev[G], acc[G];
-            if (t > 0) row_sums(t - 1, cprev);
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[g] = 0.f;
-            float mt[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
-            for (int j = tid; j < S; j += kThreads) {
-                float s[G], ot[G];
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    s[g] = 0.f;
-                    ot[g] = t < F[g] ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;    // (in flight during the band sum)
-                }
-                if (t > 0) {
-                    const float *d = Df + j;
-                    const float *x = prev + halo - reach_left + j;
-#pragma unroll kUnroll
-                    for (int k = 0; k < W; ++k) {
-                        const float dk = d[(size_t)k * Sd];
-#pragma unroll
-                        for (int g = 0; g < G; ++g) s[g] = fmaf(dk, x[g * stride + k], s[g]);
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if (t >= F[g]) continue;
-                    const size_t row = (size_t)(b0 + g) * T + t;
-                    const float o = ot[g], mm = mt[g];
-                    float v;
-                    if (t == 0) {
-                        v = expf(initial[j] + o - mm);
-                    } else {
-                        const float e = expf(o - mm), c = cprev[g];
-                        const float u = e * (ebg != 0.f ? fmaf(ebg, c, s[g]) : s[g]);
-                        v = c == 0.f ? u * 0.f : u / c;                  // (after a zero-probability frame: 0, or NaN from NaN)
-                    }
-                    cur[g * stride + halo + j] = v;
-                    post[row * S + j] = v;
-                    acc[g] += v;
-                }
-            }
-            float *p = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const float a = wave_sum(acc[g]);
-                if (lane == 0) p[g * kWaves + wave] = a;
-            }
-            __syncthreads();
-        }
-        {
-            float c[G];
-            row_sums(Fmax - 1, c);
-        }
-        __syncthreads();                                                 // (c_t written by thread 0 is read by all below)
-
-        // ---- L = sum_{t<F} (log c_t + m_t) in fp64; NaN when the sum is NaN or +inf, or the promise is broken ----
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            double a = 0.;
-            for (int t = tid; t < F[g]; t += kThreads) {
-                const size_t row = (size_t)(b0 + g) * T + t;
-                a += log((double)cbuf[row]) + (double)m[row];
-            }
-            a = wave_sum(a);
-            if (lane == 0) lsum[g * kWaves + wave] = a;
-        }
+        forward_pass(tile, obs, initial, Df, m, cbuf, post, ebg, reach_left, W, Sd, T, S);
+        log_likelihood(tile, m, cbuf, flag, loglik, B, T);
         __syncthreads();
-        if (tid < G) {
-            double L = 0.;
-            for (int w = 0; w < kWaves; ++w) L += lsum[tid * kWaves + w];
-            float out = (L != L || L == (double)INFINITY) ? NAN : (float)L;
-            if (*flag != 0) out = NAN;
-            Ls[tid] = (double)out;
-            if (b0 + tid < B) loglik[b0 + tid] = out;
-        }
-        __syncthreads();
+        const int b0 = tile.b0, Fmax = tile.Fmax;
         bool bad[G];
         float gw[G];                                                     // g_b of an item that counts, else 0
 #pragma unroll

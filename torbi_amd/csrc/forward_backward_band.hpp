@@ -110,71 +110,91 @@ __global__ __launch_bounds__(64) void fb_band_verify_kernel(const float *__restr
     if (broken) *flag = 1;
 }
 
-// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, S, halo) ----
-// (counts_band.hpp's fb_band_counts_kernel repeats the passes below and promises the same bits of gamma, c_t and L: a change
-// to the ownership, the reductions or the order of the arithmetic here has to be made there too;
-// tests/test_counts_band_gpu.py compares the two bit for bit)
+// diagonal loads in flight per band sum of a tile of G items
+constexpr int band_unroll(int G) { return G <= 2 ? 8 : (G <= 4 ? 4 : 2); }
+
+// ---- the pieces fb_band_kernel, fb_band_counts_kernel (counts_band.hpp) and fb_band_filter_kernel (sample_band.hpp) share:
+// this one definition of the ownership, the reductions and the order of the arithmetic fixes the bits of a_t, c_t and L of
+// all three ----
+
+// One tile of G items in the dynamic LDS of a workgroup (lds_bytes above), and the frames of its items.
 template <int G>
-__global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
-                                                           const float *__restrict__ initial, const float *__restrict__ Df,
-                                                           const float *__restrict__ Db, const float *__restrict__ m,
-                                                           float *__restrict__ cbuf, const int32_t *__restrict__ flag,
-                                                           float *__restrict__ post, float *__restrict__ loglik, float ebg,
-                                                           int reach_left, int reach_right, int W, int Sd, int B, int T,
-                                                           int S) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int halo = reach_left > reach_right ? reach_left : reach_right, stride = row_stride(S, halo);
-    double *lsum = reinterpret_cast<double *>(lds_raw);                 // [G][16]
-    double *Ls = lsum + G * kWaves;                                      // [G] (L as the float the caller gets)
-    float *rows = reinterpret_cast<float *>(Ls + G);                     // [2][G][stride]
-    float *part = rows + (size_t)2 * G * stride;                         // [2][G][16]
+struct Tile {
+    double *lsum, *Ls;                       // [G][16] wave sums of L; [G] L as the float the caller gets
+    float *rows, *part;                      // [2][G][stride]; [2][G][16] wave sums of a row
+    int halo, stride, b0, Fmax, F[G];
+
+    __device__ __forceinline__ Tile(unsigned char *lds, int reach_left, int reach_right, int S) {
+        halo = reach_left > reach_right ? reach_left : reach_right;
+        stride = row_stride(S, halo);
+        lsum = reinterpret_cast<double *>(lds);
+        Ls = lsum + G * kWaves;
+        rows = reinterpret_cast<float *>(Ls + G);
+        part = rows + (size_t)2 * G * stride;
+    }
+};
+
+// items b0 .. b0 + G - 1: their frames, and zero rows (no barrier: the caller's next one covers the rows)
+template <int G>
+__device__ __forceinline__ void tile_begin(Tile<G> &tile, const int32_t *__restrict__ frames, int b0, int B, int T) {
+    tile.b0 = b0;
+    tile.Fmax = 1;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        tile.F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;  // (0: an item beyond the batch never takes a step)
+        tile.Fmax = tile.F[g] > tile.Fmax ? tile.F[g] : tile.Fmax;
+    }
+    for (int e = threadIdx.x; e < 2 * G * tile.stride; e += kThreads) tile.rows[e] = 0.f;  // (the halos stay zero all tile long)
+}
+
+// rows an item does not have
+template <int G>
+__device__ __forceinline__ void zero_absent_rows(const Tile<G> &tile, float *__restrict__ post, int B, int T, int S) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (tile.b0 + g >= B) continue;
+        float *out = post + (size_t)(tile.b0 + g) * T * S;
+        for (size_t e = (size_t)tile.F[g] * S + threadIdx.x; e < (size_t)T * S; e += kThreads) out[e] = 0.f;
+    }
+}
+
+// c_t of every item of the tile from the wave sums of frame t; thread 0 stores it for the later passes and L
+template <int G>
+__device__ __forceinline__ void row_sums(const Tile<G> &tile, int t, float *__restrict__ cbuf, int T, float *c) {
+    const float *p = tile.part + (size_t)(t & 1) * G * kWaves;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        c[g] = sum16(p[g * kWaves + (threadIdx.x & 15)]);
+        if (threadIdx.x == 0 && t < tile.F[g]) cbuf[(size_t)(tile.b0 + g) * T + t] = c[g];
+    }
+}
+
+// ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1}; a_t to `out` [B][T][S], c_t to cbuf; ends
+// behind a barrier, with every c_t of the tile stored ----
+template <int G>
+__device__ __forceinline__ void forward_pass(const Tile<G> &tile, const float *__restrict__ obs,
+                                             const float *__restrict__ initial, const float *__restrict__ Df,
+                                             const float *__restrict__ m, float *__restrict__ cbuf, float *__restrict__ out,
+                                             float ebg, int reach_left, int W, int Sd, int T, int S) {
+    constexpr int kUnroll = band_unroll(G);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b0 = blockIdx.x * G;
-    constexpr int kUnroll = G <= 2 ? 8 : (G <= 4 ? 4 : 2);          // diagonal loads in flight per band sum
-
-    int F[G], Fmax = 1;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;       // (0: an item beyond the batch never takes a step)
-        Fmax = F[g] > Fmax ? F[g] : Fmax;
-    }
-    for (int e = tid; e < 2 * G * stride; e += kThreads) rows[e] = 0.f;  // (the halos stay zero for the whole call)
-    // rows an item does not have
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        if (b0 + g >= B) continue;
-        float *out = post + (size_t)(b0 + g) * T * S;
-        for (size_t e = (size_t)F[g] * S + tid; e < (size_t)T * S; e += kThreads) out[e] = 0.f;
-    }
-    __syncthreads();
-
-    // c_t of every item of the tile from the wave sums of frame t; thread 0 stores it for the backward pass and L
-    auto row_sums = [&](int t, float *c) {
-        const float *p = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            c[g] = sum16(p[g * kWaves + (lane & 15)]);
-            if (tid == 0 && t < F[g]) cbuf[(size_t)(b0 + g) * T + t] = c[g];
-        }
-    };
-
-    // ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1} ----
-    for (int t = 0; t < Fmax; ++t) {
-        float *cur = rows + (size_t)(t & 1) * G * stride;
-        const float *prev = rows + (size_t)((t & 1) ^ 1) * G * stride;
+    const int halo = tile.halo, stride = tile.stride, b0 = tile.b0;
+    for (int t = 0; t < tile.Fmax; ++t) {
+        float *cur = tile.rows + (size_t)(t & 1) * G * stride;
+        const float *prev = tile.rows + (size_t)((t & 1) ^ 1) * G * stride;
         float cprev[G], acc[G];
-        if (t > 0) row_sums(t - 1, cprev);
+        if (t > 0) row_sums(tile, t - 1, cbuf, T, cprev);
 #pragma unroll
         for (int g = 0; g < G; ++g) acc[g] = 0.f;
         float mt[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
+        for (int g = 0; g < G; ++g) mt[g] = t < tile.F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
         for (int j = tid; j < S; j += kThreads) {
             float s[G], ot[G];
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 s[g] = 0.f;
-                ot[g] = t < F[g] ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;    // (in flight during the band sum)
+                ot[g] = t < tile.F[g] ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;    // (in flight during the band sum)
             }
             if (t > 0) {
                 const float *d = Df + j;
@@ -188,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restri
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                if (t >= F[g]) continue;
+                if (t >= tile.F[g]) continue;
                 const size_t row = (size_t)(b0 + g) * T + t;
                 const float o = ot[g], mm = mt[g];
                 float v;
@@ -200,11 +220,11 @@ __global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restri
                     v = c == 0.f ? u * 0.f : u / c;                      // (after a zero-probability frame: 0, or NaN from NaN)
                 }
                 cur[g * stride + halo + j] = v;
-                post[row * S + j] = v;
+                out[row * S + j] = v;
                 acc[g] += v;
             }
         }
-        float *p = part + (size_t)(t & 1) * G * kWaves;
+        float *p = tile.part + (size_t)(t & 1) * G * kWaves;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const float a = wave_sum(acc[g]);
@@ -214,31 +234,62 @@ __global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restri
     }
     {
         float c[G];
-        row_sums(Fmax - 1, c);
+        row_sums(tile, tile.Fmax - 1, cbuf, T, c);
     }
     __syncthreads();                                                     // (c_t written by thread 0 is read by all below)
+}
 
-    // ---- L = sum_{t<F} (log c_t + m_t) in fp64; NaN when the sum is NaN or +inf, or the promise is broken ----
+// ---- L = sum_{t<F} (log c_t + m_t) in fp64; NaN when the sum is NaN or +inf, or the promise is broken.  To loglik and, as
+// the float the caller gets, to tile.Ls: a caller that reads Ls puts a barrier in front ----
+template <int G>
+__device__ __forceinline__ void log_likelihood(const Tile<G> &tile, const float *__restrict__ m, const float *__restrict__ cbuf,
+                                               const int32_t *__restrict__ flag, float *__restrict__ loglik, int B, int T) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         double a = 0.;
-        for (int t = tid; t < F[g]; t += kThreads) {
-            const size_t row = (size_t)(b0 + g) * T + t;
+        for (int t = tid; t < tile.F[g]; t += kThreads) {
+            const size_t row = (size_t)(tile.b0 + g) * T + t;
             a += log((double)cbuf[row]) + (double)m[row];
         }
         a = wave_sum(a);
-        if (lane == 0) lsum[g * kWaves + wave] = a;
+        if (lane == 0) tile.lsum[g * kWaves + wave] = a;
     }
     __syncthreads();
     if (tid < G) {
         double L = 0.;
-        for (int w = 0; w < kWaves; ++w) L += lsum[tid * kWaves + w];
+        for (int w = 0; w < kWaves; ++w) L += tile.lsum[tid * kWaves + w];
         float out = (L != L || L == (double)INFINITY) ? NAN : (float)L;
         if (*flag != 0) out = NAN;
-        Ls[tid] = (double)out;
-        if (b0 + tid < B) loglik[b0 + tid] = out;
+        tile.Ls[tid] = (double)out;
+        if (tile.b0 + tid < B) loglik[tile.b0 + tid] = out;
     }
+}
+
+// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, S, halo) ----
+template <int G>
+__global__ __launch_bounds__(kThreads) void fb_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
+                                                           const float *__restrict__ initial, const float *__restrict__ Df,
+                                                           const float *__restrict__ Db, const float *__restrict__ m,
+                                                           float *__restrict__ cbuf, const int32_t *__restrict__ flag,
+                                                           float *__restrict__ post, float *__restrict__ loglik, float ebg,
+                                                           int reach_left, int reach_right, int W, int Sd, int B, int T,
+                                                           int S) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Tile<G> tile(lds_raw, reach_left, reach_right, S);
+    tile_begin(tile, frames, blockIdx.x * G, B, T);
+    zero_absent_rows(tile, post, B, T, S);
     __syncthreads();
+    forward_pass(tile, obs, initial, Df, m, cbuf, post, ebg, reach_left, W, Sd, T, S);
+    log_likelihood(tile, m, cbuf, flag, loglik, B, T);
+    __syncthreads();
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int halo = tile.halo, stride = tile.stride, b0 = tile.b0, Fmax = tile.Fmax;
+    const int *F = tile.F;
+    float *const rows = tile.rows, *const part = tile.part;
+    const double *Ls = tile.Ls;
+    constexpr int kUnroll = band_unroll(G);
     bool bad[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) bad[g] = !isfinite(Ls[g]);

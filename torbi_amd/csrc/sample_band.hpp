@@ -9,11 +9,11 @@
 // -- the band minus the constant, then the constant over everything: the mixture the band split of the filter uses --, and
 // j_t is the state of the chosen slot.  Z = Zband + ebg * c_t with c_t as the filter stored it.
 //
-// fb_band_filter_kernel<G> is the forward half of fb_band_kernel<G>: it leaves a_t in the filter rows [B][T][S] and c_t in
-// cbuf.  sample_band_backward_kernel<VEC> then draws every path, one wave per draw: lane k owns in-band slot lo + k (at most
-// 64 of them), so a frame costs one load of a_t[lo .. hi] and one of A[j][lo .. hi], both issued as soon as j is known.  The
-// whole row is read only at frame F-1 and where u Z falls behind the band part (ebg != 0), with sample.hpp's streamed search.
-// Vector stores only, no atomics, no LDS in the sampler, nothing waits across workgroups.
+// fb_band_filter_kernel<G> is the forward half of fb_band_kernel<G>, the same functions: it leaves a_t in the filter rows
+// [B][T][S] and c_t in cbuf.  sample_band_backward_kernel<VEC> then draws every path, one wave per draw: lane k owns in-band
+// slot lo + k (at most 64 of them), so a frame costs one load of a_t[lo .. hi] and one of A[j][lo .. hi], both issued as soon
+// as j is known.  The whole row is read only at frame F-1 and where u Z falls behind the band part (ebg != 0), with
+// sample.hpp's streamed search.  Vector stores only, no atomics, no LDS in the sampler, nothing waits across workgroups.
 #pragma once
 
 #include "forward_backward_band.hpp"
@@ -36,9 +36,6 @@ inline SampleLayout sample_layout(char *base, int B, int T, int S, int reach_lef
 }
 
 // ---- the forward pass of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, S, halo) ----
-// (this repeats the forward pass and the log-likelihood of fb_band_kernel and promises the same bits of a_t, c_t and L: a
-// change to the ownership, the reductions or the order of the arithmetic there has to be made here too;
-// tests/test_sample_band_gpu.py compares L bit for bit)
 template <int G>
 __global__ __launch_bounds__(kThreads) void fb_band_filter_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
                                                                   const float *__restrict__ initial, const float *__restrict__ Df,
@@ -47,113 +44,11 @@ __global__ __launch_bounds__(kThreads) void fb_band_filter_kernel(const float *_
                                                                   float *__restrict__ loglik, float ebg, int reach_left,
                                                                   int reach_right, int W, int Sd, int B, int T, int S) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int halo = reach_left > reach_right ? reach_left : reach_right, stride = row_stride(S, halo);
-    double *lsum = reinterpret_cast<double *>(lds_raw);                 // [G][16]
-    double *Ls = lsum + G * kWaves;                                      // [G] (unused here: the layout is fb_band_kernel's)
-    float *rows = reinterpret_cast<float *>(Ls + G);                     // [2][G][stride]
-    float *part = rows + (size_t)2 * G * stride;                         // [2][G][16]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b0 = blockIdx.x * G;
-    constexpr int kUnroll = G <= 2 ? 8 : (G <= 4 ? 4 : 2);          // diagonal loads in flight per band sum
-
-    int F[G], Fmax = 1;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;       // (0: an item beyond the batch never takes a step)
-        Fmax = F[g] > Fmax ? F[g] : Fmax;
-    }
-    for (int e = tid; e < 2 * G * stride; e += kThreads) rows[e] = 0.f;  // (the halos stay zero for the whole call)
+    Tile<G> tile(lds_raw, reach_left, reach_right, S);
+    tile_begin(tile, frames, blockIdx.x * G, B, T);
     __syncthreads();
-
-    // c_t of every item of the tile from the wave sums of frame t; thread 0 stores it for the sampler and L
-    auto row_sums = [&](int t, float *c) {
-        const float *p = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            c[g] = sum16(p[g * kWaves + (lane & 15)]);
-            if (tid == 0 && t < F[g]) cbuf[(size_t)(b0 + g) * T + t] = c[g];
-        }
-    };
-
-    // ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1} ----
-    for (int t = 0; t < Fmax; ++t) {
-        float *cur = rows + (size_t)(t & 1) * G * stride;
-        const float *prev = rows + (size_t)((t & 1) ^ 1) * G * stride;
-        float cprev[G], acc[G];
-        if (t > 0) row_sums(t - 1, cprev);
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = 0.f;
-        float mt[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
-        for (int j = tid; j < S; j += kThreads) {
-            float s[G], ot[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                s[g] = 0.f;
-                ot[g] = t < F[g] ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;    // (in flight during the band sum)
-            }
-            if (t > 0) {
-                const float *d = Df + j;
-                const float *x = prev + halo - reach_left + j;
-#pragma unroll kUnroll
-                for (int k = 0; k < W; ++k) {
-                    const float dk = d[(size_t)k * Sd];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) s[g] = fmaf(dk, x[g * stride + k], s[g]);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if (t >= F[g]) continue;
-                const size_t row = (size_t)(b0 + g) * T + t;
-                const float o = ot[g], mm = mt[g];
-                float v;
-                if (t == 0) {
-                    v = expf(initial[j] + o - mm);
-                } else {
-                    const float e = expf(o - mm), c = cprev[g];
-                    const float u = e * (ebg != 0.f ? fmaf(ebg, c, s[g]) : s[g]);
-                    v = c == 0.f ? u * 0.f : u / c;                      // (after a zero-probability frame: 0, or NaN from NaN)
-                }
-                cur[g * stride + halo + j] = v;
-                filter[row * S + j] = v;
-                acc[g] += v;
-            }
-        }
-        float *p = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float a = wave_sum(acc[g]);
-            if (lane == 0) p[g * kWaves + wave] = a;
-        }
-        __syncthreads();
-    }
-    {
-        float c[G];
-        row_sums(Fmax - 1, c);
-    }
-    __syncthreads();                                                     // (c_t written by thread 0 is read by all below)
-
-    // ---- L = sum_{t<F} (log c_t + m_t) in fp64; NaN when the sum is NaN or +inf, or the promise is broken ----
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        double a = 0.;
-        for (int t = tid; t < F[g]; t += kThreads) {
-            const size_t row = (size_t)(b0 + g) * T + t;
-            a += log((double)cbuf[row]) + (double)m[row];
-        }
-        a = wave_sum(a);
-        if (lane == 0) lsum[g * kWaves + wave] = a;
-    }
-    __syncthreads();
-    if (tid < G) {
-        double L = 0.;
-        for (int w = 0; w < kWaves; ++w) L += lsum[tid * kWaves + w];
-        float out = (L != L || L == (double)INFINITY) ? NAN : (float)L;
-        if (*flag != 0) out = NAN;
-        if (b0 + tid < B) loglik[b0 + tid] = out;
-    }
+    forward_pass(tile, obs, initial, Df, m, cbuf, filter, ebg, reach_left, W, Sd, T, S);
+    log_likelihood(tile, m, cbuf, flag, loglik, B, T);
 }
 
 // ---- backward sampling on the band, every frame in one launch: one wave per draw, grid (B, ceil(N / sample::kWaves)) ----

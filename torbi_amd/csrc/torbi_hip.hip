@@ -2748,6 +2748,47 @@ int torbi_hip_sample_uniform(const float *observation, const int32_t *batch_fram
 
 // ---- forward-backward on a band with one constant outside it (forward_backward_band.hpp) ----
 
+// The checks of a band entry, in the order every one of them answers.  `pointers`: none of the entry's pointers is null;
+// `covers` and `need`: what its own _covers and _workspace_bytes say; `valid` and `in_range`: what it asks beside the shape
+// and the band.  TORBI_HIP_OK at B == 0 too, where the entry returns without a launch.
+static int fb_band_args_ok(int B, int T, int S, int reach_left, int reach_right, bool pointers, int covers, size_t need,
+                           size_t workspace_bytes, bool valid = true, bool in_range = true) {
+    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0 || !valid) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!pointers) return TORBI_HIP_EINVAL;
+    if (!fb_shape_in_range(B, T, S) || !in_range) return TORBI_HIP_ERANGE;
+    if (!covers) return TORBI_HIP_EUNSUPPORTED;
+    if (workspace_bytes < need) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+// What every band entry does first: switch to the device, then launch the diagonals of E - ebg with the promise flag, the
+// check of the promise and the row maxima.  Holds the device for the entry's own launches; hands back ebg = exp(background)
+// (0 for -inf) and the halo of the LDS rows.
+struct BandPreamble {
+    DeviceGuard guard;
+    float ebg;
+    int halo;
+    hipError_t err;
+    BandPreamble(const fbb::Layout &l, const float *observation, const int32_t *batch_frames, const float *transition,
+                 const float *initial, float background, int B, int T, int S, int device, hipStream_t st)
+        : guard(device), ebg(background == -INFINITY ? 0.f : expf(background)), halo(std::max(l.reach_left, l.reach_right)),
+          err(guard.err) {
+        if (err != hipSuccess) return;
+        const size_t cells = (size_t)l.W * l.Sd;
+        hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0,
+                           st, transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
+        if ((err = hipGetLastError()) != hipSuccess) return;
+        hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
+                           l.reach_right, S);
+        if ((err = hipGetLastError()) != hipSuccess) return;
+        const size_t rows = (size_t)B * T;
+        hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                           initial, l.m, B, T, S);
+        err = hipGetLastError();
+    }
+};
+
 // Items per workgroup of fb_band_kernel<G>: as many as the LDS rows let share one load of every diagonal, but no fewer
 // workgroups than compute units while there are items for them.
 static int fb_band_tile(int B, int S, int halo, int cus) {
@@ -2773,45 +2814,25 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
                                     const float *initial, int reach_left, int reach_right, float background,
                                     float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B,
                                     int T, int S, int device, void *stream) {
-    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
-    if (B == 0) return TORBI_HIP_OK;
-    if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !workspace)
-        return TORBI_HIP_EINVAL;
-    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
-    if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device))
-        return TORBI_HIP_EUNSUPPORTED;
-    if (workspace_bytes < torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right))
-        return TORBI_HIP_EWORKSPACE;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && workspace,
+        torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const fbb::Layout l = fbb::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
-    float *const Df = l.Df, *const Db = l.Db, *const m = l.m, *const cbuf = l.c;
-    int32_t *const flag = l.flag;
-    const float ebg = background == -INFINITY ? 0.f : expf(background);
-    hipError_t e;
-    {
-        const size_t n = (size_t)l.W * l.Sd;
-        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, Df, Db, flag, ebg,
-                           l.reach_left, l.W, l.Sd, S);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, flag, background, l.reach_left,
-                       l.reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, m, B, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const int halo = std::max(l.reach_left, l.reach_right);
+    const BandPreamble pre(l, observation, batch_frames, transition, initial, background, B, T, S, device, st);
+    if (pre.err != hipSuccess) return (int)pre.err;
+    const float ebg = pre.ebg;
+    const int halo = pre.halo;
     const int G = fb_band_tile(B, S, halo, cu_count(device));
     const dim3 grid((B + G - 1) / G);
     const size_t lds = fbb::lds_bytes(G, S, halo);
     by_value<8, 4, 2, 1>(G, [&](auto g) {
         auto *kernel = &fbb::fb_band_kernel<decltype(g)::value>;
-        hipLaunchKernelGGL(kernel, grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, Df, Db, m, cbuf, flag,
-                           posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S);
+        hipLaunchKernelGGL(kernel, grid, dim3(fbb::kThreads), lds, st, observation, batch_frames, initial, l.Df, l.Db, l.m, l.c,
+                           l.flag, posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S);
     });
     return (int)hipGetLastError();
 }
@@ -2844,34 +2865,20 @@ int torbi_hip_forward_backward_counts_band(const float *observation, const int32
                                            const float *item_weights, float *posterior_out, float *loglik_out,
                                            float *band_counts_out, float *initial_counts_out, void *workspace,
                                            size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
-    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
-    if (B == 0) return TORBI_HIP_OK;
-    if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !band_counts_out ||
-        !initial_counts_out || !workspace)
-        return TORBI_HIP_EINVAL;
-    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
-    if (!torbi_hip_forward_backward_counts_band_covers(B, T, S, reach_left, reach_right, background, device))
-        return TORBI_HIP_EUNSUPPORTED;
-    if (workspace_bytes < torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right))
-        return TORBI_HIP_EWORKSPACE;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && band_counts_out &&
+            initial_counts_out && workspace,
+        torbi_hip_forward_backward_counts_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const fbb::CountsLayout l = fbb::counts_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
-    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    const BandPreamble pre(l, observation, batch_frames, transition, initial, background, B, T, S, device, st);
+    if (pre.err != hipSuccess) return (int)pre.err;
+    const float ebg = pre.ebg;
+    const int halo = pre.halo;
     hipError_t e;
-    const size_t cells = (size_t)l.W * l.Sd;
-    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
-                       transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
-                       l.reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, l.m, B, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const int halo = std::max(l.reach_left, l.reach_right);
     const int G = fb_band_counts_tile(B, S, halo, l.W, cu_count(device));
     const int grid = std::min((B + G - 1) / G, fbb::kCountsWorkgroups);           // (<= l.planes)
     const size_t lds = fbb::lds_bytes(G, S, halo) + fbb::plane_bytes(l.W, S);
@@ -2910,31 +2917,20 @@ int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames,
                           int reach_left, int reach_right, float background, const float *uniforms, int32_t *indices_out,
                           float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int N, int device,
                           void *stream) {
-    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0 || N < 1 || N > sample::kMaxDraws) return TORBI_HIP_EINVAL;
-    if (B == 0) return TORBI_HIP_OK;
-    if (!observation || !batch_frames || !transition || !initial || !uniforms || !indices_out || !loglik_out || !workspace)
-        return TORBI_HIP_EINVAL;
-    if (!fb_shape_in_range(B, T, S) || (size_t)B * N * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
-    if (!torbi_hip_sample_band_covers(B, T, S, N, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
-    if (workspace_bytes < torbi_hip_sample_band_workspace_bytes(B, T, S, N, reach_left, reach_right)) return TORBI_HIP_EWORKSPACE;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return (int)guard.err;
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && uniforms && indices_out && loglik_out && workspace,
+        torbi_hip_sample_band_covers(B, T, S, N, reach_left, reach_right, background, device),
+        torbi_hip_sample_band_workspace_bytes(B, T, S, N, reach_left, reach_right), workspace_bytes,
+        N >= 1 && N <= sample::kMaxDraws, (size_t)B * N * T <= (size_t)1 << 32);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const fbb::SampleLayout l = fbb::sample_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
-    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    const BandPreamble pre(l, observation, batch_frames, transition, initial, background, B, T, S, device, st);
+    if (pre.err != hipSuccess) return (int)pre.err;
+    const float ebg = pre.ebg;
+    const int halo = pre.halo;
     hipError_t e;
-    const size_t cells = (size_t)l.W * l.Sd;
-    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
-                       transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
-                       l.reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, l.m, B, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    const int halo = std::max(l.reach_left, l.reach_right);
     const int G = fb_band_tile(B, S, halo, cu_count(device));            // (fb_band_kernel's tile: the same LDS rows)
     by_value<8, 4, 2, 1>(G, [&](auto g) {
         auto *kernel = &fbb::fb_band_filter_kernel<decltype(g)::value>;

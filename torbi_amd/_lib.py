@@ -239,7 +239,6 @@ def check(code, what='torbi_hip call'):
 def launch(device, need=None, workspace=None):
     """What a C entry that runs on HIP `device` takes besides its tensors: (workspace, device index, current stream as
     c_void_p).  With `need` bytes the workspace is the caller's, checked, or a fresh uint8 tensor; without, None."""
-    import torch
     if need is not None:
         if workspace is None:
             workspace = torch.empty((need,), dtype=torch.uint8, device=device)
@@ -248,6 +247,32 @@ def launch(device, need=None, workspace=None):
             raise RuntimeError(f'workspace must be a contiguous uint8 tensor of >= {need} bytes on {device}')
     index = device.index if device.index is not None else torch.cuda.current_device()
     return workspace, index, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def run(name, observation, frames, inputs, outputs, need, dims, workspace=None):
+    """One call of a C entry of the form NAME(observation, batch_frames, inputs..., outputs..., workspace, workspace_bytes,
+    dims..., device, stream) on the device of `observation` (float32, contiguous); returns `outputs`.  `frames` goes there
+    as contiguous int32 and a tensor among `inputs`, which are in the entry's order, as contiguous float32 -- one already
+    in place is not copied --, a number or None as it is.  `need`: (the entry that answers the workspace's size, its
+    arguments); `workspace`: the caller's, checked, else a fresh one.  An empty batch (dims[0] == 0) launches nothing."""
+    if dims[0] == 0:
+        return outputs
+    lib = load()
+    device = observation.device
+    workspace, index, stream = launch(device, getattr(lib, need[0])(*need[1]), workspace)
+    frames = frames.to(device, torch.int32).contiguous()
+    args = [observation.data_ptr(), frames.data_ptr()]
+    held = []                       # (a moved copy lives until the call is queued)
+    for v in inputs:
+        if isinstance(v, torch.Tensor):
+            v = v.to(device, torch.float32).contiguous()
+            held.append(v)
+            v = v.data_ptr()
+        args.append(v)
+    for t in outputs:
+        args.append(t.data_ptr())
+    check(getattr(lib, name)(*args, workspace.data_ptr(), workspace.numel(), *dims, index, stream), name)
+    return outputs
 
 
 def build_cpu(force=False, verbose=False):

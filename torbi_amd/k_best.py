@@ -18,16 +18,16 @@ route on the device (csrc/k_best_band.hpp behind torbi_hip_k_best_band*; KBEST.m
 launch, a state's list from its in-band prev-states unless an out-of-band candidate could enter it.  `route` chooses; the
 outputs are the same bits either way.
 """
-import ctypes
 import math
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs, state, viterbi
+from . import _lib, band_route, inputs
+from .posterior import _banded_operands, _shapes
 
 MAX_K = 32
-ROUTES = ('auto', 'dense', 'band')
+ROUTES = band_route.ROUTES
 # candidates per chunk of next-states on the host route (4-byte values, 8-byte sort indices)
 _HOST_CHUNK_ELEMENTS = 1 << 25
 
@@ -43,12 +43,6 @@ def _check_k(k) -> int:
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
         raise RuntimeError(f'k must be an integer in [1, {MAX_K}]; got {k!r}')
     return k
-
-
-def _check_route(route) -> str:
-    if route not in ROUTES:
-        raise ValueError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
-    return route
 
 
 def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: Optional[torch.Tensor],
@@ -81,7 +75,7 @@ def decode_k_best(observation: torch.Tensor, batch_frames: Optional[torch.Tensor
         indices.
     """
     k = _check_k(k)
-    route = _check_route(route)
+    band_route.check_route(route, ValueError)
     if initial is None:
         raise RuntimeError('decode_k_best needs an initial distribution')
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
@@ -110,7 +104,7 @@ def best_paths(observation: torch.Tensor, k: int, batch_frames: Optional[torch.T
         (indices (batch, k, frames) int32, scores (batch, k) float32) on the compute device, as `decode_k_best`.
     """
     k = _check_k(k)
-    route = _check_route(route)
+    band_route.check_route(route, ValueError)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
@@ -130,44 +124,27 @@ def decode_k_best_banded_workspace_bytes(B: int, T: int, S: int, k: int, reach_l
 
 def _covered(B, T, S, k, reach_left, reach_right, background, index=0) -> bool:
     """torbi_hip_k_best_band_covers: the band route takes this shape, k, band and background."""
-    return bool(_lib.load().torbi_hip_k_best_band_covers(B, T, S, k, int(reach_left), int(reach_right),
-                                                         ctypes.c_float(background), index))
+    return bool(_lib.load().torbi_hip_k_best_band_covers(B, T, S, k, int(reach_left), int(reach_right), background, index))
 
 
 # (k, diagonals of 1440 states) up to which tools/k_best_probe.py measured the band route faster than the dense one by more
 # than the dense route's spread (KBEST.md, "Band route"): k <= 4 up to 175 diagonals, k <= 8 up to 23; at k = 8 and 175
 # diagonals the band route is the slower one
 _AUTO_BAND = ((4, 175), (8, 23))
-_MEASURED_STATES = 1440
 
 
 def _band_pays(k: int, states: int, reach_left: int, reach_right: int) -> bool:
     """Where 'auto' takes a covered band: for a (k, width) inside what the probe measured faster, the width as the band's
     share of the matrix.  Anything beyond -- k above 8, a band that holds more than 175 / 1440 of a row -- is not
     measured and stays dense."""
-    width = reach_left + reach_right + 1
-    return any(k <= top and width * _MEASURED_STATES <= diagonals * states for top, diagonals in _AUTO_BAND)
+    return any(k <= top and band_route.share_within(states, reach_left, reach_right, diagonals) for top, diagonals in _AUTO_BAND)
 
 
 def _band_plan(trans: torch.Tensor, original: torch.Tensor, B: int, T: int, S: int, k: int, index: int, look: bool = True):
-    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
-    (`original`: the tensor the look is remembered with), else (None, the reason).  The structure is what
-    `viterbi.band_over` answers -- one look per tensor version; an unseen matrix while a stream is capturing has no band --,
-    the shape what torbi_hip_k_best_band_covers takes.  Without `look` only a structure that is already known counts: the
-    look is a small kernel, a host synchronisation and, the first time, a device allocation."""
-    if not look:
-        known = state.peek(original)
-        if known is None or ('band_over', S) not in known:
-            return None, 'the structure of the matrix is not known yet'
-    over = viterbi.band_over(trans, original, S)
-    if over is None:
-        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
-                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
-                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or finite)')
-    if not _covered(B, T, S, k, over[0], over[1], over[2], index):
-        return None, (f'torbi_hip_k_best_band_covers turns down batch={B}, frames={T}, states={S}, k={k}, reach '
-                      f'{over[0]}/{over[1]}, background {over[2]}')
-    return over, ''
+    """`band_route.plan` for this feature: the shape is what torbi_hip_k_best_band_covers takes; without `look` only a
+    structure that is already known counts."""
+    return band_route.plan(trans, original, _covered, 'torbi_hip_k_best_band_covers', dict(batch=B, frames=T, states=S, k=k),
+                           index, look)
 
 
 def _routed(obs, frames, transition, original, uniform, initial, k, route, workspace=None, look=True):
@@ -179,15 +156,15 @@ def _routed(obs, frames, transition, original, uniform, initial, k, route, works
                            'uniform route decodes; the band route needs a matrix that holds one value outside a band')
     if uniform is None and route != 'dense' and B > 0:
         trans = transition.to(device=obs.device, dtype=torch.float32).contiguous()
-        band, why = _band_plan(trans, original, B, T, S, k, obs.device.index or 0, look or route == 'band')
-        if band is None and route == 'band':
-            raise RuntimeError(f"k-best decoding with route='band': {why}")
-        if band is not None and route == 'auto':
-            fits = workspace is None or workspace.numel() >= decode_k_best_banded_workspace_bytes(B, T, S, k, band[0], band[1])
-            if not fits or not _band_pays(k, S, band[0], band[1]):
-                band = None
+
+        def pays(left, right, background):      # ... and the caller's workspace must also hold the band layout
+            return _band_pays(k, S, left, right) and (
+                workspace is None or workspace.numel() >= decode_k_best_banded_workspace_bytes(B, T, S, k, left, right))
+
+        band = band_route.choose(route, *_band_plan(trans, original, B, T, S, k, obs.device.index or 0, look or route == 'band'),
+                                 pays, "k-best decoding with route='band'")
         if band is not None:
-            return _run_band(obs, frames, trans, initial, k, band[0], band[1], band[2], workspace)
+            return _run_band(obs, frames, trans, initial, k, *band, workspace)
     return _run(obs, frames, transition, uniform, initial, k, workspace)
 
 
@@ -206,8 +183,9 @@ def k_best_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
         raise ValueError(f'transition must be ({states}, {states})')
     device = inputs._compute_device(gpu)
     trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
-    band, _ = _band_plan(trans, transition, int(batch), int(frames), states, k, device.index or 0)
-    return 'band' if band is not None and _band_pays(k, states, band[0], band[1]) else 'dense'
+    band, why = _band_plan(trans, transition, int(batch), int(frames), states, k, device.index or 0)
+    pays = lambda left, right, background: _band_pays(k, states, left, right)
+    return 'dense' if band_route.choose('auto', band, why, pays, 'k_best_route') is None else 'band'
 
 
 def decode_k_best_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -232,65 +210,34 @@ def decode_k_best_banded(observation: torch.Tensor, batch_frames: Optional[torch
     background that is neither NaN nor +inf).
     """
     k = _check_k(k)
-    if transition is None or initial is None:
-        raise RuntimeError('decode_k_best_banded needs a transition matrix and an initial distribution')
-    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    shape = _shapes('decode_k_best_banded', observation, batch_frames, transition, initial)
     if not observation.is_cuda:
         raise RuntimeError('decode_k_best_banded runs on a HIP device; decode_k_best takes host tensors')
-    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
-    if reach_left < 0 or reach_right < 0:
-        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
-    if B > 0 and not _covered(B, T, S, k, reach_left, reach_right, background):
-        raise RuntimeError(f'decode_k_best_banded does not cover B={B}, T={T}, S={S}, k={k}, reach {reach_left}/{reach_right}, '
-                           f'background {background} (decode_k_best takes any matrix)')
-    frames = inputs.frames(batch_frames, B, T, observation.device)
-    return _run_band(observation.to(torch.float32).contiguous(), frames, transition, initial, k, reach_left, reach_right,
-                     background, workspace)
+    obs, frames, left, right, background = _banded_operands(
+        'decode_k_best_banded', 'decode_k_best', _covered, shape, ('k', k), observation, batch_frames, reach_left, reach_right,
+        background, move=False)
+    return _run_band(obs, frames, transition, initial, k, left, right, background, workspace)
+
+
+def _outputs(B, k, T, device):
+    return (torch.empty((B, k, T), dtype=torch.int32, device=device), torch.empty((B, k), dtype=torch.float32, device=device))
 
 
 def _run_band(observation, frames, transition, initial, k, reach_left, reach_right, background, workspace=None):
     """One call of the band route on the device of `observation` (float32, contiguous, log space)."""
     B, T, S = observation.shape
-    device = observation.device
-    lib = _lib.load()
-    indices = torch.empty((B, k, T), dtype=torch.int32, device=device)
-    scores = torch.empty((B, k), dtype=torch.float32, device=device)
-    if B == 0:
-        return indices, scores
-    need = decode_k_best_banded_workspace_bytes(B, T, S, k, reach_left, reach_right)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
-    _lib.check(lib.torbi_hip_k_best_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                                         reach_left, reach_right, ctypes.c_float(background), indices.data_ptr(),
-                                         scores.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, k, index, stream),
-               'torbi_hip_k_best_band')
-    return indices, scores
+    return _lib.run('torbi_hip_k_best_band', observation, frames, (transition, initial, reach_left, reach_right, background),
+                    _outputs(B, k, T, observation.device),
+                    ('torbi_hip_k_best_band_workspace_bytes', (B, T, S, k, reach_left, reach_right)), (B, T, S, k), workspace)
 
 
 def _run(observation, frames, transition, uniform, initial, k, workspace=None):
-    """One call of the HIP route on the device of `observation` (float32, contiguous, log space)."""
+    """One call of the HIP route on the device of `observation` (float32, contiguous, log space).  The uniform route's
+    pointers have no state axis (`decode_k_best_workspace_bytes`)."""
     B, T, S = observation.shape
-    device = observation.device
-    lib = _lib.load()
-    indices = torch.empty((B, k, T), dtype=torch.int32, device=device)
-    scores = torch.empty((B, k), dtype=torch.float32, device=device)
-    if B == 0:
-        return indices, scores
-    need = decode_k_best_workspace_bytes(B, T, S, k, uniform=uniform is not None)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    tail = (indices.data_ptr(), scores.data_ptr(), workspace.data_ptr(), workspace.numel(), B, T, S, k, index, stream)
-    if uniform is not None:
-        _lib.check(lib.torbi_hip_k_best_uniform(observation.data_ptr(), frames.data_ptr(), ctypes.c_float(uniform),
-                                                init.data_ptr(), *tail), 'torbi_hip_k_best_uniform')
-    else:
-        trans = transition.to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(lib.torbi_hip_k_best(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(), *tail),
-                   'torbi_hip_k_best')
-    return indices, scores
+    name, model = ('torbi_hip_k_best', transition) if uniform is None else ('torbi_hip_k_best_uniform', uniform)
+    return _lib.run(name, observation, frames, (model, initial), _outputs(B, k, T, observation.device),
+                    ('torbi_hip_k_best_workspace_bytes', (B, T, S if uniform is None else 1, k)), (B, T, S, k), workspace)
 
 
 def _host(obs, frames, transition, uniform, initial, k):

@@ -12,13 +12,12 @@ matrix that holds one value outside a band csrc/forward_backward_band.hpp behind
 `gpu=None` runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and
 the numbers.
 """
-import ctypes
 import math
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs, viterbi
+from . import _lib, band_route, inputs
 
 
 def forward_backward_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -26,12 +25,16 @@ def forward_backward_workspace_bytes(B: int, T: int, S: int) -> int:
     return int(_lib.load().torbi_hip_forward_backward_workspace_bytes(B, T, S))
 
 
-def _operands(what, observation, batch_frames, transition, initial, item_weights=None):
-    """The front of the operator level (`forward_backward`, `forward_backward_counts`): every check before anything runs,
-    then the observation as contiguous float32 on its HIP device (the current one for a host tensor) and the frames."""
+def _shapes(what, observation, batch_frames, transition, initial):
+    """(B, T, S) of an operator-level call, which needs its matrix and its initial distribution."""
     if transition is None or initial is None:
         raise RuntimeError(f'{what} needs a transition matrix and an initial distribution')
-    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    return inputs.check_shapes(observation, batch_frames, transition, initial)
+
+
+def _moved(what, observation, batch_frames, B, T, item_weights=None):
+    """The observation as contiguous float32 on its HIP device (the current one for a host tensor) and the frames there,
+    after the last checks that come before anything runs."""
     if item_weights is not None and tuple(item_weights.shape) != (B,):
         raise RuntimeError(f'item_weights must have shape ({B},); got {tuple(item_weights.shape)}')
     if not torch.cuda.is_available():
@@ -41,41 +44,36 @@ def _operands(what, observation, batch_frames, transition, initial, item_weights
     return observation.to(device=device, dtype=torch.float32).contiguous(), inputs.frames(batch_frames, B, T, device)
 
 
+def _operands(what, observation, batch_frames, transition, initial, item_weights=None):
+    """The front of the operator level (`forward_backward`, `forward_backward_counts`): every check before anything runs,
+    then the observation as contiguous float32 on its HIP device (the current one for a host tensor) and the frames."""
+    B, T, S = _shapes(what, observation, batch_frames, transition, initial)
+    return _moved(what, observation, batch_frames, B, T, item_weights)
+
+
+def _outputs(B, T, S, device, counts=None):
+    """(posterior, log_likelihood) and, with `counts` rows of a counts matrix, (.., counts (rows, S), initial_counts)."""
+    out = (torch.empty((B, T, S), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.float32, device=device))
+    if counts is not None:
+        out += (torch.zeros((counts, S), dtype=torch.float32, device=device),
+                torch.zeros((S,), dtype=torch.float32, device=device))
+    return out
+
+
 def _run(observation, frames, transition, uniform, initial, workspace=None, counts=False, item_weights=None):
     """One call of the HIP route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
     there: (posterior, log_likelihood), and with `counts` (torbi_hip_forward_backward_counts, dense route only) also
     (transition_counts, initial_counts) weighted by `item_weights` (None = all ones)."""
     B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    device = observation.device
-    lib = _lib.load()
-    out = [torch.empty((B, T, S), dtype=torch.float32, device=device),
-           torch.empty((B,), dtype=torch.float32, device=device)]
-    if counts:
-        out += [torch.zeros((S, S), dtype=torch.float32, device=device),
-                torch.zeros((S,), dtype=torch.float32, device=device)]
-    if B == 0:
-        return tuple(out)
-    need = (lib.torbi_hip_forward_backward_counts_workspace_bytes if counts
-            else lib.torbi_hip_forward_backward_workspace_bytes)(B, T, S)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    head = (observation.data_ptr(), frames.data_ptr())
-    tail = tuple(t.data_ptr() for t in out) + (workspace.data_ptr(), workspace.numel(), B, T, S, index, stream)
     if uniform is not None:
-        _lib.check(lib.torbi_hip_forward_backward_uniform(*head, ctypes.c_float(uniform), init.data_ptr(), *tail),
-                   'torbi_hip_forward_backward_uniform')
+        name, model = 'torbi_hip_forward_backward_uniform', (uniform, initial)
     elif not counts:
-        trans = transition.to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(lib.torbi_hip_forward_backward(*head, trans.data_ptr(), init.data_ptr(), *tail),
-                   'torbi_hip_forward_backward')
+        name, model = 'torbi_hip_forward_backward', (transition, initial)
     else:
-        trans = transition.to(device=device, dtype=torch.float32).contiguous()
-        weights = None if item_weights is None else item_weights.to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(lib.torbi_hip_forward_backward_counts(*head, trans.data_ptr(), init.data_ptr(),
-                                                         None if weights is None else weights.data_ptr(), *tail),
-                   'torbi_hip_forward_backward_counts')
-    return tuple(out)
+        name, model = 'torbi_hip_forward_backward_counts', (transition, initial, item_weights)
+    need = 'torbi_hip_forward_backward_counts_workspace_bytes' if counts else 'torbi_hip_forward_backward_workspace_bytes'
+    return _lib.run(name, observation, frames, model, _outputs(B, T, S, observation.device, S if counts else None),
+                    (need, (B, T, S)), (B, T, S), workspace)
 
 
 def forward_backward(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -104,37 +102,23 @@ def forward_backward_banded_workspace_bytes(B: int, T: int, S: int, reach_left: 
 
 def _covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
     """torbi_hip_forward_backward_band_covers: the band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_band_covers(B, T, S, int(reach_left), int(reach_right),
-                                                                   ctypes.c_float(background), index))
+    return bool(_lib.load().torbi_hip_forward_backward_band_covers(B, T, S, int(reach_left), int(reach_right), background,
+                                                                   index))
 
 
 def _run_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
     """One call of the band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
     `frames` there: (posterior, log_likelihood)."""
     B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    device = observation.device
-    lib = _lib.load()
-    post = torch.empty((B, T, S), dtype=torch.float32, device=device)
-    loglik = torch.empty((B,), dtype=torch.float32, device=device)
-    if B == 0:
-        return post, loglik
-    need = lib.torbi_hip_forward_backward_band_workspace_bytes(B, T, S, reach_left, reach_right)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
-    _lib.check(lib.torbi_hip_forward_backward_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(),
-                                                   init.data_ptr(), reach_left, reach_right, ctypes.c_float(background),
-                                                   post.data_ptr(), loglik.data_ptr(), workspace.data_ptr(),
-                                                   workspace.numel(), B, T, S, index, stream),
-               'torbi_hip_forward_backward_band')
-    return post, loglik
+    return _lib.run('torbi_hip_forward_backward_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
+                    ('torbi_hip_forward_backward_band_workspace_bytes', (B, T, S, reach_left, reach_right)), (B, T, S), workspace)
 
 
 def _counts_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
     """torbi_hip_forward_backward_counts_band_covers: the band counts route takes this shape, band and background."""
     return bool(_lib.load().torbi_hip_forward_backward_counts_band_covers(B, T, S, int(reach_left), int(reach_right),
-                                                                          ctypes.c_float(background), index))
+                                                                          background, index))
 
 
 def _run_band_counts(observation, frames, transition, initial, reach_left, reach_right, background, item_weights=None,
@@ -143,26 +127,33 @@ def _run_band_counts(observation, frames, transition, initial, reach_left, reach
     contiguous, log space) and (B,) int32 `frames` there: (posterior, log_likelihood, band_counts (W, S), initial_counts),
     the counts weighted by `item_weights` (None = all ones)."""
     B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    device = observation.device
-    lib = _lib.load()
     W = min(reach_left, S - 1) + min(reach_right, S - 1) + 1
-    out = (torch.empty((B, T, S), dtype=torch.float32, device=device),
-           torch.empty((B,), dtype=torch.float32, device=device),
-           torch.zeros((W, S), dtype=torch.float32, device=device),
-           torch.zeros((S,), dtype=torch.float32, device=device))
-    if B == 0:
-        return out
-    need = lib.torbi_hip_forward_backward_counts_band_workspace_bytes(B, T, S, reach_left, reach_right)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
-    weights = None if item_weights is None else item_weights.to(device=device, dtype=torch.float32).contiguous()
-    _lib.check(lib.torbi_hip_forward_backward_counts_band(
-        observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(), reach_left, reach_right,
-        ctypes.c_float(background), None if weights is None else weights.data_ptr(), *(t.data_ptr() for t in out),
-        workspace.data_ptr(), workspace.numel(), B, T, S, index, stream), 'torbi_hip_forward_backward_counts_band')
-    return out
+    return _lib.run('torbi_hip_forward_backward_counts_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background, item_weights),
+                    _outputs(B, T, S, observation.device, W),
+                    ('torbi_hip_forward_backward_counts_band_workspace_bytes', (B, T, S, reach_left, reach_right)), (B, T, S),
+                    workspace)
+
+
+def _banded_operands(what, dense, covers, shape, own, observation, batch_frames, reach_left, reach_right, background,
+                     item_weights=None, move=True):
+    """The front of the stated-band entries (`forward_backward_banded`, `forward_backward_counts_banded`,
+    `forward_sample_banded`, `decode_k_best_banded`) behind `_shapes` and the entry's own check, in one order: the band, then
+    `covers(B, T, S, [the entry's own argument,] reach_left, reach_right, background)`, then the device operands of `_moved`
+    -- or without `move` the observation where it is (an entry that refuses host tensors).  `own` is () or (name, value) of
+    that argument, `dense` names the entry that takes any matrix.  Returns (observation, frames, reach_left, reach_right,
+    background)."""
+    B, T, S = shape
+    reach_left, reach_right, background = band_route.stated(reach_left, reach_right, background)
+    if B > 0 and not covers(B, T, S, *own[1:], reach_left, reach_right, background):
+        said = f' {own[0]}={own[1]},' if own else ''
+        raise RuntimeError(f'{what} does not cover B={B}, T={T}, S={S},{said} reach {reach_left}/{reach_right}, '
+                           f'background {background} ({dense} takes any matrix)')
+    if move:
+        obs, frames = _moved(what, observation, batch_frames, B, T, item_weights)
+    else:
+        obs, frames = observation.to(torch.float32).contiguous(), inputs.frames(batch_frames, B, T, observation.device)
+    return obs, frames, reach_left, reach_right, background
 
 
 def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -188,30 +179,20 @@ def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[to
     Raises where the band route does not cover the call (torbi_hip_forward_backward_band_covers: up to 4096 states, at most
     64 in-band entries in a matrix row, a background that is neither NaN nor +inf).
     """
-    if transition is None or initial is None:
-        raise RuntimeError('forward_backward_banded needs a transition matrix and an initial distribution')
-    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
-    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
-    if reach_left < 0 or reach_right < 0:
-        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
-    if B > 0 and not _covered(B, T, S, reach_left, reach_right, background):
-        raise RuntimeError(f'forward_backward_banded does not cover B={B}, T={T}, S={S}, reach {reach_left}/{reach_right}, '
-                           f'background {background} (forward_backward takes any matrix)')
-    obs, frames = _operands('forward_backward_banded', observation, batch_frames, transition, initial)
-    return _run_band(obs, frames, transition, initial, reach_left, reach_right, background, workspace)
+    shape = _shapes('forward_backward_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands('forward_backward_banded', 'forward_backward', _covered, shape, (),
+                                                            observation, batch_frames, reach_left, reach_right, background)
+    return _run_band(obs, frames, transition, initial, left, right, background, workspace)
 
 
-def _band(trans, original, B, T, S, index):
-    """(reach_left, reach_right, background) when the band route would take the prepared device matrix `trans` (`original`:
-    the caller's tensor, which the look is remembered with), else None.  The structure is what `viterbi.band_over` answers
-    -- one look per tensor version; an unseen matrix while a stream is capturing has no band -- and the shape what
-    torbi_hip_forward_backward_band_covers takes."""
-    if B < 1:
+def _band(route, trans, original, B, T, S, index):
+    """(reach_left, reach_right, background) where `route` sends the prepared device matrix `trans` to the band route
+    ('auto' takes every band torbi_hip_forward_backward_band_covers takes), else None."""
+    if route == 'dense':
         return None
-    over = viterbi.band_over(trans, original, S)
-    if over is None or not _covered(B, T, S, over[0], over[1], over[2], index):
-        return None
-    return over
+    plan = band_route.plan(trans, original, _covered, 'torbi_hip_forward_backward_band_covers', dict(batch=B, frames=T, states=S),
+                           index)
+    return band_route.choose(route, *plan, None, "state_posteriors(route='band')")
 
 
 def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
@@ -227,7 +208,7 @@ def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int,
     if device.type == 'cpu':
         return 'dense'
     trans = inputs._prepared_transition(transition, log_probs, device)
-    return 'dense' if _band(trans, transition, int(batch), int(frames), states, device.index) is None else 'band'
+    return 'dense' if _band('auto', trans, transition, int(batch), int(frames), states, device.index or 0) is None else 'band'
 
 
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -252,8 +233,7 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
         t >= batch_frames[b] are 0; an item of total probability 0 has log-likelihood -inf and NaN rows, an item that reads
         a NaN or +inf has NaN for both.
     """
-    if route not in ('auto', 'dense', 'band'):
-        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+    band_route.check_route(route)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
@@ -263,35 +243,30 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     if gpu is None:
         gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
         return gamma.to(torch.float32), L.to(torch.float32)
-    if uniform is None and route != 'dense':
-        band = _band(transition, original, B, T, S, device.index)
-        if band is not None:
-            return _run_band(obs, frames, transition, initial, band[0], band[1], band[2])
-        if route == 'band':
-            raise RuntimeError("state_posteriors(route='band'): the transition matrix has no band that "
-                               'forward_backward_banded covers')
+    band = None if uniform is not None else _band(route, transition, original, B, T, S, device.index or 0)
+    if band is not None:
+        return _run_band(obs, frames, transition, initial, *band)
     return _run(obs, frames, transition, uniform, initial)
 
 
-def _host(obs, frames, transition, uniform, initial, weights=None, counts=False):
-    """The scaled recurrence of the HIP route in float64 with torch CPU ops: (gamma, L, X, I), float64.  `uniform` (not
-    None) takes the closed form of a uniform transition matrix.  X (S, S) [next, prev] and I (S,), the expected counts
-    weighted by `weights` (None = all ones), are computed only with `counts` (dense route), else None."""
+def _forward(obs, frames, transition, uniform, initial):
+    """The forward half of the scaled recurrence in float64 with torch CPU ops: (alpha (B, T, S) unnormalised filtered rows,
+    c (B, T) their sums, e (B, T, S) = exp(x - max x), E (S, S) [next, prev], L (B,), F (B,) int64, valid (B, T)).  `uniform`
+    (not None) is the closed form of a uniform transition matrix: alpha is e and E None."""
     B, T, S = inputs.check_shapes(obs, frames, transition, initial)
     o = obs.to(torch.float64)
     pi = initial.to(torch.float64)
     F = frames.to(torch.int64).clamp(1, T)
-    t_index = torch.arange(T)
-    valid = t_index[None, :] < F[:, None]                                          # (B, T)
+    valid = torch.arange(T)[None, :] < F[:, None]                                   # (B, T)
     x = o.clone()
     x[:, 0] += pi
     m = torch.amax(x, dim=2)                                                        # NaN propagates
     m = torch.where(m == -math.inf, torch.zeros_like(m), m)
     e = torch.exp(x - m[..., None])                                                 # (B, T, S) in [0, 1] (or NaN)
     if uniform is not None:
-        s = e.sum(dim=2)
-        gamma = e / s[..., None]
-        lse = m + torch.log(s)
+        alpha, E = e, None
+        c = e.sum(dim=2)
+        lse = m + torch.log(c)
         lse[:, 1:] += float(uniform)
         L = torch.where(valid, lse, torch.zeros_like(lse)).sum(dim=1)
     else:
@@ -306,6 +281,19 @@ def _host(obs, frames, transition, uniform, initial, weights=None, counts=False)
             alpha[:, t] = torch.where(prev == 0, u * 0., u / prev)
             c[:, t] = alpha[:, t].sum(dim=1)
         L = torch.where(valid, torch.log(c) + m, torch.zeros_like(m)).sum(dim=1)
+    L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
+    return alpha, c, e, E, L, F, valid
+
+
+def _host(obs, frames, transition, uniform, initial, weights=None, counts=False):
+    """The scaled recurrence of the HIP route in float64 with torch CPU ops: (gamma, L, X, I), float64.  `uniform` (not
+    None) takes the closed form of a uniform transition matrix.  X (S, S) [next, prev] and I (S,), the expected counts
+    weighted by `weights` (None = all ones), are computed only with `counts` (dense route), else None."""
+    alpha, c, e, E, L, F, valid = _forward(obs, frames, transition, uniform, initial)
+    B, T, S = alpha.shape
+    if uniform is not None:
+        gamma = e / c[..., None]
+    else:
         gamma = torch.zeros((B, T, S), dtype=torch.float64)
         W = torch.zeros((B, T, S), dtype=torch.float64) if counts else None        # every w_t, for the counts
         w = torch.zeros((B, S), dtype=torch.float64)
@@ -317,7 +305,6 @@ def _host(obs, frames, transition, uniform, initial, weights=None, counts=False)
             w = torch.where((t <= F - 1)[:, None], e[:, t] * beta / ct, w)
             if counts:
                 W[:, t] = w
-    L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
     bad = ~torch.isfinite(L)
     gamma = torch.where(valid[..., None], gamma, torch.zeros_like(gamma))
     gamma = torch.where(bad[:, None, None] & valid[..., None], torch.full_like(gamma, math.nan), gamma)

@@ -15,13 +15,12 @@ band, csrc/sample_band.hpp behind torbi_hip_sample_band (`forward_sample_banded`
 the band.  `gpu=None` runs the dense rule in float64 with torch CPU ops.  SAMPLING.md has the contract, the kernels and the
 numbers.
 """
-import ctypes
 import math
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs, posterior, viterbi
+from . import _lib, band_route, inputs, posterior
 
 MAX_DRAWS = 4096
 _MAX_UNIFORM = 1. - 2. ** -24
@@ -49,32 +48,18 @@ def _check_uniforms(uniforms, B, T, draws=None) -> int:
     return _check_draws(int(uniforms.shape[1]))
 
 
+def _outputs(B, N, T, device):
+    return (torch.empty((B, N, T), dtype=torch.int32, device=device), torch.empty((B,), dtype=torch.float32, device=device))
+
+
 def _run(observation, frames, transition, uniform, initial, uniforms, workspace=None):
     """One call of the HIP route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
     there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
     B, T, S = inputs.check_shapes(observation, frames, transition, initial)
     N = _check_uniforms(uniforms, B, T)
-    device = observation.device
-    lib = _lib.load()
-    indices = torch.empty((B, N, T), dtype=torch.int32, device=device)
-    loglik = torch.empty((B,), dtype=torch.float32, device=device)
-    if B == 0:
-        return indices, loglik
-    need = lib.torbi_hip_sample_workspace_bytes(B, T, S, N, 1 if uniform is not None else 0)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    u = uniforms.to(device=device, dtype=torch.float32).contiguous()
-    tail = (init.data_ptr(), u.data_ptr(), indices.data_ptr(), loglik.data_ptr(), workspace.data_ptr(), workspace.numel(),
-            B, T, S, N, index, stream)
-    if uniform is not None:
-        _lib.check(lib.torbi_hip_sample_uniform(observation.data_ptr(), frames.data_ptr(), ctypes.c_float(uniform), *tail),
-                   'torbi_hip_sample_uniform')
-    else:
-        trans = transition.to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(lib.torbi_hip_sample(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), *tail),
-                   'torbi_hip_sample')
-    return indices, loglik
+    name, model = ('torbi_hip_sample', transition) if uniform is None else ('torbi_hip_sample_uniform', uniform)
+    return _lib.run(name, observation, frames, (model, initial, uniforms), _outputs(B, N, T, observation.device),
+                    ('torbi_hip_sample_workspace_bytes', (B, T, S, N, 1 if uniform is not None else 0)), (B, T, S, N), workspace)
 
 
 def forward_sample(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -113,8 +98,8 @@ def forward_sample_banded_workspace_bytes(B: int, T: int, S: int, draws: int, re
 
 def _covered(B, T, S, N, reach_left, reach_right, background, index=0) -> bool:
     """torbi_hip_sample_band_covers: the band route takes this shape, number of draws, band and background."""
-    return bool(_lib.load().torbi_hip_sample_band_covers(B, T, S, int(N), int(reach_left), int(reach_right),
-                                                         ctypes.c_float(background), index))
+    return bool(_lib.load().torbi_hip_sample_band_covers(B, T, S, int(N), int(reach_left), int(reach_right), background,
+                                                         index))
 
 
 def _run_band(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
@@ -122,23 +107,9 @@ def _run_band(observation, frames, transition, initial, uniforms, reach_left, re
     there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
     B, T, S = inputs.check_shapes(observation, frames, transition, initial)
     N = _check_uniforms(uniforms, B, T)
-    device = observation.device
-    lib = _lib.load()
-    indices = torch.empty((B, N, T), dtype=torch.int32, device=device)
-    loglik = torch.empty((B,), dtype=torch.float32, device=device)
-    if B == 0:
-        return indices, loglik
-    need = lib.torbi_hip_sample_band_workspace_bytes(B, T, S, N, reach_left, reach_right)
-    workspace, index, stream = _lib.launch(device, need, workspace)
-    frames = frames.to(device=device, dtype=torch.int32).contiguous()
-    init = initial.to(device=device, dtype=torch.float32).contiguous()
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
-    u = uniforms.to(device=device, dtype=torch.float32).contiguous()
-    _lib.check(lib.torbi_hip_sample_band(observation.data_ptr(), frames.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                                         reach_left, reach_right, ctypes.c_float(background), u.data_ptr(),
-                                         indices.data_ptr(), loglik.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                         B, T, S, N, index, stream), 'torbi_hip_sample_band')
-    return indices, loglik
+    return _lib.run('torbi_hip_sample_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background, uniforms), _outputs(B, N, T, observation.device),
+                    ('torbi_hip_sample_band_workspace_bytes', (B, T, S, N, reach_left, reach_right)), (B, T, S, N), workspace)
 
 
 def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -168,18 +139,12 @@ def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torc
     Raises where the band route does not cover the call (torbi_hip_sample_band_covers: what `forward_backward_banded`
     covers, and 1 <= draws <= 4096).
     """
-    if transition is None or initial is None:
-        raise RuntimeError('forward_sample_banded needs a transition matrix and an initial distribution')
-    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
-    N = _check_uniforms(uniforms, B, T)
-    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
-    if reach_left < 0 or reach_right < 0:
-        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
-    if B > 0 and not _covered(B, T, S, N, reach_left, reach_right, background):
-        raise RuntimeError(f'forward_sample_banded does not cover B={B}, T={T}, S={S}, draws={N}, reach '
-                           f'{reach_left}/{reach_right}, background {background} (forward_sample takes any matrix)')
-    obs, frames = posterior._operands('forward_sample_banded', observation, batch_frames, transition, initial)
-    return _run_band(obs, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace)
+    B, T, S = shape = posterior._shapes('forward_sample_banded', observation, batch_frames, transition, initial)
+    own = ('draws', _check_uniforms(uniforms, B, T))
+    obs, frames, left, right, background = posterior._banded_operands(
+        'forward_sample_banded', 'forward_sample', _covered, shape, own, observation, batch_frames, reach_left, reach_right,
+        background)
+    return _run_band(obs, frames, transition, initial, uniforms, left, right, background, workspace)
 
 
 # Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row, draws) that
@@ -188,31 +153,23 @@ def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torc
 # 23 diagonals of 1440 states in both forms of the background: 1, 8 and 512 items at one draw (3.5 x, 3.4 x, 5.8 x) and 512
 # items at 16 draws (6.0 x).  Anything outside -- a larger batch, a wider band, more draws -- is not measured and stays dense.
 _AUTO_BAND = ((1, 512, 23, 1), (512, 512, 23, 16))
-_MEASURED_STATES = 1440
 
 
 def _band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
-    width = reach_left + reach_right + 1
-    return any(low <= batch <= high and width * _MEASURED_STATES <= diagonals * states and draws <= most
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals) and draws <= most
                for low, high, diagonals, most in _AUTO_BAND)
 
 
 def _band_plan(trans, original, B, T, S, N, index):
-    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
-    (`original`: the caller's tensor, which the look is remembered with), else (None, the reason).  The structure is what
-    `viterbi.band_over` answers -- one look per tensor version; an unseen matrix while a stream is capturing has no band --,
-    the shape what torbi_hip_sample_band_covers takes."""
-    if B < 1:
-        return None, 'the batch is empty'
-    over = viterbi.band_over(trans, original, S)
-    if over is None:
-        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
-                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
-                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or finite)')
-    if not _covered(B, T, S, N, over[0], over[1], over[2], index):
-        return None, (f'torbi_hip_sample_band_covers turns down batch={B}, frames={T}, states={S}, draws={N}, reach '
-                      f'{over[0]}/{over[1]}, background {over[2]}')
-    return over, ''
+    """`band_route.plan` for this feature: the shape is what torbi_hip_sample_band_covers takes."""
+    return band_route.plan(trans, original, _covered, 'torbi_hip_sample_band_covers', dict(batch=B, frames=T, states=S, draws=N),
+                           index)
+
+
+def _band(route, trans, original, B, T, S, N, index):
+    """The band `route` takes for the prepared device matrix `trans`, or None for the dense route (`band_route.choose`)."""
+    return band_route.choose(route, *_band_plan(trans, original, B, T, S, N, index),
+                             lambda left, right, background: _band_pays(B, S, left, right, N), "sample_paths(route='band')")
 
 
 def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, draws: int = 1, gpu: int = 0,
@@ -230,8 +187,8 @@ def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
     if device.type == 'cpu':
         return 'dense'
     trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
-    band, _ = _band_plan(trans, transition, int(batch), int(frames), states, draws, device.index or 0)
-    return 'band' if band is not None and _band_pays(int(batch), states, band[0], band[1], draws) else 'dense'
+    band = _band('auto', trans, transition, int(batch), int(frames), states, draws, device.index or 0)
+    return 'dense' if band is None else 'band'
 
 
 def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Optional[torch.Tensor] = None,
@@ -260,8 +217,7 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         t >= batch_frames[b] repeat the path's last state.  An item of total probability 0 has log-likelihood -inf, an item
         that reads a NaN or +inf has NaN; both have -1 in every column of every draw.
     """
-    if route not in ('auto', 'dense', 'band'):
-        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+    band_route.check_route(route)
     draws = _check_draws(draws)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     if uniforms is not None:
@@ -275,15 +231,10 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
     frames = inputs.frames(batch_frames, B, T, device)
     original = transition
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    band = None
     if gpu is not None and uniform is None and route != 'dense':
         # (before the observation is prepared: a matrix without a band raises before anything runs)
-        band, why = _band_plan(transition.to(dtype=torch.float32).contiguous(), original, B, T, S, draws, device.index or 0)
-        if band is None and route == 'band':
-            raise RuntimeError(f"sample_paths(route='band'): {why}")
-        if band is not None and route == 'auto' and not _band_pays(B, S, band[0], band[1], draws):
-            band = None
-    else:
-        band = None
+        band = _band(route, transition.to(dtype=torch.float32).contiguous(), original, B, T, S, draws, device.index or 0)
     obs = inputs.observation(observation, log_probs, device)
     if uniforms is None:
         uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)
@@ -291,41 +242,14 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         indices, L = _host(obs, frames, transition, uniform, initial.to(torch.float32), uniforms)
         return indices.to(torch.int32), L.to(torch.float32)
     if band is not None:
-        return _run_band(obs, frames, transition, initial, uniforms, band[0], band[1], band[2])
+        return _run_band(obs, frames, transition, initial, uniforms, *band)
     return _run(obs, frames, transition, uniform, initial, uniforms)
 
 
 def _filter(obs, frames, transition, uniform, initial):
-    """The forward recurrence of `posterior._host` in float64: (a (B, T, S) unnormalised filtered rows -- with `uniform`
-    the rows exp(x - max x) --, E (S, S) or None, L (B,), F (B,) int64)."""
-    B, T, S = inputs.check_shapes(obs, frames, transition, initial)
-    o = obs.to(torch.float64)
-    pi = initial.to(torch.float64)
-    F = frames.to(torch.int64).clamp(1, T)
-    valid = torch.arange(T)[None, :] < F[:, None]
-    x = o.clone()
-    x[:, 0] += pi
-    m = torch.amax(x, dim=2)                                                        # NaN propagates
-    m = torch.where(m == -math.inf, torch.zeros_like(m), m)
-    e = torch.exp(x - m[..., None])
-    if uniform is not None:
-        lse = m + torch.log(e.sum(dim=2))
-        lse[:, 1:] += float(uniform)
-        L = torch.where(valid, lse, torch.zeros_like(lse)).sum(dim=1)
-        a, E = e, None
-    else:
-        E = torch.exp(transition.to(torch.float64))                                 # [next, prev]
-        a = torch.zeros((B, T, S), dtype=torch.float64)
-        c = torch.zeros((B, T), dtype=torch.float64)
-        a[:, 0] = e[:, 0]
-        c[:, 0] = a[:, 0].sum(dim=1)
-        for t in range(1, T):
-            u = e[:, t] * (a[:, t - 1] @ E.T)
-            prev = c[:, t - 1, None]
-            a[:, t] = torch.where(prev == 0, u * 0., u / prev)
-            c[:, t] = a[:, t].sum(dim=1)
-        L = torch.where(valid, torch.log(c) + m, torch.zeros_like(m)).sum(dim=1)
-    L = torch.where(torch.isnan(L) | (L == math.inf), torch.full_like(L, math.nan), L)
+    """The forward recurrence of `posterior._host` in float64 (`posterior._forward`): (a (B, T, S) unnormalised filtered
+    rows -- with `uniform` the rows exp(x - max x) --, E (S, S) or None, L (B,), F (B,) int64)."""
+    a, _, _, E, L, F, _ = posterior._forward(obs, frames, transition, uniform, initial)
     return a, E, L, F
 
 

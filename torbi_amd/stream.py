@@ -21,28 +21,24 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, inputs, viterbi
+from . import _lib, band_route, inputs
 
 # ring slots of a new decoder; the ring doubles when a push needs more
 INITIAL_CAPACITY = 16
 
-ROUTES = ('auto', 'dense', 'band')
+ROUTES = band_route.ROUTES
+
+
+def _covered(batch, states, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_stream_band_covers: the band route takes this many streams, this band and background."""
+    return bool(_lib.load().torbi_hip_stream_band_covers(int(batch), states, reach_left, reach_right, background, index))
 
 
 def _band_plan(trans: torch.Tensor, original: torch.Tensor, batch: int, states: int, index: int
                ) -> Tuple[Optional[Tuple[int, int, float]], str]:
-    """((reach_left, reach_right, background), '') where the band route takes the prepared device matrix `trans`
-    (`original`: the tensor the look is remembered with), else (None, the reason).  The structure is what
-    `viterbi.band_over` answers, the shape what torbi_hip_stream_band_covers takes."""
-    over = viterbi.band_over(trans, original, states)
-    if over is None:
-        return None, ('the matrix does not hold one value outside a band that viterbi.band_over can answer for '
-                      f'(states % 4 == 0, 64 <= states <= {viterbi.BAND_MAX_STATES}, reach_left + reach_right + 4 <= '
-                      f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or a finite value below every entry of the band)')
-    if not _lib.load().torbi_hip_stream_band_covers(int(batch), states, over[0], over[1], ctypes.c_float(over[2]), index):
-        return None, (f'torbi_hip_stream_band_covers turns down batch={batch}, states={states}, reach {over[0]}/{over[1]}, '
-                      f'background {over[2]}')
-    return over, ''
+    """`band_route.plan` for this feature: the shape is what torbi_hip_stream_band_covers takes."""
+    return band_route.plan(trans, original, _covered, 'torbi_hip_stream_band_covers', dict(batch=int(batch), states=states),
+                           index, finite='a finite value below every entry of the band')
 
 
 def stream_route(transition: Optional[torch.Tensor], batch: int, states: int, gpu: Optional[int] = 0,
@@ -104,8 +100,7 @@ class StreamDecoder:
                  max_lag: Optional[int] = None, route: str = 'auto'):
         if batch < 1 or states < 1:
             raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
-        if route not in ROUTES:
-            raise ValueError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+        band_route.check_route(route, ValueError)
         if max_lag is not None:
             try:
                 if isinstance(max_lag, bool):
@@ -138,7 +133,7 @@ class StreamDecoder:
             self.route = 'host'
         else:
             self._lib = _lib.load()
-            self._band = None if route == 'dense' else self._prepare_band(original, route == 'band')
+            self._band = None if route == 'dense' else self._prepare_band(original, route)
             self.route = 'dense' if self._band is None else 'band'
             if self._band is None:
                 self._transposed = self.transition.t().contiguous()
@@ -291,9 +286,9 @@ class StreamDecoder:
         return out
 
     # ------------------------------------------------------------------ HIP route
-    def _prepare_band(self, original: torch.Tensor, must: bool):
+    def _prepare_band(self, original: torch.Tensor, route: str):
         """(reach_left, reach_right, background, diagonals) where the band route takes the decoder's matrix, else None --
-        or, with `must`, a RuntimeError that names the reason.  The diagonals come from a private copy of the matrix, so that
+        or, under 'band', a RuntimeError that names the reason.  The diagonals come from a private copy of the matrix, so that
         the look, the extraction and the device's verdict all speak of the same values whatever the caller later writes."""
         index = self.device.index or 0
         over, reason = _band_plan(self.transition, original, self.batch, self.states, index)
@@ -310,9 +305,7 @@ class StreamDecoder:
             if int(ok.item()) == 1:                             # (the one read-back of the constructor)
                 return left, right, background, diagonals
             reason = f'an entry outside the band of reach {left}/{right} differs from the background {background}'
-        if must:
-            raise RuntimeError(f"StreamDecoder(route='band'): {reason}")
-        return None
+        return band_route.choose(route, None, reason, None, "StreamDecoder(route='band')")
 
     def _grow(self, capacity: int) -> None:
         """Ring of `capacity` slots (at least double the old one); pending rows and the newest row move to their new

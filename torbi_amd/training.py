@@ -18,10 +18,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, inputs
-from .posterior import _band, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts
+from . import _lib, band_route, inputs
+from .posterior import _banded_operands, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts, _shapes
 
-ROUTES = ('auto', 'dense', 'band')
+ROUTES = band_route.ROUTES
 
 
 def expected_counts_workspace_bytes(B: int, T: int, S: int) -> int:
@@ -82,17 +82,11 @@ def forward_backward_counts_banded(observation: torch.Tensor, batch_frames: Opti
     Raises where the band counts route does not cover the call (torbi_hip_forward_backward_counts_band_covers: what
     `forward_backward_banded` covers and 4 W S bytes plus one item's rows within 160 KB of LDS).
     """
-    if transition is None or initial is None:
-        raise RuntimeError('forward_backward_counts_banded needs a transition matrix and an initial distribution')
-    B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
-    reach_left, reach_right, background = int(reach_left), int(reach_right), float(background)
-    if reach_left < 0 or reach_right < 0:
-        raise RuntimeError(f'reach_left and reach_right must be >= 0; got {reach_left}, {reach_right}')
-    if B > 0 and not _counts_covered(B, T, S, reach_left, reach_right, background):
-        raise RuntimeError(f'forward_backward_counts_banded does not cover B={B}, T={T}, S={S}, reach '
-                           f'{reach_left}/{reach_right}, background {background} (forward_backward_counts takes any matrix)')
-    obs, frames = _operands('forward_backward_counts_banded', observation, batch_frames, transition, initial, item_weights)
-    return _run_band_counts(obs, frames, transition, initial, reach_left, reach_right, background, item_weights, workspace)
+    shape = _shapes('forward_backward_counts_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands(
+        'forward_backward_counts_banded', 'forward_backward_counts', _counts_covered, shape, (), observation, batch_frames,
+        reach_left, reach_right, background, item_weights)
+    return _run_band_counts(obs, frames, transition, initial, left, right, background, item_weights, workspace)
 
 
 def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right: int) -> torch.Tensor:
@@ -111,33 +105,28 @@ def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right
     return dense
 
 
-def _auto_takes(B, W) -> bool:
-    """The classes of (items, diagonals) route='auto' sends to the band counts route; route='band' takes whatever is
-    covered.  Measured on the pitch band (W = 23 at 1440 states, close to the largest plane that is covered) at 1, 8 and 512
-    items, the band route beat the dense one 3.0 to 8.1 times with a spread below 2.2 % (POSTERIOR.md "Band counts"), so no
-    class is excluded; one that is found to lose goes here."""
-    return True
+# The classes of (items, diagonals) route='auto' sends to the band counts route; route='band' takes whatever is covered.
+# Measured on the pitch band (W = 23 at 1440 states, close to the largest plane that is covered) at 1, 8 and 512 items, the
+# band route beat the dense one 3.0 to 8.1 times with a spread below 2.2 % (POSTERIOR.md "Band counts"), so no class is
+# excluded; one that is found to lose goes here, as a function of (reach_left, reach_right, background).
+_auto_takes = None
 
 
 def _counts_band(trans, original, B, T, S, index, route):
     """(reach_left, reach_right) when `route` sends the counts of the prepared device matrix `trans` to the band route, else
-    None: `posterior._band` finds a band, the matrix is -inf outside it (so the dense (S, S) result is exactly zero there),
+    None: the matrix is -inf outside a band (so the dense (S, S) result is exactly zero there),
     torbi_hip_forward_backward_counts_band_covers takes it and, for 'auto', the class was measured faster."""
     if route == 'dense':
         return None
-    band = _band(trans, original, B, T, S, index)
-    if band is not None and band[2] == -math.inf and _counts_covered(B, T, S, band[0], band[1], band[2], index) \
-            and (route == 'band' or _auto_takes(B, band[0] + band[1] + 1)):
-        return band[0], band[1]
-    if route == 'band':
-        raise RuntimeError("route='band': the transition matrix has no band with -inf outside it that "
-                           'forward_backward_counts_banded covers')
-    return None
+    plan = band_route.plan(trans, original, _counts_take,
+                           'the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers)',
+                           dict(batch=B, frames=T, states=S), index)
+    band = band_route.choose(route, *plan, _auto_takes, "route='band'")
+    return None if band is None else band[:2]
 
 
-def _check_route(route):
-    if route not in ROUTES:
-        raise RuntimeError(f"route must be 'auto', 'dense' or 'band'; got {route!r}")
+def _counts_take(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    return background == -math.inf and _counts_covered(B, T, S, reach_left, reach_right, background, index)
 
 
 def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
@@ -153,7 +142,8 @@ def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
     if device.type == 'cpu':
         return 'dense'
     trans = inputs._prepared_transition(transition, log_probs, device)
-    return 'dense' if _counts_band(trans, transition, int(batch), int(frames), states, device.index, 'auto') is None else 'band'
+    band = _counts_band(trans, transition, int(batch), int(frames), states, device.index or 0, 'auto')
+    return 'dense' if band is None else 'band'
 
 
 def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -178,7 +168,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
         transition_counts[j, i] is the expected number of steps from state i to state j; one M-step divides each column by
         its sum.
     """
-    _check_route(route)
+    band_route.check_route(route)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
@@ -195,7 +185,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
             raise RuntimeError("route='band': a uniform transition matrix has no band")
         band = None
     else:
-        band = _counts_band(transition, original, B, T, S, device.index, route)
+        band = _counts_band(transition, original, B, T, S, device.index or 0, route)
     if band is not None:
         _, L, Xb, I = _run_band_counts(obs, frames, transition, initial, band[0], band[1], -math.inf)
         return band_counts_to_dense(Xb, band[0], band[1]), I, L
@@ -222,7 +212,7 @@ class _LogLikelihood(torch.autograd.Function):
             obs = observation.detach().to(dtype=torch.float32).contiguous()
             trans = transition.detach().to(device=device, dtype=torch.float32).contiguous()
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
-            ctx.band = _counts_band(trans, transition, B, T, S, device.index, route)
+            ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
             if ctx.band is not None:
                 gamma, L = _run_band(obs, frames, trans, init, ctx.band[0], ctx.band[1], -math.inf)
             else:
@@ -293,5 +283,5 @@ def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tenso
     """
     if transition is None or initial is None:
         raise RuntimeError('log_likelihood needs a transition matrix and an initial distribution')
-    _check_route(route)
+    band_route.check_route(route)
     return _LogLikelihood.apply(observation, batch_frames, transition, initial, route)

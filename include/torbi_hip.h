@@ -570,6 +570,47 @@ int torbi_hip_stream_posterior_flush(const int32_t *info, const float *expa, voi
                                      void *stream);
 
 /*
+ * (added within ABI 17) The band route of streaming posteriors, for a transition matrix that holds ONE value outside a band
+ * (csrc/stream_posterior_band.hpp, STREAM.md "Streaming posteriors: band route"): what torbi_hip_stream_posterior_push and
+ * torbi_hip_stream_posterior_flush compute, their info, outputs, counts_out and non-finite rules, on a state of the same
+ * layout and size (torbi_hip_stream_posterior_state_size; a state may change routes between two calls), at the cost of the
+ * band: W = reach_left + reach_right + 1 multiplies per state and step where the dense route spends S.  The caller states
+ * the band j - reach_left <= i <= j + reach_right of transition [next j][prev i] (log scores) and `background`, the value
+ * of every entry outside it.  The bits differ from the dense route's; a stream's bits depend on its own data and on
+ * (t, n') only, as there.
+ *
+ * torbi_hip_stream_smooth_band_covers answers 1 where the route takes a call, else 0, without touching a device: B >= 1,
+ * 1 <= S <= 4096 (odd S and unaligned rows included), reach_left, reach_right >= 0 with min(W, S) <= 64 after the reaches
+ * are clamped to S - 1, and a background that is neither NaN nor +inf (-inf and every finite value are taken by the same
+ * kernels): what torbi_hip_forward_backward_band_covers takes of a matrix.
+ * torbi_hip_stream_smooth_band_tile: streams per workgroup of a call's kernels (spb_forward_kernel<G> and
+ * spb_backward_kernel<G>: 8, halved while the rows of G streams with their halos and wave sums,
+ * 8 G (S + 2 max(reach_left, reach_right) + 16) bytes, exceed 64 KB of LDS, then while there are fewer workgroups than compute
+ * units); EINVAL / EUNSUPPORTED for a shape the push turns down; without a usable device it answers for 256 compute units.
+ *
+ * torbi_hip_stream_smooth_band_prepare, once per matrix: diagonals_out (torbi_hip_stream_smooth_band_diagonals_size bytes,
+ * 2 W roundup(S, 64) floats; 0 for S < 1 or a negative reach) receives the diagonals of exp(transition) - exp(background)
+ * along the next state and along the prev state, 0 where the matrix edge clips one, and ok_out[0] (int32, device) 1 where
+ * every entry outside the band equals `background` bit for bit, else 0: the caller reads it before it trusts the diagonals.
+ *
+ * push and flush: the dense calls with `diagonals`, reach_left, reach_right and background in place of expa / expa_t.
+ * Every argument is checked before any device work: the dense entries' codes as they stand (EINVAL, ERANGE, EWORKSPACE),
+ * then EINVAL for a negative reach and EUNSUPPORTED where _covers answers 0.  Neither call synchronises the host.
+ */
+int torbi_hip_stream_smooth_band_covers(int B, int S, int reach_left, int reach_right, float background, int device);
+int torbi_hip_stream_smooth_band_tile(int B, int S, int reach_left, int reach_right, int device);
+size_t torbi_hip_stream_smooth_band_diagonals_size(int S, int reach_left, int reach_right);
+int torbi_hip_stream_smooth_band_prepare(const float *transition, int S, int reach_left, int reach_right, float background,
+                                         float *diagonals_out, int32_t *ok_out, int device, void *stream);
+int torbi_hip_stream_smooth_band_push(const float *observation, int Tc, const int32_t *info, const float *diagonals, int reach_left,
+                                      int reach_right, float background, const float *initial, void *state, size_t state_bytes,
+                                      int capacity, float *posterior_out, int out_capacity, int32_t *counts_out, int lag, int B,
+                                      int S, int device, void *stream);
+int torbi_hip_stream_smooth_band_flush(const int32_t *info, const float *diagonals, int reach_left, int reach_right,
+                                       float background, void *state, size_t state_bytes, int capacity, float *posterior_out,
+                                       int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream);
+
+/*
  * (ABI 17) Forward-backward: per-frame state posteriors and the sequence log-likelihood of the HMM that
  * torbi_hip_viterbi_decode decodes (torbi_amd/posterior.py, POSTERIOR.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.  For t < F_b:

@@ -8,9 +8,19 @@
   (c) state bytes per stream
   (d) the accuracy of tests/test_stream_posterior_gpu.py's shapes against the float64 route, as shares of the bounds
 Every figure of (a) and (b) is the median of --repeats runs with its min and max.
+
+--band measures the band route against the dense route instead (STREAM.md, "Streaming posteriors: band route"): both routes
+of StreamPosteriors alternated in one process on the same inputs, the pitch matrix synth.banded_transition(1440, 12) with -inf
+and with log(tiny) outside the band, lag 8:
+  (a) B=512, 500 frames in pushes of 100: milliseconds per run (flush included)
+  (b) B=1, one-frame pushes: wall time per push with the device synchronised inside the timed span, p50 / p99, and the host's
+      own time per push without it
+  (c) B=8, 300 frames in pushes of 15: milliseconds per run
+and the accuracy of tests/test_stream_posterior_band_gpu.py's shapes against the float64 route, as shares of the bounds.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -24,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import torbi_amd  # noqa: E402
 from torbi_amd import synth  # noqa: E402
 from stream_posterior_cases import DEVICE_GAMMA, ROW_SUM, Feeder, problem, ragged_plan  # noqa: E402
+from stream_posterior_band_cases import BACKGROUNDS, band_problem  # noqa: E402
 
 DEV = torch.device('cuda:0')
 LAG = 8
@@ -109,6 +120,120 @@ def accuracy():
     return rows
 
 
+ROUTES = ('dense', 'band')
+
+
+def pitch_matrix(S, tiny):
+    return torch.tensor(synth.banded_transition(S, 12, tiny=tiny), device=DEV)
+
+
+def band_batch_case(B, T, S, push, repeats, tiny):
+    """Milliseconds per run of T frames in pushes of `push`, flush included, the two routes alternated run by run."""
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    obs = torch.log_softmax(torch.randn((B, T, S), device=DEV, generator=gen) * 2.0, dim=-1)
+    trans, init = pitch_matrix(S, tiny), torch.log(torch.full((S,), 1. / S, device=DEV))
+    times = {route: [] for route in ROUTES}
+    for _ in range(repeats + 1):
+        for route in ROUTES:
+            sp = torbi_amd.StreamPosteriors(B, S, trans, init, log_probs=True, gpu=0, lag=LAG, route=route)
+            assert sp.route == route
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in range(0, T, push):
+                sp.push(obs[:, t:t + push])
+            sp.flush()
+            torch.cuda.synchronize()
+            times[route].append(time.perf_counter() - t0)
+    found = {route: spread([1e3 * s for s in v[1:]]) for route, v in times.items()}      # (the first pass grows the ring)
+    found['band_wins'] = found['band']['max'] < found['dense']['min']                    # the slowest of one, the fastest of the other
+    found.update(batch=B, frames=T, push_frames=push, tiny=tiny,
+                 streams_per_workgroup=sp._lib.torbi_hip_stream_smooth_band_tile(B, S, 11, 11, 0))
+    return found
+
+
+def band_single_case(S, pushes, repeats, tiny):
+    """One stream, one-frame pushes: (p50, p99) of the wall time per push with the device synchronised inside the timed span,
+    and of the host's own time per push, the two routes alternated push by push."""
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    one = torch.log_softmax(torch.randn((1, pushes + 20, S), device=DEV, generator=gen) * 2.0, dim=-1)
+    trans, init = pitch_matrix(S, tiny), torch.log(torch.full((S,), 1. / S, device=DEV))
+    names = [f'{route}{part}' for route in ROUTES for part in ('', '_host_only')]
+    runs = {name: [] for name in names}
+    for _ in range(repeats):
+        decoders = [torbi_amd.StreamPosteriors(1, S, trans, init, log_probs=True, gpu=0, lag=LAG, route=route) for route in ROUTES]
+        times = {name: [] for name in names}
+        for t in range(one.shape[1]):
+            frame = one[:, t:t + 1]
+            for route, sp in zip(ROUTES, decoders):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sp.push(frame)
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                if t >= 20:                                      # (warm-up pushes: first launches)
+                    times[route].append(t2 - t0)
+                    times[route + '_host_only'].append(t1 - t0)
+        for name, v in times.items():
+            runs[name].append((np.percentile(v, 50) * 1e3, np.percentile(v, 99) * 1e3))
+    found = {name: {'p50_ms': spread([r[0] for r in v]), 'p99_ms': spread([r[1] for r in v])} for name, v in runs.items()}
+    found['band_wins'] = found['band']['p50_ms']['max'] < found['dense']['p50_ms']['min']
+    found['tiny'] = tiny
+    return found
+
+
+def band_accuracy():
+    """Worst errors of the prefix property after every push on the shapes of the band route's GPU tests."""
+    rows = []
+    cases = [(B, S, lag, reach, BACKGROUNDS[(S + B) % 3], 24)
+             for S, reach in ((1, (0, 0)), (5, (5, 2)), (37, (36, 36)), (64, (1, 2)), (65, (5, 2)), (257, (3, 0)))
+             for B, lag in ((1, 0), (5, 4), (17, 8))]
+    cases += [(511, 64, 2, (1, 2), -20., 9), (1021, 63, 2, (1, 2), -3., 9), (2041, 64, 2, (1, 2), -math.inf, 9),
+              (2, 1440, 3, 'pitch', -math.inf, 12), (2, 1440, 3, 'pitch', 'log(tiny)', 12), (1, 4096, 2, (31, 32), -20., 6)]
+    for B, S, lag, reach, background, T in cases:
+        if reach == 'pitch':
+            obs, _, init = problem(B, T, S, 'none', True, seed=S + B)
+            trans = torch.from_numpy(synth.banded_transition(S, 12, tiny=background != -math.inf))
+            sp = torbi_amd.StreamPosteriors(B, S, trans, init, log_probs=True, gpu=0, lag=lag, route='band')
+            left, right = 11, 11
+        else:
+            left, right = reach
+            obs, trans, init, band = band_problem(B, T, S, left, right, background, True, seed=S + B)
+            sp = torbi_amd.StreamPosteriors(B, S, trans, init, log_probs=True, gpu=0, lag=lag, route='band', band=band)
+        fd = Feeder(sp, obs, trans, init, True, DEVICE_GAMMA, record=False)
+        for Tc, f in ragged_plan(B, T, seed=S + B + lag):
+            fd.push(Tc, f)
+        fd.flush()
+        rows.append({'B': B, 'S': S, 'lag': lag, 'reach': f'{left}/{right}', 'background': str(background),
+                     'G': sp._lib.torbi_hip_stream_smooth_band_tile(B, S, left, right, 0), 'gamma': fd.worst['gamma'],
+                     'gamma_share': fd.worst['gamma'] / DEVICE_GAMMA, 'sum': fd.worst['sum'], 'sum_share': fd.worst['sum'] / ROW_SUM,
+                     'loglik_share': float(fd.worst['loglik_share'])})
+    return rows
+
+
+def band_main(args):
+    found = {'device': torch.cuda.get_device_name(0), 'lag': LAG, 'batch': [], 'single': [], 'small_batch': []}
+    for tiny in (False, True):
+        found['batch'].append(band_batch_case(args.batch, args.frames, args.states, args.push, args.repeats, tiny))
+        found['single'].append(band_single_case(args.states, args.single_pushes, args.repeats, tiny))
+        found['small_batch'].append(band_batch_case(8, 300, args.states, 15, args.repeats, tiny))
+    if not args.skip_accuracy:
+        found['accuracy'] = band_accuracy()
+    print(json.dumps(found))
+    form = lambda v, digits=2: f"{v['median']:.{digits}f} ms ({v['min']:.{digits}f} - {v['max']:.{digits}f})"
+    for b in found['batch'] + found['small_batch']:
+        print(f"| {b['batch']} x {b['frames']} x {args.states}, pushes of {b['push_frames']}, {'log(tiny)' if b['tiny'] else '-inf'} "
+              f"(G = {b['streams_per_workgroup']}) | {form(b['dense'])} | {form(b['band'])} | "
+              f"{b['dense']['median'] / b['band']['median']:.1f} x | {'yes' if b['band_wins'] else 'no'} |")
+    for one in found['single']:
+        for name in ('dense', 'band', 'dense_host_only', 'band_host_only'):
+            print(f"| {name}, {'log(tiny)' if one['tiny'] else '-inf'} | {form(one[name]['p50_ms'], 4)} | {form(one[name]['p99_ms'], 4)} |")
+        print(f"| band wins, {'log(tiny)' if one['tiny'] else '-inf'} | {'yes' if one['band_wins'] else 'no'} | |")
+    for r in found.get('accuracy', []):
+        print(f"| {r['B']} x {r['S']}, lag {r['lag']}, reach {r['reach']}, background {r['background']} (G = {r['G']}) | "
+              f"{r['gamma']:.1e} ({r['gamma_share']:.3f}) | {r['sum']:.1e} ({r['sum_share']:.3f}) | {r['loglik_share']:.3f} |")
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--repeats', type=int, default=5)
@@ -119,7 +244,10 @@ def main():
     p.add_argument('--single-pushes', type=int, default=300)
     p.add_argument('--skip-accuracy', action='store_true')
     p.add_argument('--only-batch', action='store_true', help='case (a) alone: the target of a kernel trace')
+    p.add_argument('--band', action='store_true', help='the band route against the dense route (see above)')
     args = p.parse_args()
+    if args.band:
+        return band_main(args)
     found = {'device': torch.cuda.get_device_name(0), 'lag': LAG,
              'batch': batch_case(args.batch, args.frames, args.states, args.push, args.repeats)}
     if not args.only_batch:

@@ -18,7 +18,7 @@ from .pipeline import DecodePipeline
 from .state import reset as reset_path_state
 from .core import release_job_memory
 from .stream import StreamDecoder, stream_route
-from .stream_posterior import StreamPosteriors
+from .stream_posterior import StreamPosteriors, stream_posterior_route
 from .posterior import (forward_backward, forward_backward_banded, forward_backward_banded_workspace_bytes,
                         forward_backward_workspace_bytes, posterior_route, state_posteriors)
 from .training import (band_counts_to_dense, counts_route, expected_counts, expected_counts_banded_workspace_bytes,
@@ -39,4 +39,4 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route', 'stream_route', 'decode_k_best_banded',
            'decode_k_best_banded_workspace_bytes', 'k_best_route', 'sample_paths', 'forward_sample',
            'forward_sample_workspace_bytes', 'forward_sample_banded', 'forward_sample_banded_workspace_bytes', 'sample_route',
-           'StreamPosteriors']
+           'StreamPosteriors', 'stream_posterior_route']

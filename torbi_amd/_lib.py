@@ -106,6 +106,17 @@ SYMBOLS = {
     'torbi_hip_stream_posterior_flush': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
         _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_smooth_band_covers': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int]),
+    'torbi_hip_stream_smooth_band_tile': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_stream_smooth_band_diagonals_size': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_stream_smooth_band_prepare': (_c.c_int, [
+        _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_smooth_band_push': (_c.c_int, [
+        _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_stream_smooth_band_flush': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+        _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     'torbi_hip_forward_backward_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
     'torbi_hip_forward_backward': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,

@@ -44,6 +44,7 @@
 #include "stream_posterior.hpp"
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
+#include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
@@ -2475,6 +2476,125 @@ int torbi_hip_stream_posterior_flush(const int32_t *info, const float *expa, voi
     if (guard.err != hipSuccess) return (int)guard.err;
     return stream_posterior_sweep(info, -1, expa, stream_posterior_state(state, B, S, capacity), capacity, posterior_out,
                                   out_capacity, counts_out, 0, B, S, device, static_cast<hipStream_t>(stream));
+}
+
+// ---- streaming posteriors on a band with one constant outside it (stream_posterior_band.hpp) ----
+
+// the matrices the band route takes: torbi_hip_forward_backward_band_covers' rule for (S, band, background)
+static bool stream_smooth_band_shape(int S, int reach_left, int reach_right) {
+    if (S < 1 || S > spb::kMaxStates || reach_left < 0 || reach_right < 0) return false;
+    const int W = spb::band_of(S, reach_left, reach_right).W;
+    return (W < S ? W : S) <= spb::kMaxWindow;               // at most 64 in-band entries in a matrix row
+}
+
+int torbi_hip_stream_smooth_band_covers(int B, int S, int reach_left, int reach_right, float background, int device) {
+    (void)device;
+    if (B < 1 || !stream_smooth_band_shape(S, reach_left, reach_right)) return 0;
+    return background != background || background == INFINITY ? 0 : 1;
+}
+
+// Streams per workgroup of spb_forward_kernel<G> / spb_backward_kernel<G>: stream_tile's rule with the band kernels' LDS
+int torbi_hip_stream_smooth_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (!stream_smooth_band_shape(S, reach_left, reach_right)) return TORBI_HIP_EUNSUPPORTED;
+    const int halo = spb::band_of(S, reach_left, reach_right).halo;
+    return items_per_workgroup(spb::kMaxGroup, B, 1, cu_count(device),
+                               [&](int G) { return spb::lds_bytes(G, S, halo) <= (size_t)spb::kMaxLdsBytes; });
+}
+
+size_t torbi_hip_stream_smooth_band_diagonals_size(int S, int reach_left, int reach_right) {
+    if (S < 1 || reach_left < 0 || reach_right < 0) return 0;
+    const spb::Band band = spb::band_of(S, reach_left, reach_right);
+    return (size_t)2 * band.W * band.Sd * sizeof(float);
+}
+
+int torbi_hip_stream_smooth_band_prepare(const float *transition, int S, int reach_left, int reach_right, float background,
+                                         float *diagonals_out, int32_t *ok_out, int device, void *stream) {
+    if (S < 1 || reach_left < 0 || reach_right < 0 || !transition || !diagonals_out || !ok_out) return TORBI_HIP_EINVAL;
+    if (!torbi_hip_stream_smooth_band_covers(1, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const spb::Band band = spb::band_of(S, reach_left, reach_right);
+    const size_t cells = (size_t)band.W * band.Sd;
+    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    hipError_t e;
+    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
+                       transition, diagonals_out, diagonals_out + cells, ok_out, ebg, band.reach_left, band.W, band.Sd, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, ok_out, background, band.reach_left,
+                       band.reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(spb::spb_verdict_kernel, dim3(1), dim3(1), 0, st, ok_out);
+    return (int)hipGetLastError();
+}
+
+// the argument rules of both calls: the dense entries' with `diagonals` where their matrix stands, then the band's own
+static int stream_smooth_band_args_ok(const void *info, const void *diagonals, int reach_left, int reach_right, float background,
+                                      const void *state, size_t state_bytes, int capacity, const void *posterior_out,
+                                      int out_capacity, int lag, int B, int S, int device) {
+    const int code = stream_posterior_args_ok(info, diagonals, state, state_bytes, capacity, posterior_out, out_capacity, lag, B, S);
+    if (code != TORBI_HIP_OK) return code;
+    if (reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (!torbi_hip_stream_smooth_band_covers(B, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    return TORBI_HIP_OK;
+}
+
+// the backward sweep of a push (Tc >= 0) or a flush (Tc < 0)
+static int stream_smooth_band_sweep(const int32_t *info, int Tc, const float *diagonals, const spb::Band &band, float ebg, int G,
+                                    const StreamPosteriorState &ss, int capacity, float *posterior_out, int out_capacity,
+                                    int32_t *counts_out, int lag, int B, int S, hipStream_t st) {
+    by_value<8, 4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &spb::spb_backward_kernel<decltype(g)::value>;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(spb::kThreads), spb::lds_bytes(G, S, band.halo), st,
+                           reinterpret_cast<const stream::Info *>(info), Tc, diagonals + (size_t)band.W * band.Sd, ss.L, ss.a, ss.e,
+                           ss.c, ebg, band.reach_left, band.halo, band.W, band.Sd, capacity, posterior_out, out_capacity,
+                           counts_out, lag, B, S);
+    });
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_stream_smooth_band_push(const float *observation, int Tc, const int32_t *info, const float *diagonals, int reach_left,
+                                      int reach_right, float background, const float *initial, void *state, size_t state_bytes,
+                                      int capacity, float *posterior_out, int out_capacity, int32_t *counts_out, int lag, int B,
+                                      int S, int device, void *stream) {
+    int code = stream_smooth_band_args_ok(info, diagonals, reach_left, reach_right, background, state, state_bytes, capacity,
+                                          posterior_out, out_capacity, lag, B, S, device);
+    if (code != TORBI_HIP_OK) return code;
+    if (Tc < 0 || (Tc > 0 && (!observation || !initial))) return TORBI_HIP_EINVAL;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const StreamPosteriorState ss = stream_posterior_state(state, B, S, capacity);
+    const spb::Band band = spb::band_of(S, reach_left, reach_right);
+    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    const int G = torbi_hip_stream_smooth_band_tile(B, S, reach_left, reach_right, device);
+    if (Tc > 0) {
+        by_value<8, 4, 2, 1>(G, [&](auto g) {
+            auto *kernel = &spb::spb_forward_kernel<decltype(g)::value>;
+            hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(spb::kThreads), spb::lds_bytes(G, S, band.halo), st, observation,
+                               Tc, reinterpret_cast<const stream::Info *>(info), diagonals, initial, ss.L, ss.a, ss.e, ss.c, ss.m,
+                               ebg, band.reach_left, band.halo, band.W, band.Sd, capacity, out_capacity, lag, B, S);
+        });
+        if ((code = (int)hipGetLastError()) != hipSuccess) return code;
+    }
+    return stream_smooth_band_sweep(info, Tc, diagonals, band, ebg, G, ss, capacity, posterior_out, out_capacity, counts_out, lag, B,
+                                    S, st);
+}
+
+int torbi_hip_stream_smooth_band_flush(const int32_t *info, const float *diagonals, int reach_left, int reach_right,
+                                       float background, void *state, size_t state_bytes, int capacity, float *posterior_out,
+                                       int out_capacity, int32_t *counts_out, int B, int S, int device, void *stream) {
+    const int code = stream_smooth_band_args_ok(info, diagonals, reach_left, reach_right, background, state, state_bytes, capacity,
+                                                posterior_out, out_capacity, 0, B, S, device);
+    if (code != TORBI_HIP_OK) return code;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const spb::Band band = spb::band_of(S, reach_left, reach_right);
+    return stream_smooth_band_sweep(info, -1, diagonals, band, background == -INFINITY ? 0.f : expf(background),
+                                    torbi_hip_stream_smooth_band_tile(B, S, reach_left, reach_right, device),
+                                    stream_posterior_state(state, B, S, capacity), capacity, posterior_out, out_capacity, counts_out,
+                                    0, B, S, static_cast<hipStream_t>(stream));
 }
 
 // ---- forward-backward: state posteriors and log-likelihood (forward_backward.hpp) ----

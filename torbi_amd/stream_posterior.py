@@ -6,7 +6,12 @@ n' = n + f, the rows gamma_{t|n'} = P(state_t = j | frames 0 .. n' - 1) for t = 
 is the newest row, `log_likelihood` the running log P(frames so far), `flush` the remaining rows.  The HIP route is
 csrc/stream_posterior.hpp behind torbi_hip_stream_posterior_* (include/torbi_hip.h); `gpu=None` runs the same rule on the
 host in float64 with torch CPU ops.  STREAM.md, "Streaming posteriors", has the layout, the kernels and the numbers.
+
+A matrix that holds ONE value outside a band (the pitch matrix of a live pitch tracker: 23 diagonals of 1440 states) can
+take the band route on the device (csrc/stream_posterior_band.hpp behind torbi_hip_stream_smooth_band_*; STREAM.md,
+"Streaming posteriors: band route"): a step costs the band, not the matrix.  `route` and `band` choose.
 """
+import ctypes
 import math
 import operator
 from typing import List, Optional, Sequence, Tuple
@@ -14,10 +19,65 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, inputs
+from . import _lib, band_route, inputs
 
 # ring slots of a new decoder
 INITIAL_CAPACITY = 16
+
+ROUTES = band_route.ROUTES
+# Where 'auto' takes a covered band: the classes in which tools/stream_posterior_probe.py --band measured the band route's
+# slowest of five runs faster than the dense route's fastest of five (STREAM.md, "Streaming posteriors: band route").  Each
+# entry: (smallest batch, largest batch, diagonals of 1440 states).  Measured, all on 23 diagonals of 1440 states in both forms
+# of the background at lag 8: 1 stream in one-frame pushes (27 x), 8 streams in pushes of 15 (61 x), 512 streams in pushes of
+# 100 (33 x).  Anything outside -- a larger batch, a band that holds more of a row -- is not measured and stays dense.
+_AUTO_BAND = ((1, 512, 23),)
+
+
+def _covered(batch, states, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_stream_smooth_band_covers: the band route takes this many streams, this band and background."""
+    return bool(_lib.load().torbi_hip_stream_smooth_band_covers(int(batch), int(states), reach_left, reach_right, background,
+                                                                index))
+
+
+def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
+               for low, high, diagonals in _AUTO_BAND)
+
+
+def _band_plan(trans: torch.Tensor, original: torch.Tensor, batch: int, states: int, index: int):
+    """`band_route.plan` for this feature: the shape is what torbi_hip_stream_smooth_band_covers takes."""
+    return band_route.plan(trans, original, _covered, 'torbi_hip_stream_smooth_band_covers',
+                           dict(batch=int(batch), states=int(states)), index)
+
+
+def _stated_band(band):
+    """`band=` of the constructor as (reach_left, reach_right, background), or a ValueError."""
+    try:
+        reach_left, reach_right, background = band
+        return band_route.stated(operator.index(reach_left), operator.index(reach_right), background)
+    except (TypeError, ValueError, RuntimeError) as error:
+        raise ValueError(f'band must be (reach_left >= 0, reach_right >= 0, background); got {band!r} ({error})') from None
+
+
+def stream_posterior_route(transition: Optional[torch.Tensor], batch: int, states: int, gpu: Optional[int] = 0,
+                           log_probs: bool = False) -> str:
+    """The route `StreamPosteriors(batch, states, transition, log_probs=log_probs, gpu=gpu, route='auto')` takes: 'band' (one
+    value outside a band the band kernels cover, in a class where the band route was measured faster), 'dense', or 'host'
+    for `gpu=None`.  `transition=None` is 'dense'."""
+    if gpu is None:
+        return 'host'
+    if transition is None:
+        return 'dense'
+    states = int(states)
+    if tuple(transition.shape) != (states, states):
+        raise ValueError(f'transition must be ({states}, {states})')
+    device = inputs._compute_device(gpu)
+    original = transition
+    transition, _, _ = inputs.model(transition, None, log_probs, states, device)
+    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    band, why = _band_plan(trans, original, batch, states, device.index or 0)
+    pays = lambda left, right, background: _band_pays(int(batch), states, left, right)
+    return 'dense' if band_route.choose('auto', band, why, pays, 'stream_posterior_route') is None else 'band'
 
 
 class StreamPosteriors:
@@ -45,12 +105,33 @@ class StreamPosteriors:
       INITIAL_CAPACITY) never exceeds `round_capacity(lag + largest Tc pushed)`.  The host route holds at most lag + Tc
       rows per stream.
     * On the device exp(transition) and its transpose are built once, here, with torch.exp from a private copy of the matrix.
+
+    `route` ('auto', 'dense' or 'band'; validated and otherwise ignored with `gpu=None`): which device route the decoder
+    takes.  'dense', the default, is the route for any matrix, and every call that does not say otherwise keeps its bits.
+    'band' is the band route for a matrix that holds one value outside a band: `viterbi.band_over` finds the band,
+    torbi_hip_stream_smooth_band_covers says whether the kernels take it, and the constructor builds the diagonals from a
+    private copy of the matrix and reads the device's verdict on it back once (its one read-back; `push`, `flush`,
+    `filtered()` and `log_likelihood` still never synchronise).  It raises RuntimeError, naming the reason, where any of
+    these says no.  'auto' takes the band route where all of them say yes and the class was measured faster
+    (`torbi_amd.stream_posterior_route` answers which), else the dense route.
+    `band=(reach_left, reach_right, background)` states the band instead of looking for it -- every entry [next j][prev i]
+    outside j - reach_left <= i <= j + reach_right (log scores, after the preparation) equals `background` -- which also
+    reaches what the look cannot answer for (1 <= states <= 4096, odd counts included; min(reach_left + reach_right + 1,
+    states) <= 64).  A band the kernels do not cover, or a matrix that breaks the promise, raises RuntimeError; `band=`
+    with route='dense' is a ValueError.  `sp.route` tells: 'band', 'dense' or 'host'.  The state, the memory per slot and the
+    rules above are the same on either device route; the bits of the two differ (within 2e-4).
     """
 
     def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
-                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0, lag: int = 8):
+                 initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0, lag: int = 8,
+                 route: str = 'dense', band: Optional[Tuple[int, int, float]] = None):
         if batch < 1 or states < 1:
             raise ValueError('StreamPosteriors needs batch >= 1 and states >= 1')
+        band_route.check_route(route, ValueError)
+        if band is not None:
+            band = _stated_band(band)
+            if route == 'dense':
+                raise ValueError("band= states a band for the band route: pass route='band' or 'auto' with it, not 'dense'")
         try:
             if isinstance(lag, bool):
                 raise TypeError
@@ -63,9 +144,10 @@ class StreamPosteriors:
         self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
         S = self.states
         self.device = inputs._compute_device(gpu)
+        original = transition
         transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
         if transition is None:
-            transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
+            original = transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
         self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
             raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
@@ -77,11 +159,15 @@ class StreamPosteriors:
             self._carry = [None] * self.batch                       # (a, c) of the newest frame
             self._sum = [0.] * self.batch                           # running sums of log c_t + m_t
             self._held = 0
+            self.route = 'host'
         else:
             self._lib = _lib.load()
-            private = transition.to(device=self.device, dtype=torch.float32).clone()
-            self._expa = torch.exp(private).contiguous()            # [next, prev]
-            self._expa_t = self._expa.t().contiguous()              # [prev, next]
+            private = transition.to(device=self.device, dtype=torch.float32).clone().contiguous()
+            self._band = self._prepare_band(private, original, route, band)
+            self.route = 'dense' if self._band is None else 'band'
+            if self._band is None:
+                self._expa = torch.exp(private).contiguous()        # [next, prev]
+                self._expa_t = self._expa.t().contiguous()          # [prev, next]
             self._capacity = 0
             self._state = None
             self._grow(INITIAL_CAPACITY)
@@ -248,6 +334,41 @@ class StreamPosteriors:
         return result
 
     # ------------------------------------------------------------------ HIP route
+    def _prepare_band(self, private: torch.Tensor, original: torch.Tensor, route: str, stated):
+        """(reach_left, reach_right, c_float(background), diagonals) where the decoder takes the band route, else None -- or a
+        RuntimeError that names the reason, under 'band' and for a stated band.  The diagonals come from `private`, the
+        decoder's own copy of the matrix, so that the look, the diagonals and the device's verdict all speak of the same values
+        whatever the caller later writes."""
+        B, S, index = self.batch, self.states, self.device.index or 0
+        who = "StreamPosteriors(route='band')"
+        if stated is not None:
+            who = f'StreamPosteriors(band={stated!r})'
+            if not _covered(B, S, *stated, index):
+                raise RuntimeError(f'{who}: torbi_hip_stream_smooth_band_covers turns down batch={B}, states={S}, reach '
+                                   f'{stated[0]}/{stated[1]}, background {stated[2]}')
+            over = stated
+        elif route == 'dense':
+            return None
+        else:
+            over = band_route.choose(route, *_band_plan(private, original, B, S, index),
+                                     lambda left, right, background: _band_pays(B, S, left, right), who)
+            if over is None:
+                return None
+        left, right, background = over
+        diagonals = torch.empty(self._lib.torbi_hip_stream_smooth_band_diagonals_size(S, left, right) // 4, dtype=torch.float32,
+                                device=self.device)
+        ok = torch.empty(1, dtype=torch.int32, device=self.device)
+        _, index, stream = _lib.launch(self.device)
+        _lib.check(self._lib.torbi_hip_stream_smooth_band_prepare(private.data_ptr(), S, left, right, ctypes.c_float(background),
+                                                                  diagonals.data_ptr(), ok.data_ptr(), index, stream),
+                   'torbi_hip_stream_smooth_band_prepare')
+        if int(ok.item()) == 1:                                 # (the one read-back of the constructor)
+            return left, right, ctypes.c_float(background), diagonals
+        reason = f'an entry outside the band of reach {left}/{right} differs from the background {background}'
+        if stated is not None:
+            raise RuntimeError(f'{who}: {reason}')
+        return band_route.choose(route, None, reason, None, who)
+
     def _rings(self, state=None, capacity=None):
         """(a (B, cap, S), e (B, cap, S), c (B, cap), m (B, cap)) float32 views of the state."""
         state = self._state if state is None else state
@@ -299,10 +420,17 @@ class StreamPosteriors:
         info = self._info(pending, f)
         out = torch.empty((B, max(1, int(counts.max())), S), dtype=torch.float32, device=self.device)
         _, index, stream = _lib.launch(self.device)
-        _lib.check(self._lib.torbi_hip_stream_posterior_push(
-            obs.data_ptr(), int(obs.shape[1]), info.data_ptr(), self._expa.data_ptr(), self._expa_t.data_ptr(),
-            self.initial.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1],
-            None, min(self.lag, 2 ** 31 - 1), B, S, index, stream), 'torbi_hip_stream_posterior_push')
+        tail = (self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1], None,
+                min(self.lag, 2 ** 31 - 1), B, S, index, stream)
+        if self._band is not None:
+            left, right, background, diagonals = self._band
+            _lib.check(self._lib.torbi_hip_stream_smooth_band_push(
+                obs.data_ptr(), int(obs.shape[1]), info.data_ptr(), diagonals.data_ptr(), left, right, background,
+                self.initial.data_ptr(), *tail), 'torbi_hip_stream_smooth_band_push')
+        else:
+            _lib.check(self._lib.torbi_hip_stream_posterior_push(
+                obs.data_ptr(), int(obs.shape[1]), info.data_ptr(), self._expa.data_ptr(), self._expa_t.data_ptr(),
+                self.initial.data_ptr(), *tail), 'torbi_hip_stream_posterior_push')
         return [out[b, :counts[b]] for b in range(B)]
 
     def _flush_device(self, items: List[int]) -> dict:
@@ -313,7 +441,12 @@ class StreamPosteriors:
         info = self._info(pending, marks)
         out = torch.empty((B, max(1, int(pending[items].max())), S), dtype=torch.float32, device=self.device)
         _, index, stream = _lib.launch(self.device)
-        _lib.check(self._lib.torbi_hip_stream_posterior_flush(
-            info.data_ptr(), self._expa.data_ptr(), self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(),
-            out.shape[1], None, B, S, index, stream), 'torbi_hip_stream_posterior_flush')
+        tail = (self._state.data_ptr(), self._state_bytes, self._capacity, out.data_ptr(), out.shape[1], None, B, S, index, stream)
+        if self._band is not None:
+            left, right, background, diagonals = self._band
+            _lib.check(self._lib.torbi_hip_stream_smooth_band_flush(info.data_ptr(), diagonals.data_ptr(), left, right, background,
+                                                                    *tail), 'torbi_hip_stream_smooth_band_flush')
+        else:
+            _lib.check(self._lib.torbi_hip_stream_posterior_flush(info.data_ptr(), self._expa.data_ptr(), *tail),
+                       'torbi_hip_stream_posterior_flush')
         return {k: out[k, :pending[k]] for k in items}

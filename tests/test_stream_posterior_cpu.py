@@ -129,6 +129,19 @@ def test_empty_pushes_and_a_second_flush():
     assert (cpu(fd.sp.filtered()) == 0).all()
 
 
+def test_flushing_no_stream_returns_nothing_before_and_after_a_push():
+    """The host behaviour the device route matches (tests/test_stream_posterior_gpu.py): ([], tensor([])), nothing changes."""
+    sp = torbi_amd.StreamPosteriors(2, 4, gpu=None, lag=1)
+    for pushed in (0, 2):
+        if pushed:
+            sp.push(torch.rand((2, pushed, 4)))
+        before = (sp.pending.tolist(), sp.frames.tolist(), sp.log_likelihood.clone())
+        rest, final = sp.flush([])
+        assert rest == [] and final.dtype == torch.float32 and tuple(final.shape) == (0,)
+        assert (sp.pending.tolist(), sp.frames.tolist()) == before[:2] == ([min(pushed, 1)] * 2, [pushed] * 2)
+        assert torch.equal(sp.log_likelihood, before[2])
+
+
 def test_flushing_one_stream_half_way_restarts_it_from_initial():
     B, S, T = 3, 5, 14
     fd = feeder(B, S, 'dense', True, lag=3, T=T, seed=6)

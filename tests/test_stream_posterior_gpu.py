@@ -208,6 +208,30 @@ def test_flushing_one_stream_leaves_its_neighbours_bits():
     assert all(np.array_equal(x, y) for x, y in zip(*runs))
 
 
+@pytest.mark.parametrize('route', ['dense', 'band'])
+def test_flushing_no_stream_returns_nothing_and_changes_nothing(route):
+    """`flush(items=[])` is the host route's ([], empty) on both device routes, and the flush after it returns the bits of an
+    object that was fed the same pushes without it."""
+    B, S, model = (2, 4, dict(lag=1)) if route == 'dense' else (2, 8, dict(lag=1, route='band', band=(1, 1, -math.inf)))
+    obs, trans, init = problem(B, 2, S, route, True, seed=17)     # ('band': tridiagonal, -inf outside reach 1/1)
+    runs = []
+    for empty_flush in (True, False):
+        sp = torbi_amd.StreamPosteriors(B, S, trans, init, log_probs=True, gpu=0, **model)
+        assert sp.route == route
+        for t in range(2):
+            sp.push(obs[:, t:t + 1].to(DEV))
+        if empty_flush:
+            before = (sp.pending.tolist(), sp.frames.tolist(), bits(sp.log_likelihood))
+            rest, final = sp.flush(items=[])
+            assert rest == [] and final.dtype == torch.float32 and tuple(final.shape) == (0,) and final.device == DEV
+            assert (sp.pending.tolist(), sp.frames.tolist()) == before[:2] == ([1, 1], [2, 2])
+            assert np.array_equal(bits(sp.log_likelihood), before[2])
+        rest, final = sp.flush()
+        runs.append([bits(r) for r in rest] + [bits(final)])
+    assert all(r.shape == (1, S) for r in runs[0][:B]) and not np.isnan(runs[0][-1].view(np.float32)).any()
+    assert all(np.array_equal(x, y) for x, y in zip(*runs))
+
+
 # ---- 13. non-finite inputs ---------------------------------------------------------------------------------------------
 
 def test_a_nan_observation_poisons_its_stream_alone_until_the_flush():

@@ -38,18 +38,25 @@ constexpr int kMaxLdsBytes = 64 * 1024;
 
 __host__ __device__ inline int clamp_reach(int reach, int S) { return reach < 0 ? 0 : (reach > S - 1 ? S - 1 : reach); }
 
-struct Layout {
-    int reach_left, reach_right, W, Sd;      // (the reaches clamped to S - 1)
-    float *Df, *Db, *m, *c; int32_t *flag; size_t total;
-};
+// what the band is to the kernels, one-shot and streaming (stream_posterior_band.hpp): the reaches clamped to S - 1, the
+// diagonals [W][Sd], the zero halo of the LDS rows
+struct Band { int reach_left, reach_right, W, Sd, halo; };
+inline Band band_of(int S, int reach_left, int reach_right) {
+    Band b;
+    b.reach_left = clamp_reach(reach_left, S);
+    b.reach_right = clamp_reach(reach_right, S);
+    b.W = b.reach_left + b.reach_right + 1;
+    b.Sd = (int)align_up((size_t)S, 64);
+    b.halo = b.reach_left > b.reach_right ? b.reach_left : b.reach_right;
+    return b;
+}
+
+struct Layout : Band { float *Df, *Db, *m, *c; int32_t *flag; size_t total; };
 
 // `base`: the caller's workspace aligned up to 256 bytes, or null for the byte count alone
 inline Layout layout(char *base, int B, int T, int S, int reach_left, int reach_right) {
     Layout l;
-    l.reach_left = clamp_reach(reach_left, S);
-    l.reach_right = clamp_reach(reach_right, S);
-    l.W = l.reach_left + l.reach_right + 1;
-    l.Sd = (int)align_up((size_t)S, 64);
+    static_cast<Band &>(l) = band_of(S, reach_left, reach_right);
     Scratch a(base);
     l.Df = a.take<float>((size_t)l.W * l.Sd);
     l.Db = a.take<float>((size_t)l.W * l.Sd);
@@ -108,6 +115,18 @@ __global__ __launch_bounds__(64) void fb_band_verify_kernel(const float *__restr
     for (int i = lane; i < S; i += 64)
         if ((i < j - reach_left || i > j + reach_right) && __float_as_uint(row[i]) != want) broken = true;
     if (broken) *flag = 1;
+}
+
+// host: the two launches above, in this order -- what every band entry and the streaming prepare do to a matrix first
+inline hipError_t prepare_and_verify(const float *A, const Band &b, float *Df, float *Db, int32_t *flag, float ebg,
+                                     float background, int S, hipStream_t st) {
+    const size_t cells = (size_t)b.W * b.Sd;
+    hipLaunchKernelGGL(fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st, A,
+                       Df, Db, flag, ebg, b.reach_left, b.W, b.Sd, S);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fb_band_verify_kernel, dim3(S), dim3(64), 0, st, A, flag, background, b.reach_left, b.reach_right, S);
+    return hipGetLastError();
 }
 
 // diagonal loads in flight per band sum of a tile of G items

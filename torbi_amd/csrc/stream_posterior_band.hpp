@@ -43,18 +43,6 @@ constexpr int kMaxWindow = fbb::kMaxWindow;
 constexpr int kMaxGroup = 8;                 // streams per workgroup: the largest tile whose kernels need no scratch
 constexpr int kMaxLdsBytes = 64 * 1024;
 
-// what the band is to the kernels: the reaches clamped to S - 1
-struct Band { int reach_left, reach_right, W, Sd, halo; };
-inline Band band_of(int S, int reach_left, int reach_right) {
-    Band b;
-    b.reach_left = fbb::clamp_reach(reach_left, S);
-    b.reach_right = fbb::clamp_reach(reach_right, S);
-    b.W = b.reach_left + b.reach_right + 1;
-    b.Sd = (S + 63) / 64 * 64;
-    b.halo = b.reach_left > b.reach_right ? b.reach_left : b.reach_right;
-    return b;
-}
-
 // LDS of a tile of G streams: the rows [2][G][S + 2 halo] and the wave sums [2][G][16], fp32
 inline size_t lds_bytes(int G, int S, int halo) { return (size_t)2 * G * (fbb::row_stride(S, halo) + kWaves) * sizeof(float); }
 

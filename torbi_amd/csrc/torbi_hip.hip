@@ -1475,6 +1475,10 @@ hipError_t run_resident(const HostBatch *hb, int n, const float *trans, const fl
 inline int band_tiles(int B) { return (B + band::kNI - 1) / band::kNI; }
 
 // batches with B > 0 only; tile map, statistics, tickets and give-up flags live in the first batch's workspace
+// The one value outside a band: neither NaN nor +inf; the forward-backward kernels read its exp (0 for -inf).
+static bool background_ok(float background) { return background == background && background != INFINITY; }
+static float exp_background(float background) { return background == -INFINITY ? 0.f : expf(background); }
+
 // What the band route does with a launch group: whole tiles (band_tile_forward.hpp: one workgroup per tile, once the group
 // has a tile for at least every other compute unit) or tiles split over R members (band_forward.hpp), `cap` tiles per
 // launch -- every member of a launch resident at once, because they wait for each other inside it.
@@ -1488,7 +1492,7 @@ struct BandChoice {
 inline bool choose_band(int S, int hl, int hr, int tiles, int cus, BandChoice &c, float background = -INFINITY) {
     c = BandChoice{};
     c.background = background;
-    if (tiles < 1 || background != background || background == INFINITY) return false;
+    if (tiles < 1 || !background_ok(background)) return false;
     const char *force = getenv("TORBI_HIP_BAND_FORM");            // experiments: "tile" / "split"
     const char *tw = getenv("TORBI_HIP_TILE_WAVES");              // experiments: 8 / 12 waves per workgroup
     const bool tile_ok = band::make_tile_plan(S, hl, hr, c.tile, tw ? atoi(tw) : 0) && !(force && force[0] == 's');
@@ -2203,6 +2207,12 @@ static int stream_args_ok(const void *info, const void *transition, const void *
     return TORBI_HIP_OK;
 }
 
+// the per-push arguments of torbi_hip_stream_push_lag and torbi_hip_stream_band_push; `inputs`: nothing that a push with
+// frames reads is null
+static int stream_push_args_ok(int Tc, bool inputs, int max_lag, const void *forced_out) {
+    return Tc < 0 || (Tc > 0 && !inputs) || max_lag < -1 || (max_lag >= 0 && !forced_out) ? TORBI_HIP_EINVAL : TORBI_HIP_OK;
+}
+
 // Streams per workgroup of a push's forward kernel (stream_forward_kernel<G, *>): as many as the double-buffered rows let
 // share one pass over the matrix, but no fewer workgroups than compute units while there are streams for them.
 static int stream_tile(int B, int S, int device) {
@@ -2227,9 +2237,8 @@ int torbi_hip_stream_push_lag(const float *observation, int Tc, const int32_t *i
                               int32_t *indices_out, int out_capacity, int32_t *counts_out, int max_lag, int32_t *forced_out,
                               int B, int S, int device, void *stream) {
     int code = stream_args_ok(info, transition, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code == TORBI_HIP_OK) code = stream_push_args_ok(Tc, observation && transition_t && initial, max_lag, forced_out);
     if (code != TORBI_HIP_OK) return code;
-    if (Tc < 0 || (Tc > 0 && (!observation || !transition_t || !initial))) return TORBI_HIP_EINVAL;
-    if (max_lag < -1 || (max_lag >= 0 && !forced_out)) return TORBI_HIP_EINVAL;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2299,7 +2308,7 @@ static bool stream_band_shape(int S, int reach_left, int reach_right) {
 int torbi_hip_stream_band_covers(int B, int S, int reach_left, int reach_right, float background, int device) {
     (void)device;
     if (B < 1 || !stream_band_shape(S, reach_left, reach_right)) return 0;
-    return background != background || background == INFINITY ? 0 : 1;
+    return background_ok(background) ? 1 : 0;
 }
 
 // Streams per workgroup of stream_band_forward_kernel<G>: stream_tile's rule with the band kernel's LDS (rows with halos,
@@ -2338,9 +2347,8 @@ int torbi_hip_stream_band_push(const float *observation, int Tc, const int32_t *
                                int B, int S, int device, void *stream) {
     // torbi_hip_stream_push_lag's argument rules, the diagonals standing where its matrix stands; then the band's own
     int code = stream_args_ok(info, diagonals, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
+    if (code == TORBI_HIP_OK) code = stream_push_args_ok(Tc, observation && initial, max_lag, forced_out);
     if (code != TORBI_HIP_OK) return code;
-    if (Tc < 0 || (Tc > 0 && (!observation || !initial))) return TORBI_HIP_EINVAL;
-    if (max_lag < -1 || (max_lag >= 0 && !forced_out)) return TORBI_HIP_EINVAL;
     if (reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
     if (!torbi_hip_stream_band_covers(B, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
     DeviceGuard guard(device);
@@ -2483,28 +2491,28 @@ int torbi_hip_stream_posterior_flush(const int32_t *info, const float *expa, voi
 // the matrices the band route takes: torbi_hip_forward_backward_band_covers' rule for (S, band, background)
 static bool stream_smooth_band_shape(int S, int reach_left, int reach_right) {
     if (S < 1 || S > spb::kMaxStates || reach_left < 0 || reach_right < 0) return false;
-    const int W = spb::band_of(S, reach_left, reach_right).W;
+    const int W = fbb::band_of(S, reach_left, reach_right).W;
     return (W < S ? W : S) <= spb::kMaxWindow;               // at most 64 in-band entries in a matrix row
 }
 
 int torbi_hip_stream_smooth_band_covers(int B, int S, int reach_left, int reach_right, float background, int device) {
     (void)device;
     if (B < 1 || !stream_smooth_band_shape(S, reach_left, reach_right)) return 0;
-    return background != background || background == INFINITY ? 0 : 1;
+    return background_ok(background) ? 1 : 0;
 }
 
 // Streams per workgroup of spb_forward_kernel<G> / spb_backward_kernel<G>: stream_tile's rule with the band kernels' LDS
 int torbi_hip_stream_smooth_band_tile(int B, int S, int reach_left, int reach_right, int device) {
     if (B < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
     if (!stream_smooth_band_shape(S, reach_left, reach_right)) return TORBI_HIP_EUNSUPPORTED;
-    const int halo = spb::band_of(S, reach_left, reach_right).halo;
+    const int halo = fbb::band_of(S, reach_left, reach_right).halo;
     return items_per_workgroup(spb::kMaxGroup, B, 1, cu_count(device),
                                [&](int G) { return spb::lds_bytes(G, S, halo) <= (size_t)spb::kMaxLdsBytes; });
 }
 
 size_t torbi_hip_stream_smooth_band_diagonals_size(int S, int reach_left, int reach_right) {
     if (S < 1 || reach_left < 0 || reach_right < 0) return 0;
-    const spb::Band band = spb::band_of(S, reach_left, reach_right);
+    const fbb::Band band = fbb::band_of(S, reach_left, reach_right);
     return (size_t)2 * band.W * band.Sd * sizeof(float);
 }
 
@@ -2515,16 +2523,10 @@ int torbi_hip_stream_smooth_band_prepare(const float *transition, int S, int rea
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const spb::Band band = spb::band_of(S, reach_left, reach_right);
-    const size_t cells = (size_t)band.W * band.Sd;
-    const float ebg = background == -INFINITY ? 0.f : expf(background);
-    hipError_t e;
-    hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, st,
-                       transition, diagonals_out, diagonals_out + cells, ok_out, ebg, band.reach_left, band.W, band.Sd, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, ok_out, background, band.reach_left,
-                       band.reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const fbb::Band band = fbb::band_of(S, reach_left, reach_right);
+    const hipError_t e = fbb::prepare_and_verify(transition, band, diagonals_out, diagonals_out + (size_t)band.W * band.Sd, ok_out,
+                                                 exp_background(background), background, S, st);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(spb::spb_verdict_kernel, dim3(1), dim3(1), 0, st, ok_out);
     return (int)hipGetLastError();
 }
@@ -2541,7 +2543,7 @@ static int stream_smooth_band_args_ok(const void *info, const void *diagonals, i
 }
 
 // the backward sweep of a push (Tc >= 0) or a flush (Tc < 0)
-static int stream_smooth_band_sweep(const int32_t *info, int Tc, const float *diagonals, const spb::Band &band, float ebg, int G,
+static int stream_smooth_band_sweep(const int32_t *info, int Tc, const float *diagonals, const fbb::Band &band, float ebg, int G,
                                     const StreamPosteriorState &ss, int capacity, float *posterior_out, int out_capacity,
                                     int32_t *counts_out, int lag, int B, int S, hipStream_t st) {
     by_value<8, 4, 2, 1>(G, [&](auto g) {
@@ -2566,8 +2568,8 @@ int torbi_hip_stream_smooth_band_push(const float *observation, int Tc, const in
     if (guard.err != hipSuccess) return (int)guard.err;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const StreamPosteriorState ss = stream_posterior_state(state, B, S, capacity);
-    const spb::Band band = spb::band_of(S, reach_left, reach_right);
-    const float ebg = background == -INFINITY ? 0.f : expf(background);
+    const fbb::Band band = fbb::band_of(S, reach_left, reach_right);
+    const float ebg = exp_background(background);
     const int G = torbi_hip_stream_smooth_band_tile(B, S, reach_left, reach_right, device);
     if (Tc > 0) {
         by_value<8, 4, 2, 1>(G, [&](auto g) {
@@ -2590,8 +2592,7 @@ int torbi_hip_stream_smooth_band_flush(const int32_t *info, const float *diagona
     if (code != TORBI_HIP_OK) return code;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
-    const spb::Band band = spb::band_of(S, reach_left, reach_right);
-    return stream_smooth_band_sweep(info, -1, diagonals, band, background == -INFINITY ? 0.f : expf(background),
+    return stream_smooth_band_sweep(info, -1, diagonals, fbb::band_of(S, reach_left, reach_right), exp_background(background),
                                     torbi_hip_stream_smooth_band_tile(B, S, reach_left, reach_right, device),
                                     stream_posterior_state(state, B, S, capacity), capacity, posterior_out, out_capacity, counts_out,
                                     0, B, S, static_cast<hipStream_t>(stream));
@@ -2892,16 +2893,9 @@ struct BandPreamble {
     hipError_t err;
     BandPreamble(const fbb::Layout &l, const float *observation, const int32_t *batch_frames, const float *transition,
                  const float *initial, float background, int B, int T, int S, int device, hipStream_t st)
-        : guard(device), ebg(background == -INFINITY ? 0.f : expf(background)), halo(std::max(l.reach_left, l.reach_right)),
-          err(guard.err) {
+        : guard(device), ebg(exp_background(background)), halo(l.halo), err(guard.err) {
         if (err != hipSuccess) return;
-        const size_t cells = (size_t)l.W * l.Sd;
-        hipLaunchKernelGGL(fbb::fb_band_prepare_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0,
-                           st, transition, l.Df, l.Db, l.flag, ebg, l.reach_left, l.W, l.Sd, S);
-        if ((err = hipGetLastError()) != hipSuccess) return;
-        hipLaunchKernelGGL(fbb::fb_band_verify_kernel, dim3(S), dim3(64), 0, st, transition, l.flag, background, l.reach_left,
-                           l.reach_right, S);
-        if ((err = hipGetLastError()) != hipSuccess) return;
+        if ((err = fbb::prepare_and_verify(transition, l, l.Df, l.Db, l.flag, ebg, background, S, st)) != hipSuccess) return;
         const size_t rows = (size_t)B * T;
         hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
                            initial, l.m, B, T, S);
@@ -2919,9 +2913,9 @@ int torbi_hip_forward_backward_band_covers(int B, int T, int S, int reach_left, 
                                            int device) {
     (void)device;
     if (B < 1 || T < 1 || S < 1 || S > fbb::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
-    if (background != background || background == INFINITY) return 0;
+    if (!background_ok(background)) return 0;
     if (!fb_shape_in_range(B, T, S)) return 0;
-    const int W = fbb::clamp_reach(reach_left, S) + fbb::clamp_reach(reach_right, S) + 1;
+    const int W = fbb::band_of(S, reach_left, reach_right).W;
     return (W < S ? W : S) <= fbb::kMaxWindow ? 1 : 0;       // at most 64 in-band entries in a matrix row
 }
 
@@ -2970,9 +2964,8 @@ static int fb_band_counts_tile(int B, int S, int halo, int W, int cus) {
 int torbi_hip_forward_backward_counts_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
                                                   int device) {
     if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device)) return 0;
-    const int left = fbb::clamp_reach(reach_left, S), right = fbb::clamp_reach(reach_right, S);
-    return fbb::lds_bytes(1, S, std::max(left, right)) + fbb::plane_bytes(left + right + 1, S) <= (size_t)fbb::kCountsLdsBytes
-               ? 1 : 0;
+    const fbb::Band band = fbb::band_of(S, reach_left, reach_right);
+    return fbb::lds_bytes(1, S, band.halo) + fbb::plane_bytes(band.W, S) <= (size_t)fbb::kCountsLdsBytes ? 1 : 0;
 }
 
 size_t torbi_hip_forward_backward_counts_band_workspace_bytes(int B, int T, int S, int reach_left, int reach_right) {
@@ -3175,7 +3168,7 @@ int torbi_hip_k_best_band_covers(int B, int T, int S, int k, int reach_left, int
     if (S % 4 != 0 || S < kbb::kMinStates || S > kbb::kMaxStates || (long long)reach_left + reach_right + 4 > kbb::kMaxWindow)
         return 0;
     if (kbb::lds_bytes(1, S, k, reach_left, reach_right) > (size_t)kbb::kMaxLdsBytes) return 0;
-    return background != background || background == INFINITY ? 0 : 1;
+    return background_ok(background) ? 1 : 0;
 }
 
 size_t torbi_hip_k_best_band_workspace_bytes(int B, int T, int S, int k, int reach_left, int reach_right) {

@@ -15,16 +15,13 @@ and returns the older ones along the path that is best at the newest frame (STRE
 """
 import ctypes
 import math
-import operator
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, band_route, inputs
-
-# ring slots of a new decoder; the ring doubles when a push needs more
-INITIAL_CAPACITY = 16
+from . import _lib, band_route, inputs, stream_ring
+from .stream_ring import INITIAL_CAPACITY
 
 ROUTES = band_route.ROUTES
 
@@ -51,16 +48,11 @@ def stream_route(transition: Optional[torch.Tensor], batch: int, states: int, gp
     states = int(states)
     if transition is not None and tuple(transition.shape) != (states, states):
         raise ValueError(f'transition must be ({states}, {states})')
-    device = inputs._compute_device(gpu)
-    original = transition
-    transition, uniform, _ = inputs.model(transition, None, log_probs, states, device)
-    if transition is None:
-        original = transition = torch.full((states, states), uniform, dtype=torch.float32, device=device)
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    device, original, trans, _ = stream_ring.model(transition, None, log_probs, states, gpu)
     return 'dense' if _band_plan(trans, original, batch, states, device.index or 0)[0] is None else 'band'
 
 
-class StreamDecoder:
+class StreamDecoder(stream_ring.StreamRing):
     """Viterbi decoding of `batch` independent streams whose frames arrive in pieces.
 
     `transition` (states, states) [next, prev], `initial` (states,) and `log_probs` mean what they mean to
@@ -98,33 +90,9 @@ class StreamDecoder:
     def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
                  initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0,
                  max_lag: Optional[int] = None, route: str = 'auto'):
-        if batch < 1 or states < 1:
-            raise ValueError('StreamDecoder needs batch >= 1 and states >= 1')
-        band_route.check_route(route, ValueError)
-        if max_lag is not None:
-            try:
-                if isinstance(max_lag, bool):
-                    raise TypeError
-                max_lag = operator.index(max_lag)
-            except TypeError:
-                raise ValueError(f'max_lag must be None or an integer >= 0, got {max_lag!r}') from None
-            if max_lag < 0:
-                raise ValueError(f'max_lag must be None or an integer >= 0, got {max_lag!r}')
-        self.max_lag = max_lag
-        self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
-        S = self.states
-        self.device = inputs._compute_device(gpu)
-        # the model of from_probabilities (torbi_amd/inputs.py): chunking cannot change a bit
-        original = transition
-        transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
-        if transition is None:
-            original = transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
-        self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
-        self.transition = transition.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(self.transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
-            raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
-        self._frames = np.zeros(self.batch, dtype=np.int64)        # frames pushed
-        self._base = np.zeros(self.batch, dtype=np.int64)          # first frame not yet returned
+        self._check(batch, states, route)
+        self.max_lag = stream_ring.depth('max_lag', max_lag, optional=True)
+        original, self.transition = self._model(batch, states, transition, initial, log_probs, gpu)
         self._forced = np.zeros(self.batch, dtype=np.int64)        # frames returned by forced commits (max_lag)
         if gpu is None:
             self._rows = [[] for _ in range(self.batch)]            # posterior rows of frames base-1 .. n-1 (host)
@@ -143,24 +111,9 @@ class StreamDecoder:
 
     # ------------------------------------------------------------------ public
     @property
-    def frames(self) -> torch.Tensor:
-        """(batch,) int64: frames pushed to each stream since it started."""
-        return torch.from_numpy(self._frames.copy())
-
-    @property
-    def pending(self) -> torch.Tensor:
-        """(batch,) int64: frames pushed and not yet returned."""
-        return torch.from_numpy(self._frames - self._base)
-
-    @property
     def forced(self) -> torch.Tensor:
         """(batch,) int64: frames of each stream returned by forced commits (`max_lag`) since it started."""
         return torch.from_numpy(self._forced.copy())
-
-    @property
-    def capacity(self) -> int:
-        """Ring slots per stream on the device; on the host the most rows a stream has held."""
-        return self._held if self.gpu is None else self._capacity
 
     def push(self, observation: torch.Tensor, frames: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """Append frames to the streams and return what became decided.
@@ -169,15 +122,7 @@ class StreamDecoder:
         1-D int32 tensors on the compute device: the indices of the frames this push decided, oldest first.  On the GPU this
         reads one small per-stream count array back, so every call synchronises the host with the current stream once.
         """
-        if observation.dim() != 3 or observation.shape[0] != self.batch or observation.shape[2] != self.states:
-            raise ValueError(f'observation must be ({self.batch}, Tc, {self.states}), got {tuple(observation.shape)}')
-        Tc = int(observation.shape[1])
-        if frames is None:
-            f = np.full(self.batch, Tc, dtype=np.int64)
-        else:
-            f = torch.as_tensor(frames).detach().to('cpu', torch.int64).reshape(-1).numpy().copy()
-            if f.shape[0] != self.batch or (f < 0).any() or (f > Tc).any():
-                raise ValueError(f'frames must hold {self.batch} counts in 0 .. {Tc}')
+        _, f = self._push_front(observation, frames)
         obs = inputs.observation(observation, self.log_probs, self.device)
         if self.gpu is None:
             return self._push_host(obs, f)
@@ -187,13 +132,11 @@ class StreamDecoder:
         """End streams `items` (default: all): return their remaining indices (one 1-D int32 tensor per item, in the
         order given) and reset them, so that their next push starts a new sequence from `initial`.  The final state is the
         first NaN of the newest posterior row, otherwise its first maximum (the reference's argmax)."""
-        items = list(range(self.batch)) if items is None else [int(k) for k in items]
-        if any(k < 0 or k >= self.batch for k in items):
-            raise IndexError(f'stream index out of range 0 .. {self.batch - 1}')
+        items, marks = self._flush_front(items)
         if self.gpu is None:
             rest = {k: self._flush_host(k) for k in items}
         else:
-            rest = self._flush_device(sorted(set(items)))
+            rest = self._flush_device(marks)
         for k in set(items):
             self._frames[k] = self._base[k] = self._forced[k] = 0
         return [rest[k] for k in items]
@@ -290,30 +233,21 @@ class StreamDecoder:
         """(reach_left, reach_right, background, diagonals) where the band route takes the decoder's matrix, else None --
         or, under 'band', a RuntimeError that names the reason.  The diagonals come from a private copy of the matrix, so that
         the look, the extraction and the device's verdict all speak of the same values whatever the caller later writes."""
-        index = self.device.index or 0
-        over, reason = _band_plan(self.transition, original, self.batch, self.states, index)
+        over, reason = _band_plan(self.transition, original, self.batch, self.states, self.device.index or 0)
         if over is not None:
-            left, right, background = over
-            private = self.transition.clone()
-            diagonals = torch.empty(self._lib.torbi_hip_stream_band_diagonals_bytes(self.states, left, right) // 4,
-                                    dtype=torch.float32, device=self.device)
-            ok = torch.empty(1, dtype=torch.int32, device=self.device)
-            _, index, stream = _lib.launch(self.device)
-            _lib.check(self._lib.torbi_hip_stream_band_prepare(private.data_ptr(), self.states, left, right,
-                                                               ctypes.c_float(background), diagonals.data_ptr(), ok.data_ptr(),
-                                                               index, stream), 'torbi_hip_stream_band_prepare')
-            if int(ok.item()) == 1:                             # (the one read-back of the constructor)
-                return left, right, background, diagonals
-            reason = f'an entry outside the band of reach {left}/{right} differs from the background {background}'
+            diagonals, reason = self._band_diagonals('torbi_hip_stream_band_diagonals_bytes', 'torbi_hip_stream_band_prepare',
+                                                     self.transition.clone(), over)
+            if diagonals is not None:
+                return (*over, diagonals)
         return band_route.choose(route, None, reason, None, "StreamDecoder(route='band')")
 
     def _grow(self, capacity: int) -> None:
-        """Ring of `capacity` slots (at least double the old one); pending rows and the newest row move to their new
-        slots by one device copy, the walk memo starts empty.  On the band route the rows are the pending frames' pointer
-        rows (moved through an int32 view) and the newest row is the carried row behind the memo."""
+        """Ring of round_capacity(`capacity`) slots (a push that needs more than the old ring at least doubles it); pending
+        rows and the newest row move to their new slots by one device copy, the walk memo starts empty.  On the band route the
+        rows are the pending frames' pointer rows (moved through an int32 view) and the newest row is the carried row behind
+        the memo."""
         B, S = self.batch, self.states
-        capacity = max(int(capacity), 2 * self._capacity)
-        capacity = 1 << (capacity - 1).bit_length()
+        capacity = self.round_capacity(capacity)
         nbytes = self._lib.torbi_hip_stream_state_bytes(B, S, capacity)
         if nbytes == 0:
             raise ValueError('torbi_hip_stream_state_bytes rejected the shape')
@@ -322,35 +256,15 @@ class StreamDecoder:
         state[B * capacity * S * 4:B * capacity * (S + 1) * 4].zero_()
         if self._state is not None and self._band is not None:
             old = self._state[:B * self._capacity * S * 4].view(torch.int32).view(B, self._capacity, S)
-            items = [np.full(int(self._frames[b] - self._base[b]), b, dtype=np.int64) for b in range(B)]
-            frames = [np.arange(int(self._base[b]), int(self._frames[b]), dtype=np.int64) for b in range(B)]
-            bi = torch.from_numpy(np.concatenate(items)).to(self.device)
-            fr = torch.from_numpy(np.concatenate(frames)).to(self.device)
-            if bi.numel():
-                ring.view(torch.int32)[bi, fr % capacity] = old[bi, fr % self._capacity]
+            self._move([(ring.view(torch.int32), old)], self._moving(self._base), capacity)
             state[B * capacity * (S + 1) * 4:nbytes] = self._state[B * self._capacity * (S + 1) * 4:self._state_bytes]
         elif self._state is not None:
-            items, frames = [], []
-            for b in range(B):
-                n = int(self._frames[b])
-                if n == 0:
-                    continue
-                lo = min(int(self._base[b]), n - 1)
-                frames.append(np.arange(lo, n, dtype=np.int64))
-                items.append(np.full(n - lo, b, dtype=np.int64))
-            if items:
-                bi = torch.from_numpy(np.concatenate(items)).to(self.device)
-                fr = torch.from_numpy(np.concatenate(frames)).to(self.device)
-                ring[bi, fr % capacity] = self._ring()[bi, fr % self._capacity]
+            self._move([(ring, self._ring())], self._newest_and_pending(), capacity)
         self._state, self._capacity, self._state_bytes = state, capacity, nbytes
 
     def _ring(self) -> torch.Tensor:
         B, S, cap = self.batch, self.states, self._capacity
         return self._state[:B * cap * S * 4].view(torch.float32).view(B, cap, S)
-
-    def _info(self, pending: np.ndarray, third: np.ndarray) -> torch.Tensor:
-        info = np.stack([pending, self._base % self._capacity, third, (self._frames == 0).astype(np.int64)], axis=1)
-        return torch.from_numpy(info.astype(np.int32)).to(self.device)
 
     def _results(self, out: torch.Tensor, counts: torch.Tensor, what: str) -> np.ndarray:
         """`counts` (B,) or, from a push with a maximum lag, (2, B): counts and forced counts, read back in one copy."""
@@ -402,11 +316,9 @@ class StreamDecoder:
         self._base += got
         return [out[b, :got[b]] for b in range(B)]
 
-    def _flush_device(self, items: List[int]) -> dict:
+    def _flush_device(self, marks: np.ndarray) -> dict:
         B, S = self.batch, self.states
         pending = self._frames - self._base
-        marks = np.zeros(B, dtype=np.int64)
-        marks[items] = 1
         info = self._info(pending, marks)
         out = torch.empty((B, max(1, int(pending.max()))), dtype=torch.int32, device=self.device)
         counts = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -421,4 +333,4 @@ class StreamDecoder:
                 out.data_ptr(), out.shape[1], counts.data_ptr(), B, S, index, stream),
                 'torbi_hip_stream_flush')
         got = self._results(out, counts, 'torbi_hip_stream_flush')
-        return {k: out[k, :got[k]] for k in items}
+        return {k: out[k, :got[k]] for k in np.flatnonzero(marks).tolist()}

@@ -19,10 +19,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, band_route, inputs
-
-# ring slots of a new decoder
-INITIAL_CAPACITY = 16
+from . import _lib, band_route, inputs, stream_ring
+from .stream_ring import INITIAL_CAPACITY
 
 ROUTES = band_route.ROUTES
 # Where 'auto' takes a covered band: the classes in which tools/stream_posterior_probe.py --band measured the band route's
@@ -71,16 +69,13 @@ def stream_posterior_route(transition: Optional[torch.Tensor], batch: int, state
     states = int(states)
     if tuple(transition.shape) != (states, states):
         raise ValueError(f'transition must be ({states}, {states})')
-    device = inputs._compute_device(gpu)
-    original = transition
-    transition, _, _ = inputs.model(transition, None, log_probs, states, device)
-    trans = transition.to(device=device, dtype=torch.float32).contiguous()
+    device, original, trans, _ = stream_ring.model(transition, None, log_probs, states, gpu)
     band, why = _band_plan(trans, original, batch, states, device.index or 0)
     pays = lambda left, right, background: _band_pays(int(batch), states, left, right)
     return 'dense' if band_route.choose('auto', band, why, pays, 'stream_posterior_route') is None else 'band'
 
 
-class StreamPosteriors:
+class StreamPosteriors(stream_ring.StreamRing):
     """State posteriors of `batch` independent streams whose frames arrive in pieces; memory per stream is bounded by `lag`.
 
     `transition` (states, states) [next, prev], `initial` (states,), `log_probs` and `gpu` mean what they mean to
@@ -125,36 +120,15 @@ class StreamPosteriors:
     def __init__(self, batch: int, states: int, transition: Optional[torch.Tensor] = None,
                  initial: Optional[torch.Tensor] = None, log_probs: bool = False, gpu: Optional[int] = 0, lag: int = 8,
                  route: str = 'dense', band: Optional[Tuple[int, int, float]] = None):
-        if batch < 1 or states < 1:
-            raise ValueError('StreamPosteriors needs batch >= 1 and states >= 1')
-        band_route.check_route(route, ValueError)
+        self._check(batch, states, route)
         if band is not None:
             band = _stated_band(band)
             if route == 'dense':
                 raise ValueError("band= states a band for the band route: pass route='band' or 'auto' with it, not 'dense'")
-        try:
-            if isinstance(lag, bool):
-                raise TypeError
-            lag = operator.index(lag)
-        except TypeError:
-            raise ValueError(f'lag must be an integer >= 0, got {lag!r}') from None
-        if lag < 0:
-            raise ValueError(f'lag must be an integer >= 0, got {lag!r}')
-        self.lag = lag
-        self.batch, self.states, self.log_probs, self.gpu = int(batch), int(states), bool(log_probs), gpu
-        S = self.states
-        self.device = inputs._compute_device(gpu)
-        original = transition
-        transition, uniform, initial = inputs.model(transition, initial, log_probs, S, self.device)
-        if transition is None:
-            original = transition = torch.full((S, S), uniform, dtype=torch.float32, device=self.device)
-        self.initial = initial.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(transition.shape) != (S, S) or tuple(self.initial.shape) != (S,):
-            raise ValueError(f'transition must be ({S}, {S}) and initial ({S},)')
-        self._frames = np.zeros(self.batch, dtype=np.int64)        # frames pushed
-        self._base = np.zeros(self.batch, dtype=np.int64)          # first frame not yet returned
+        self.lag = stream_ring.depth('lag', lag)
+        original, transition = self._model(batch, states, transition, initial, log_probs, gpu)
         if gpu is None:
-            self._E = torch.exp(transition.to(torch.float32).to(torch.float64))      # [next, prev]
+            self._E = torch.exp(transition.to(torch.float64))                         # [next, prev]
             self._rows = [[] for _ in range(self.batch)]            # (a_t, e_t, c_t) of the pending frames
             self._carry = [None] * self.batch                       # (a, c) of the newest frame
             self._sum = [0.] * self.batch                           # running sums of log c_t + m_t
@@ -162,7 +136,7 @@ class StreamPosteriors:
             self.route = 'host'
         else:
             self._lib = _lib.load()
-            private = transition.to(device=self.device, dtype=torch.float32).clone().contiguous()
+            private = transition.clone()
             self._band = self._prepare_band(private, original, route, band)
             self.route = 'dense' if self._band is None else 'band'
             if self._band is None:
@@ -173,27 +147,6 @@ class StreamPosteriors:
             self._grow(INITIAL_CAPACITY)
 
     # ------------------------------------------------------------------ public
-    @staticmethod
-    def round_capacity(slots: int) -> int:
-        """Ring slots the device route allocates for `slots` rows per stream: the power of two at or above, at least
-        INITIAL_CAPACITY."""
-        return max(INITIAL_CAPACITY, 1 << (max(int(slots), 1) - 1).bit_length())
-
-    @property
-    def frames(self) -> torch.Tensor:
-        """(batch,) int64: frames pushed to each stream since it started."""
-        return torch.from_numpy(self._frames.copy())
-
-    @property
-    def pending(self) -> torch.Tensor:
-        """(batch,) int64: frames pushed and not yet returned."""
-        return torch.from_numpy(self._frames - self._base)
-
-    @property
-    def capacity(self) -> int:
-        """Ring slots per stream on the device; on the host the most rows a stream has held."""
-        return self._held if self.gpu is None else self._capacity
-
     @property
     def log_likelihood(self) -> torch.Tensor:
         """(batch,) float32 on the compute device: log P(frames so far), the fp64 running sum of log c_t + m_t rounded on
@@ -215,7 +168,7 @@ class StreamPosteriors:
             a = torch.stack([torch.zeros(S, dtype=torch.float64) if k is None else k[0] for k in self._carry])
             c = torch.stack([torch.ones((), dtype=torch.float64) if k is None else k[1] for k in self._carry])
         else:
-            slot = self._to_device((np.maximum(self._frames, 1) - 1) % self._capacity)
+            slot = self._upload((np.maximum(self._frames, 1) - 1) % self._capacity)
             item = torch.arange(B, device=self.device)
             ring_a, _, ring_c, _ = self._rings()
             a, c = ring_a[item, slot], ring_c[item, slot]
@@ -231,15 +184,7 @@ class StreamPosteriors:
         f_b >= 1, else 0.  Performs NO host synchronisation: k_b is a function of values the host already holds, so nothing
         is read back (the per-call stream table goes to the device through pinned memory).
         """
-        if observation.dim() != 3 or observation.shape[0] != self.batch or observation.shape[2] != self.states:
-            raise ValueError(f'observation must be ({self.batch}, Tc, {self.states}), got {tuple(observation.shape)}')
-        Tc = int(observation.shape[1])
-        if frames is None:
-            f = np.full(self.batch, Tc, dtype=np.int64)
-        else:
-            f = torch.as_tensor(frames).detach().to('cpu', torch.int64).reshape(-1).numpy().copy()
-            if f.shape[0] != self.batch or (f < 0).any() or (f > Tc).any():
-                raise ValueError(f'frames must hold {self.batch} counts in 0 .. {Tc}')
+        _, f = self._push_front(observation, frames)
         if not f.any():
             return [torch.empty((0, self.states), dtype=torch.float32, device=self.device) for _ in range(self.batch)]
         obs = inputs.observation(observation, self.log_probs, self.device)
@@ -258,23 +203,21 @@ class StreamPosteriors:
         order given -- the stream's remaining frames as gamma_{t|n} -- and final (len(items),) float32, their log-likelihoods.
         The streams are reset: their next push starts from `initial`.  A stream without frames returns a (0, states) tensor
         and a log-likelihood of 0.  Reads nothing back."""
-        items = list(range(self.batch)) if items is None else [int(k) for k in items]
-        if any(k < 0 or k >= self.batch for k in items):
-            raise IndexError(f'stream index out of range 0 .. {self.batch - 1}')
-        final = self.log_likelihood[self._to_device(np.asarray(items, dtype=np.int64))]
-        chosen = sorted(set(items))
+        items, marks = self._flush_front(items)
+        final = self.log_likelihood[self._upload(np.asarray(items, dtype=np.int64))]
+        chosen = np.flatnonzero(marks).tolist()
         if self.gpu is None:
             rest = {k: self._sweep_host(k, int(self._frames[k] - self._base[k])) for k in chosen}
             for k in chosen:
                 self._rows[k], self._carry[k], self._sum[k] = [], None, 0.
         else:
-            rest = self._flush_device(chosen)
+            rest = self._flush_device(chosen, marks) if chosen else {}        # (no stream ends: nothing to launch)
         for k in chosen:
             self._frames[k] = self._base[k] = 0
         return [rest[k] for k in items], final
 
     # ------------------------------------------------------------------ shared
-    def _to_device(self, values: np.ndarray) -> torch.Tensor:
+    def _upload(self, values: np.ndarray) -> torch.Tensor:
         """A small host array on the compute device without a host synchronisation (through pinned memory)."""
         host = torch.from_numpy(np.ascontiguousarray(values))
         if self.gpu is None:
@@ -282,7 +225,7 @@ class StreamPosteriors:
         return host.pin_memory().to(self.device, non_blocking=True)
 
     def _mask(self, flags: np.ndarray) -> torch.Tensor:
-        return self._to_device(flags.astype(np.bool_))
+        return self._upload(flags.astype(np.bool_))
 
     # ------------------------------------------------------------------ host route
     def _sweep_host(self, b: int, count: int, pending: Optional[int] = None) -> torch.Tensor:
@@ -354,17 +297,10 @@ class StreamPosteriors:
                                      lambda left, right, background: _band_pays(B, S, left, right), who)
             if over is None:
                 return None
-        left, right, background = over
-        diagonals = torch.empty(self._lib.torbi_hip_stream_smooth_band_diagonals_size(S, left, right) // 4, dtype=torch.float32,
-                                device=self.device)
-        ok = torch.empty(1, dtype=torch.int32, device=self.device)
-        _, index, stream = _lib.launch(self.device)
-        _lib.check(self._lib.torbi_hip_stream_smooth_band_prepare(private.data_ptr(), S, left, right, ctypes.c_float(background),
-                                                                  diagonals.data_ptr(), ok.data_ptr(), index, stream),
-                   'torbi_hip_stream_smooth_band_prepare')
-        if int(ok.item()) == 1:                                 # (the one read-back of the constructor)
-            return left, right, ctypes.c_float(background), diagonals
-        reason = f'an entry outside the band of reach {left}/{right} differs from the background {background}'
+        diagonals, reason = self._band_diagonals('torbi_hip_stream_smooth_band_diagonals_size',
+                                                 'torbi_hip_stream_smooth_band_prepare', private, over)
+        if diagonals is not None:
+            return over[0], over[1], ctypes.c_float(over[2]), diagonals
         if stated is not None:
             raise RuntimeError(f'{who}: {reason}')
         return band_route.choose(route, None, reason, None, who)
@@ -392,24 +328,8 @@ class StreamPosteriors:
         state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         if self._state is not None:
             state[:8 * B] = self._state[:8 * B]
-            items, frames = [], []
-            for b in range(B):
-                n = int(self._frames[b])
-                if n == 0:
-                    continue
-                lo = min(int(self._base[b]), n - 1)
-                frames.append(np.arange(lo, n, dtype=np.int64))
-                items.append(np.full(n - lo, b, dtype=np.int64))
-            if items:
-                bi, fr = self._to_device(np.concatenate(items)), np.concatenate(frames)
-                new, old = self._to_device(fr % capacity), self._to_device(fr % self._capacity)
-                for dst, src in zip(self._rings(state, capacity), self._rings()):
-                    dst[bi, new] = src[bi, old]
+            self._move(zip(self._rings(state, capacity), self._rings()), self._newest_and_pending(), capacity)
         self._state, self._capacity, self._state_bytes = state, capacity, nbytes
-
-    def _info(self, pending: np.ndarray, third: np.ndarray) -> torch.Tensor:
-        info = np.stack([pending, self._base % self._capacity, third, (self._frames == 0).astype(np.int64)], axis=1)
-        return self._to_device(info.astype(np.int32))
 
     def _push_device(self, obs: torch.Tensor, f: np.ndarray, counts: np.ndarray) -> List[torch.Tensor]:
         B, S = self.batch, self.states
@@ -433,11 +353,9 @@ class StreamPosteriors:
                 self.initial.data_ptr(), *tail), 'torbi_hip_stream_posterior_push')
         return [out[b, :counts[b]] for b in range(B)]
 
-    def _flush_device(self, items: List[int]) -> dict:
+    def _flush_device(self, items: List[int], marks: np.ndarray) -> dict:
         B, S = self.batch, self.states
         pending = self._frames - self._base
-        marks = np.zeros(B, dtype=np.int64)
-        marks[items] = 1
         info = self._info(pending, marks)
         out = torch.empty((B, max(1, int(pending[items].max())), S), dtype=torch.float32, device=self.device)
         _, index, stream = _lib.launch(self.device)

@@ -12,7 +12,7 @@ import torch
 from . import data as _data
 from . import inputs, timer
 from .inputs import _prepared_transition
-from .viterbi import decode, decode_cpu, decode_uniform, uniform_supported
+from .viterbi import check_dtypes, decode, decode_cpu, decode_uniform, uniform_supported
 
 # reference torbi/config/defaults.py:80,83
 BATCH_SIZE = 512
@@ -95,6 +95,9 @@ def from_probabilities(
         transition, uniform, initial = inputs.model(transition, initial, log_probs, states, device)
         if _model is not None:
             _model.update(initial=initial, transition=transition, uniform=uniform)
+    # the operator refuses a model that is not float32, like upstream's: said here, before the observation is written in
+    # place, so that a call that raises has launched and changed nothing
+    check_dtypes(None, None, transition, initial)
 
     if gpu is None:
         # the reference's CPU route (core.py:145-201 with device = 'cpu') on the host twin of the operator

@@ -47,10 +47,13 @@ def frames(batch_frames, B: int, T: int, device) -> torch.Tensor:
     return batch_frames.to(device=device, dtype=torch.int32).contiguous()
 
 
-def model(transition, initial, log_probs: bool, states: int, device):
+def model(transition, initial, log_probs: bool, states: int, device, plain: bool = False):
     """(transition or None, uniform or None, initial) in log space on `device` (core.py:161-187).  A missing initial
     becomes log(1/S + tiny); a missing transition is returned as the float value of upstream's float32 fill log(1/S)
-    (`torch.full((S, S), uniform)` gives upstream's matrix).  Dtypes are kept."""
+    (`torch.full((S, S), uniform)` gives upstream's matrix).  Dtypes are kept, like upstream, whose operator then refuses
+    what is not float32 -- unless `plain`: the device routes of the features that convert (posteriors, counts, k-best,
+    sampling, the stream classes) take the matrix as `device_matrix` gives it, the one tensor their band planner looks at
+    and their kernels read (their `gpu=None` routes compute in the dtype they are given)."""
     if initial is None:
         initial = torch.full((states,), math.log((1. / states) + torch.finfo(torch.float32).tiny), dtype=torch.float32,
                              device=device)
@@ -59,6 +62,8 @@ def model(transition, initial, log_probs: bool, states: int, device):
     uniform = None
     if transition is None:
         uniform = float(torch.tensor(math.log(1. / states), dtype=torch.float32))
+    elif plain:
+        transition = device_matrix(transition, log_probs, device)
     elif device.type == 'cpu':
         transition = (transition if log_probs else torch.log(transition)).to(device)
     else:
@@ -101,9 +106,34 @@ def _prepared_transition(transition: torch.Tensor, log_probs: bool, device) -> t
     if kept is not None and key in kept:
         return kept[key]
     prepared = (transition if log_probs else torch.log(transition)).to(device)
-    if kept is not None:
+    if kept is not None and prepared is not transition:        # (a tensor in its own notes would never be collected)
         kept[key] = prepared
     return prepared
+
+
+def device_matrix(transition: torch.Tensor, log_probs: bool, device) -> torch.Tensor:
+    """`_prepared_transition` as every device route of a feature reads it: float32, contiguous, its base 16-byte aligned.
+    THE matrix of a call: what the band planner looks at (`viterbi.band_over` reads S * S float32 words, row-major, behind
+    the pointer and refuses anything else) is what the kernels are handed, so a band is never found in one layout and
+    promised for another, and nothing is copied twice."""
+    return plain_matrix(_prepared_transition(transition, log_probs, device))
+
+
+def plain_matrix(matrix: torch.Tensor) -> torch.Tensor:
+    """A matrix where it lives as float32, contiguous, its base 16-byte aligned: the tensor itself when it is all that --
+    whatever is known about it stays known --, else ONE copy (S x S: nothing next to a call), remembered with the tensor's
+    notes (object and version, torbi_amd/state.py) so that repeated calls look at, and hand on, the SAME copy."""
+    kept = state.notes(matrix)
+    if kept is not None and 'plain' in kept:
+        return kept['plain']
+    plain = (matrix.detach() if matrix.requires_grad else matrix).to(torch.float32).contiguous()
+    if plain.data_ptr() % 16:
+        plain = plain.clone()
+    if plain is matrix:
+        return matrix
+    if kept is not None:
+        kept['plain'] = plain
+    return plain
 
 
 def _host_log(observation: torch.Tensor) -> torch.Tensor:

@@ -108,12 +108,11 @@ def best_paths(observation: torch.Tensor, k: int, batch_frames: Optional[torch.T
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
-    original = transition
-    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device, plain=gpu is not None)
     obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         return _host(obs, frames, transition, uniform, initial, k)
-    return _routed(obs, frames, transition, original, uniform, initial, k, route)
+    return _routed(obs, frames, transition, transition, uniform, initial, k, route)
 
 
 def decode_k_best_banded_workspace_bytes(B: int, T: int, S: int, k: int, reach_left: int, reach_right: int) -> int:
@@ -148,14 +147,15 @@ def _band_plan(trans: torch.Tensor, original: torch.Tensor, B: int, T: int, S: i
 
 
 def _routed(obs, frames, transition, original, uniform, initial, k, route, workspace=None, look=True):
-    """The device call of `decode_k_best` / `best_paths` by `route` (prepared inputs; `original`: the caller's matrix;
-    `look`: whether 'auto' may look at a matrix it has not seen)."""
+    """The device call of `decode_k_best` / `best_paths` by `route` (prepared inputs; `original`: the tensor the look at the
+    matrix is remembered with -- `best_paths`' device matrix itself, `decode_k_best`'s caller's log matrix --; `look`: whether
+    'auto' may look at a matrix it has not seen)."""
     B, T, S = obs.shape
     if uniform is not None and route == 'band':
         raise RuntimeError("k-best decoding with route='band': there is no transition matrix (the uniform model), which the "
                            'uniform route decodes; the band route needs a matrix that holds one value outside a band')
     if uniform is None and route != 'dense' and B > 0:
-        trans = transition.to(device=obs.device, dtype=torch.float32).contiguous()
+        trans = inputs.plain_matrix(transition.to(obs.device))
 
         def pays(left, right, background):      # ... and the caller's workspace must also hold the band layout
             return _band_pays(k, S, left, right) and (
@@ -182,8 +182,8 @@ def k_best_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
     if tuple(transition.shape) != (states, states):
         raise ValueError(f'transition must be ({states}, {states})')
     device = inputs._compute_device(gpu)
-    trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
-    band, why = _band_plan(trans, transition, int(batch), int(frames), states, k, device.index or 0)
+    trans = inputs.device_matrix(transition, log_probs, device)
+    band, why = _band_plan(trans, trans, int(batch), int(frames), states, k, device.index or 0)
     pays = lambda left, right, background: _band_pays(k, states, left, right)
     return 'dense' if band_route.choose('auto', band, why, pays, 'k_best_route') is None else 'band'
 

@@ -186,8 +186,9 @@ def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[to
 
 
 def _band(route, trans, original, B, T, S, index):
-    """(reach_left, reach_right, background) where `route` sends the prepared device matrix `trans` to the band route
-    ('auto' takes every band torbi_hip_forward_backward_band_covers takes), else None."""
+    """(reach_left, reach_right, background) where `route` sends the device matrix `trans` (`inputs.device_matrix`; also
+    `original`, the tensor the look is remembered with) to the band route ('auto' takes every band
+    torbi_hip_forward_backward_band_covers takes), else None."""
     if route == 'dense':
         return None
     plan = band_route.plan(trans, original, _covered, 'torbi_hip_forward_backward_band_covers', dict(batch=B, frames=T, states=S),
@@ -204,11 +205,11 @@ def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int,
         return 'uniform'
     if tuple(transition.shape) != (states, states):
         raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
-    device = inputs._compute_device(gpu)
-    if device.type == 'cpu':
+    if gpu is None:
         return 'dense'
-    trans = inputs._prepared_transition(transition, log_probs, device)
-    return 'dense' if _band('auto', trans, transition, int(batch), int(frames), states, device.index or 0) is None else 'band'
+    device = inputs._compute_device(gpu)
+    trans = inputs.device_matrix(transition, log_probs, device)
+    return 'dense' if _band('auto', trans, trans, int(batch), int(frames), states, device.index or 0) is None else 'band'
 
 
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -237,13 +238,12 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
-    original = transition
-    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device, plain=gpu is not None)
     obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
         return gamma.to(torch.float32), L.to(torch.float32)
-    band = None if uniform is not None else _band(route, transition, original, B, T, S, device.index or 0)
+    band = None if uniform is not None else _band(route, transition, transition, B, T, S, device.index or 0)
     if band is not None:
         return _run_band(obs, frames, transition, initial, *band)
     return _run(obs, frames, transition, uniform, initial)

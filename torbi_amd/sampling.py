@@ -167,7 +167,8 @@ def _band_plan(trans, original, B, T, S, N, index):
 
 
 def _band(route, trans, original, B, T, S, N, index):
-    """The band `route` takes for the prepared device matrix `trans`, or None for the dense route (`band_route.choose`)."""
+    """The band `route` takes for the device matrix `trans` (`inputs.device_matrix`; also `original`, the tensor the look is
+    remembered with), or None for the dense route (`band_route.choose`)."""
     return band_route.choose(route, *_band_plan(trans, original, B, T, S, N, index),
                              lambda left, right, background: _band_pays(B, S, left, right, N), "sample_paths(route='band')")
 
@@ -183,11 +184,11 @@ def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
     states = int(states)
     if tuple(transition.shape) != (states, states):
         raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
-    device = inputs._compute_device(gpu)
-    if device.type == 'cpu':
+    if gpu is None:
         return 'dense'
-    trans = inputs._prepared_transition(transition, log_probs, device).to(dtype=torch.float32).contiguous()
-    band = _band('auto', trans, transition, int(batch), int(frames), states, draws, device.index or 0)
+    device = inputs._compute_device(gpu)
+    trans = inputs.device_matrix(transition, log_probs, device)
+    band = _band('auto', trans, trans, int(batch), int(frames), states, draws, device.index or 0)
     return 'dense' if band is None else 'band'
 
 
@@ -229,12 +230,11 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
                            'independently); the band route needs a matrix that holds one value outside a band')
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
-    original = transition
-    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device, plain=gpu is not None)
     band = None
     if gpu is not None and uniform is None and route != 'dense':
         # (before the observation is prepared: a matrix without a band raises before anything runs)
-        band = _band(route, transition.to(dtype=torch.float32).contiguous(), original, B, T, S, draws, device.index or 0)
+        band = _band(route, transition, transition, B, T, S, draws, device.index or 0)
     obs = inputs.observation(observation, log_probs, device)
     if uniforms is None:
         uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)

@@ -39,16 +39,17 @@ def depth(name: str, value, optional: bool = False) -> Optional[int]:
 def model(transition: Optional[torch.Tensor], initial: Optional[torch.Tensor], log_probs: bool, states: int, gpu: Optional[int]):
     """(device, original, transition, initial): the model of `from_probabilities` (torbi_amd/inputs.py) as contiguous float32
     on the compute device, so that chunking cannot change a bit.  `transition=None` is the constant matrix it stands for;
-    `original` is what the band planner looks at, the caller's tensor or that matrix."""
+    `original` is the tensor the band planner's look is remembered with: the matrix itself (`inputs.plain_matrix`), which is
+    the caller's tensor where that is already a plain log matrix on the device."""
     device = inputs._compute_device(gpu)
-    original = transition
-    transition, uniform, initial = inputs.model(transition, initial, log_probs, states, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, states, device, plain=gpu is not None)
     if transition is None:
-        original = transition = torch.full((states, states), uniform, dtype=torch.float32, device=device)
+        transition = torch.full((states, states), uniform, dtype=torch.float32, device=device)
     initial = initial.to(device=device, dtype=torch.float32).contiguous()
     if tuple(transition.shape) != (states, states) or tuple(initial.shape) != (states,):
         raise ValueError(f'transition must be ({states}, {states}) and initial ({states},)')
-    return device, original, transition.to(device=device, dtype=torch.float32).contiguous(), initial
+    transition = inputs.plain_matrix(transition)
+    return device, transition, transition, initial
 
 
 class StreamRing:

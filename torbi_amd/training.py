@@ -113,8 +113,9 @@ _auto_takes = None
 
 
 def _counts_band(trans, original, B, T, S, index, route):
-    """(reach_left, reach_right) when `route` sends the counts of the prepared device matrix `trans` to the band route, else
-    None: the matrix is -inf outside a band (so the dense (S, S) result is exactly zero there),
+    """(reach_left, reach_right) when `route` sends the counts of the device matrix `trans` (`inputs.plain_matrix`;
+    `original`: the tensor the look is remembered with) to the band route, else None: the matrix is -inf outside a band (so
+    the dense (S, S) result is exactly zero there),
     torbi_hip_forward_backward_counts_band_covers takes it and, for 'auto', the class was measured faster."""
     if route == 'dense':
         return None
@@ -138,11 +139,11 @@ def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
         return 'dense'
     if tuple(transition.shape) != (states, states):
         raise RuntimeError(f'transition must have shape ({states}, {states}); got {tuple(transition.shape)}')
-    device = inputs._compute_device(gpu)
-    if device.type == 'cpu':
+    if gpu is None:
         return 'dense'
-    trans = inputs._prepared_transition(transition, log_probs, device)
-    band = _counts_band(trans, transition, int(batch), int(frames), states, device.index or 0, 'auto')
+    device = inputs._compute_device(gpu)
+    trans = inputs.device_matrix(transition, log_probs, device)
+    band = _counts_band(trans, trans, int(batch), int(frames), states, device.index or 0, 'auto')
     return 'dense' if band is None else 'band'
 
 
@@ -173,7 +174,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
     original = transition
-    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device)
+    transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device, plain=gpu is not None)
     if transition is None:
         transition = torch.full((S, S), uniform, dtype=torch.float32, device=device)
     obs = inputs.observation(observation, log_probs, device)
@@ -185,7 +186,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
             raise RuntimeError("route='band': a uniform transition matrix has no band")
         band = None
     else:
-        band = _counts_band(transition, original, B, T, S, device.index or 0, route)
+        band = _counts_band(transition, transition, B, T, S, device.index or 0, route)
     if band is not None:
         _, L, Xb, I = _run_band_counts(obs, frames, transition, initial, band[0], band[1], -math.inf)
         return band_counts_to_dense(Xb, band[0], band[1]), I, L
@@ -210,7 +211,7 @@ class _LogLikelihood(torch.autograd.Function):
             device = observation.device
             frames = inputs.frames(batch_frames, B, T, device)
             obs = observation.detach().to(dtype=torch.float32).contiguous()
-            trans = transition.detach().to(device=device, dtype=torch.float32).contiguous()
+            trans = inputs.plain_matrix(transition.detach().to(device))
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
             ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
             if ctx.band is not None:

@@ -27,6 +27,12 @@ def _require_gpu():
 def _check_inputs(observation, batch_frames, transition, initial):
     """`inputs.check_shapes` and the operator's dtypes (transition None: a uniform matrix)."""
     shape = inputs.check_shapes(observation, batch_frames, transition, initial)
+    check_dtypes(observation, batch_frames, transition, initial)
+    return shape
+
+
+def check_dtypes(observation, batch_frames, transition, initial):
+    """The operator's dtypes (None: not given, or not asked about)."""
     # dtype errors mirror what ATen's data_ptr<T>() raises in the reference operator
     # (torbi/csrc/cuda/viterbi.cu:203-215): fp32 scores, int32 lengths
     for name, tensor, dtype in (('observation', observation, torch.float32),
@@ -36,7 +42,6 @@ def _check_inputs(observation, batch_frames, transition, initial):
         if tensor is not None and tensor.dtype != dtype:
             raise RuntimeError(
                 f'expected scalar type {dtype} for {name} but found {tensor.dtype}')
-    return shape
 
 
 def workspace_bytes(batch: int, frames: int, states: int) -> int:
@@ -230,10 +235,20 @@ def _watch_resident(transition, workspace, batch, frames, states, seeds=3) -> No
         known[1] = (known[3], done, seeds)
 
 
+def _readable(trans: torch.Tensor, who: str) -> None:
+    """The look reads states * states float32 words, row-major, behind `trans.data_ptr()`: a tensor of another dtype or with
+    other strides is refused, on any device and before anything is asked of one, so that a front that forgets to prepare its
+    matrix (`inputs.plain_matrix`) fails here instead of reading a mirrored band, or memory that is not the tensor's."""
+    if trans.dtype != torch.float32 or not trans.is_contiguous():
+        raise RuntimeError(f'viterbi.{who} reads a contiguous float32 matrix; got {trans.dtype} with strides '
+                           f'{tuple(trans.stride())} (inputs.plain_matrix prepares one)')
+
+
 def band_reach(trans: torch.Tensor, original: torch.Tensor, states: int):
     """(reach_left, reach_right) of a transition matrix the band kernel could take -- transition[j][i] is -inf unless
     j - reach_left <= i <= j + reach_right (include/torbi_hip.h, torbi_hip_band_reach) -- else None.  One small kernel and
     a host sync the first time a tensor version is seen; kept with the tensor's notes (torbi_amd/state.py)."""
+    _readable(trans, 'band_reach')
     if states % 4 or not 64 <= states <= BAND_MAX_STATES or not trans.is_cuda or trans.data_ptr() % 16:
         return None
     found = _device_reach(trans, original, states)
@@ -247,6 +262,7 @@ def band_over(trans: torch.Tensor, original: torch.Tensor, states: int):
     torbi/core.py:341-347) --: `background` = the corner entry transition[0][S - 1], the reaches over every other value
     (include/torbi_hip.h, torbi_hip_band_reach_over); None where the band kernels could not take it.  A matrix that is -inf
     outside its band answers (reach_left, reach_right, -inf).  One small kernel and a host sync per tensor version."""
+    _readable(trans, 'band_over')
     if states % 4 or not 64 <= states <= BAND_MAX_STATES or not trans.is_cuda or trans.data_ptr() % 16:
         return None
     found = _device_look(trans, original, states)
@@ -370,6 +386,14 @@ def decode(
     frames = batch_frames.to(device).contiguous()
     trans = transition.to(device).contiguous()
     init = initial.to(device).contiguous()
+    # The forward kernels read observation rows and the initial row in 16-byte pieces where S % 4 == 0, and not every one of
+    # them is known to choose by the pointer (the band forms do, csrc/torbi_hip.hip decode_group; the matrix is chosen by
+    # the pointer, tests/test_gpu_parity.py): a view that starts off a 16-byte boundary -- `flat[1:]`, one element into its
+    # buffer -- is copied.
+    if obs.data_ptr() % 16:
+        obs = obs.clone()
+    if init.data_ptr() % 16:
+        init = init.clone()
 
     indices = torch.empty((B, T), dtype=torch.int32, device=device)
     if B == 0:

@@ -360,6 +360,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void *base, un
 #ifndef RESIDENT_HORIZON_SLACK
 #define RESIDENT_HORIZON_SLACK 2
 #endif
+// RESIDENT_MASK_CLOSED: the whole-tile form (not CLUSTER, not REPAIR, up to eight passes) walks the blocks behind a pass's
+// first evaluated test with the lanes of closed rows switched off.  A termination test finds a lane closed when the bound says that no later
+// entry can raise any of its four maxima (or the lane is past S); a lane quad -- the 16 items of one next-state (8-item
+// tiles: of two) -- is closed when all four lanes are, and its posterior reads, broadcasts, adds and maxima would be for
+// maxima that are already final.  Only whole quads are switched off (the quad broadcasts read all four lanes), the set of
+// open quads only shrinks within a pass, and everything outside an entry block's eight pairs -- loop control, list loads,
+// statistics, outputs -- runs on every lane as before.  The wave stays in lock step, so no instruction is saved: what goes
+// is the LDS traffic and the lane work of the closed quads (tools/scan_mask_sim.py: 12.7 % of a pass's posterior reads on the
+// benchmark's rows).  The open set is one SGPR pair, no vector register.  Results do not depend on it.
+#ifndef RESIDENT_MASK_CLOSED
+#define RESIDENT_MASK_CLOSED 1
+#endif
 
 // RESIDENT_PRIO: wave priorities of the whole-tile form (not CLUSTER, not REPAIR; 0 = none).  Co-resident waves of a SIMD
 // issue by priority, then age: with none set the oldest wave of a SIMD runs ahead, parks at the timestep's second barrier and
@@ -841,12 +853,43 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                         for (int r = 0; r < kR; ++r) best[it] = fmaxf(best[it], seedv[it][r] + seedt[it][r]);
                 };
                 const int first_test = RESIDENT_HORIZON ? horizon[p] : 1;
+                // RESIDENT_MASK_CLOSED: the lanes of the quads that still have an open pair (wave-uniform: an SGPR pair).
+                // Every lane until the pass's first evaluated test; from there on each test takes the closed quads out.
+                // INVARIANT: within a pass this set only shrinks (`best` only grows, the list's `tn` only falls, and the
+                // `&=` below holds it whatever the arithmetic does).  The read-ahead depends on it: a masked consume()
+                // requests pair 0 of the NEXT block under ITS mask, so the next block's mask must be a subset of it --
+                // a quad that came back would evaluate a pair it never read.  A closed lane's `ahead` is stale and its
+                // `best` final; neither is touched again before the epilogue reads `best`.
+                // (not with eleven passes, like RESIDENT_PRIO: with the extra code the compiler no longer unrolls that pass
+                // loop and pend[] goes to scratch)
+                constexpr bool kMask = RESIDENT_MASK_CLOSED && !CLUSTER && !REPAIR && MAXP <= 8 && !(RESIDENT_ABL & 1);
+                u64 open = ~0ull;
                 auto more = [&](const ListBlock<EPL> &blk) {
                     if (RESIDENT_ABL & 1) return nblk < 11;
                     if (RESIDENT_HORIZON && nblk < first_test) return true;
                     const float tn = group_bcast<G, 0>(blk.e[0].x);
-                    return (bool)__any(jv && ((tn + thr[0] > best[0]) | (tn + thr[1] > best[1]) | (tn + thr[2] > best[2]) |
-                                              (tn + thr[3] > best[3])));
+                    const bool mine = jv && ((tn + thr[0] > best[0]) | (tn + thr[1] > best[1]) | (tn + thr[2] > best[2]) |
+                                             (tn + thr[3] > best[3]));
+                    if constexpr (kMask) {
+                        u64 m = __ballot(mine);                 // bit = lane; a quad's four bits -> their OR, four times
+                        m |= m >> 1;
+                        m |= m >> 2;
+                        m &= 0x1111111111111111ull;
+                        m |= m << 1;
+                        m |= m << 2;
+                        open &= m;
+                        return open != 0ull;                    // (= __any(mine): `m` without the quads closed before)
+                    } else {
+                        return (bool)__any(mine);
+                    }
+                };
+                // a block behind a test: its eight pairs on the open quads only (EXEC = open; nothing else runs under it)
+                auto consume_open = [&](const ListBlock<EPL> &blk, const ListBlock<EPL> &after) {
+                    if constexpr (kMask) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(open)) consume(blk, after);
+                    } else {
+                        consume(blk, after);
+                    }
                 };
                 const int Sp = (S + 15) / 16 * 16;
                 fold_seeds();
@@ -855,12 +898,12 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     if (!more(nxt)) break;
                     RCOUNT(7, 1);
                     ++nblk;
-                    consume(nxt, cur);
+                    consume_open(nxt, cur);
                     load_list_block(nxt, row, kk + 2 * kBlk);
                     if (!more(cur)) break;
                     RCOUNT(7, 1);
                     ++nblk;
-                    consume(cur, nxt);
+                    consume_open(cur, nxt);
                     load_list_block(cur, row, kk + 3 * kBlk);
                 }
                 if ((t & 15) == 1) { stat_blocks += (unsigned)nblk; stat_passes += 1u; }

@@ -1,5 +1,5 @@
-"""The pruned scan's test horizon, one-slot test and top-list filter (csrc/resident_forward.hpp: RESIDENT_HORIZON,
-RESIDENT_SLOT_TEST, RESIDENT_TOP_FILTER) change which termination tests a wave pass evaluates and which outputs get a list
+"""The pruned scan's test horizon, one-slot test and top-list filter (csrc/resident_forward.hpp: horizon[],
+more(), last4[]) change which termination tests a wave pass evaluates and which outputs get a list
 key, never a result: on the smallest shapes at which a horizon taken from the previous timestep can go wrong, the decoded
 indices are the oracle's and the final posterior rows are, bit for bit, those of the dense route -- whole tiles and clusters."""
 import numpy as np

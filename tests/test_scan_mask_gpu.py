@@ -1,4 +1,4 @@
-"""The pruned scan's closed-row mask (csrc/resident_forward.hpp: RESIDENT_MASK_CLOSED) switches the lanes of rows whose
+"""The pruned scan's closed-row mask (csrc/resident_forward.hpp: kMask) switches the lanes of rows whose
 maxima are final off for the blocks behind a termination test, and changes no result: on the smallest shapes at which a mask
 can go wrong the decoded indices are the oracle's, the final posterior rows are, bit for bit, those of the dense route, and the
 launch reports the instance the shape has to run."""

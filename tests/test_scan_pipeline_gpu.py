@@ -1,6 +1,6 @@
-"""The pruned scan's read-ahead depth, early block-boundary requests and wave priorities (csrc/resident_forward.hpp:
-RESIDENT_DEPTH, RESIDENT_SPLIT_ADDS, RESIDENT_PRIO) change when a posterior read is requested and which wave issues first,
-never a result: on the smallest shapes that reach the places a deeper read-ahead can go wrong, the decoded indices are the
+"""The pruned scan's read-ahead, early block-boundary requests and wave priorities (csrc/resident_forward.hpp: consume(),
+prio_level()) change when a posterior read is requested and which wave issues first,
+never a result: on the smallest shapes that reach the places a read-ahead can go wrong, the decoded indices are the
 oracle's and the final posterior rows are, bit for bit, those of the dense route -- whole tiles, clusters and a launch group."""
 import numpy as np
 import pytest
@@ -27,7 +27,7 @@ def _build(name):
         B, T, S = 17, 8, 64
         obs, trans, init = synth.problem(B, T, S, seed=21)
         frames = np.full(B, T, np.int32)
-    elif name == 'not_a_multiple_of_16':                 # lanes past S and padding entries are two pairs ahead
+    elif name == 'not_a_multiple_of_16':                 # lanes past S and padding entries are read ahead
         B, T, S = 17, 8, 100
         obs, trans, init = synth.problem(B, T, S, seed=23)
         frames = np.full(B, T, np.int32)
@@ -130,7 +130,7 @@ def test_one_and_three_seed_instances_are_exact_at_the_depth_their_registers_gav
 
 def test_a_launch_group_of_unequal_batches_is_exact_with_waves_of_one_and_two_passes():
     """Three batches of unequal size in ONE whole-tile launch: 272 states are 17 row groups over twelve waves, so waves 0-4
-    make two passes per timestep and the others one -- the wave priorities (RESIDENT_PRIO) differ inside a workgroup."""
+    make two passes per timestep and the others one -- the wave priorities (prio_level) differ inside a workgroup."""
     S, T = 272, 12
     _, trans, init = synth.problem(1, 1, S, seed=33)
     trans = np.ascontiguousarray(trans, dtype=np.float32)

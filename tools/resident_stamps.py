@@ -50,7 +50,7 @@ for i, name in enumerate(names):
     print(f'{name:38s} {v:9.0f} ticks/step  {100 * v * steps / tot:5.1f} %')
 if PATH != 'cluster':
     # per wave of a workgroup (mean over workgroups): when it reaches barrier B (phases 0-4) and how long it waits there --
-    # the spread of finishing times RESIDENT_PRIO is meant to close
+    # the spread of finishing times the wave priorities (prio_level) are meant to close
     reach = acc[:, :, :5].sum(axis=2).mean(axis=0) / steps
     wait = acc[:, :, 5].mean(axis=0) / steps
     print('reaches barrier B, ticks into the timestep, waves 0-11:', ' '.join(f'{v:.0f}' for v in reach),

@@ -1,4 +1,4 @@
-"""CPU simulation of RESIDENT_MASK_CLOSED (csrc/resident_forward.hpp): how much of a wave pass's posterior reads belongs to
+"""CPU simulation of the pruned scan's closed-row mask (csrc/resident_forward.hpp, kMask): how much of a wave pass's posterior reads belongs to
 rows that are already closed.
 
 Built on scan_horizon_sim.pass_depths (the exact recurrence on one tile of 16 items; per wave pass -- 16 next-states x 16

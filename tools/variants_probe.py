@@ -1,6 +1,6 @@
 """Build variants of the library with extra -D flags here, time them on the GPU box.
 
-    python tools/variants_probe.py build NAME "-DTORBI_KR=2 ..."     # here: tools/libtorbi_hip_NAME.so
+    python tools/variants_probe.py build NAME "-DRESIDENT_ABL=1 ..." # here: tools/libtorbi_hip_NAME.so
     python tools/variants_probe.py run NAME [NAME ...]               # GPU box: tools/resident_probe.py per variant
                                                                      # ("base" = the in-tree library)
 """

@@ -32,18 +32,11 @@
 #include <stdint.h>
 #include <math.h>
 
-#ifndef HELD_FIRST_SLEEP
-#define HELD_FIRST_SLEEP 16     // x 64 cycles before the first poll of a timestep (tools/held_probe.py, 1 x 500 x 1440,
-                                // us per timestep: 0 -> 2.79, 8 -> 2.41, 12 -> 2.32, 16 -> 2.26, 20 -> 2.34, 32 -> 2.67)
-#endif
-#ifndef HELD_TWO_POINT
-#define HELD_TWO_POINT 1        // two sequences in flight: the next one's words are asked for after the folds (1) / the scan (0)
-#endif
-#ifndef HELD_POLL_SLEEP
-#define HELD_POLL_SLEEP 1       // x 64 cycles between polls
-#endif
-
 namespace held {
+
+constexpr int kFirstSleep = 16; // x 64 cycles before the first poll of a timestep (tools/held_probe.py, 1 x 500 x 1440,
+                                // us per timestep: 0 -> 2.79, 8 -> 2.41, 12 -> 2.32, 16 -> 2.26, 20 -> 2.34, 32 -> 2.67)
+constexpr int kPollSleep = 1;   // x 64 cycles between polls
 
 // Two shapes: up to 2048 states 8 next-states per workgroup of 512 threads (<= 256 workgroups, 4 prev-states per thread);
 // up to 4096 states 16 next-states per workgroup of 1024 threads (<= 256 workgroups, 4 prev-states per thread, 64 matrix
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(kThreads + (STORE_WAVE ? 64 : 0)) void held_forward
             // The next item's inputs can be asked for once its previous row has had time to become visible (~1 us after
             // that grid-wide store; asked for earlier, the poll fails and the next one waits behind it):
             //   three or more sequences in flight -- it was stored at least one item ago: ask at the top of this item;
-            //   two -- it was stored as this item began: ask after this item's scan / folds (HELD_TWO_POINT);
+            //   two -- it was stored as this item began: ask after this item's folds (not already after its scan);
             //   one -- the next item is this sequence again: sleep, then ask (below).
             // (Measured and dropped: a second poll in flight half a round trip behind the first -- 3.1 against 2.8 us
             // per timestep; the hand-off is paid in the consumer's own memory queue, every extra poll lengthens it.)
@@ -275,13 +268,13 @@ __global__ __launch_bounds__(kThreads + (STORE_WAVE ? 64 : 0)) void held_forward
             }
             if (!ok) {
                 const unsigned long long waiting_since = wall_clock64();     // (100 MHz, the same on every compute unit)
-                if (others == 0) __builtin_amdgcn_s_sleep(HELD_FIRST_SLEEP);
+                if (others == 0) __builtin_amdgcn_s_sleep(kFirstSleep);
                 for (;;) {
                     request(t, b, mine);
                     if (complete(mine, t)) break;
                     // (once given up, never wait again)
                     if (gave_up || wall_clock64() - waiting_since >= wait_ticks) { gave_up = true; break; }
-                    __builtin_amdgcn_s_sleep(HELD_POLL_SLEEP);
+                    __builtin_amdgcn_s_sleep(kPollSleep);
                 }
             }
             float p[K];
@@ -303,12 +296,6 @@ __global__ __launch_bounds__(kThreads + (STORE_WAVE ? 64 : 0)) void held_forward
                     a[r] = take ? tid + kThreads * k : a[r];
                 }
             }
-#if HELD_TWO_POINT == 0
-            if (prefetch && !requested) {
-                request(nt, nb, ahead);
-                requested = true;
-            }
-#endif
             // rows x 64 lanes -> one row per lane (halving folds), then over the lanes that share a row
             int row;
             bool keeper;
@@ -328,12 +315,10 @@ __global__ __launch_bounds__(kThreads + (STORE_WAVE ? 64 : 0)) void held_forward
                 row = ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
                 keeper = (lane & 3) == 0;
             }
-#if HELD_TWO_POINT == 1
             if (prefetch && !requested) {
                 request(nt, nb, ahead);
                 requested = true;
             }
-#endif
             const int slot = round & 1;
             if (keeper) {
                 sv[slot][wave][row] = v[0];

@@ -26,6 +26,7 @@
 #include "pruned_forward.hpp"
 #include "lazy_backtrace.hpp"
 #include "nonfinite.hpp"
+#include "group_order.hpp"      // kMaxBatches; the kernels that rank a launch group's items and tiles
 
 namespace resident {
 
@@ -39,13 +40,10 @@ using pruned::load_list_block;
 constexpr int kNI = 16;            // batch items per tile up to kMaxS16 states (4 item groups of 4 per next-state: a lane
                                    // quad, 16 next-states per wave pass); 8 above (2 lanes per next-state, 32 per pass):
                                    // the posterior tile [S][items] fp32 has to fit the 160 KB LDS
-constexpr int kMaxBatches = 16;    // batches one launch can carry
 constexpr int kRowGroup = 16;      // next-states per wave pass of the 16-item form
 // items per tile / next-states per wave pass for S states
-#ifndef TORBI_TILE16_MAX_S
-#define TORBI_TILE16_MAX_S pruned::kMaxS16      // (experiments: -DTORBI_TILE16_MAX_S=0 runs every shape on 8-item tiles)
-#endif
-__host__ __device__ inline int tile_items(int S) { return S <= TORBI_TILE16_MAX_S ? kNI : kNI / 2; }
+// (8-item tiles for every shape were no faster for a single batch: profiles/r03_single_batch_8_item_tiles.txt)
+__host__ __device__ inline int tile_items(int S) { return S <= pruned::kMaxS16 ? kNI : kNI / 2; }
 __host__ __device__ inline int pass_rows(int S) { return 64 / (tile_items(S) / 4); }
 
 typedef unsigned long long u64;
@@ -84,10 +82,7 @@ struct Group {
 // at kernel entry, and a cluster that finds itself on ONE XCD exchanges through that XCD's L2 -- plain stores that stay in
 // it, L1-bypassing loads that hit it -- instead of write-through stores and reads across the fabric (round 5; no faster
 // on the benchmark: profiles/r05_cluster_exchange.txt).
-#ifndef RESIDENT_MAX_R
-#define RESIDENT_MAX_R 16
-#endif
-constexpr int kMaxR = RESIDENT_MAX_R;    // members per cluster
+constexpr int kMaxR = 16;                // members per cluster
 constexpr int kMaxTop = 4;               // list entries per item a member publishes (>= KR + 1 of every instantiation)
 // The exchange is SELF-VALIDATING (round 5): a slot starts out as kAbsentBits in every word -- a NaN no fp32 addition of
 // the recurrence produces -- and a consumer takes a 16-byte piece of a posterior row when none of its four words is that
@@ -144,145 +139,6 @@ inline size_t lds_bytes(int S, int ktop = kTop) {
 // row groups (16 next-states) member m of R scans: [m * nrg / R, (m + 1) * nrg / R)
 __host__ __device__ inline int cluster_first_group(int m, int nrg, int R) { return (int)((long long)m * nrg / R); }
 
-// once per decode: order[rank] = item, items ranked by descending (clamped) length, ties by item number.  A tile of
-// 16 consecutive ranks then loops to the longest of 16 items of SIMILAR length -- a ragged batch costs recurrence
-// steps for its valid frames only (collate pads every item of a 512-batch to the batch maximum: reference
-// torbi/data/collate.py:24-31) -- and the longest tiles are dispatched first.  Results do not depend on the order.
-// grid = (ceil(max B / 256), batches), block = 256; O(B^2) compares up to kMaxOrdered items; larger batches are ranked by
-// a counting sort over the lengths (order_large_* below: items of equal length in arrival order of their atomics --
-// which of two equally long items lands in which tile changes nothing, neither results nor work).
-constexpr int kMaxOrdered = 8192;
-struct OrderJob { const int32_t *frames; int32_t *order; int B, T, tile0; int32_t *hist; int32_t *route_record; int route; };
-struct OrderJobs { OrderJob job[kMaxBatches]; int ascending; int n; int tiles; int32_t *tile_map; unsigned *stats;
-                   unsigned *flags; int nflags;         // cluster form: the flag / ticket words to zero (else nflags = 0)
-                   int ni; };                           // items per tile (16, or 8 above kMaxS16 states)
-
-// (The clamped lengths are staged in the LDS, kOrderChunk at a time, and every thread ranks its item against the chunk from
-// there, four lengths a read: a thread that read frames[o] from memory for every o took 35 us for 512 items.)
-constexpr int kOrderChunk = 2048;
-__global__ __launch_bounds__(256) void order_items_kernel(OrderJobs jobs) {
-    __shared__ __align__(16) int s_len[kOrderChunk];
-    const OrderJob &jb = jobs.job[blockIdx.y];
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    const int B = jb.B, T = jb.T;
-    if (b == 0 && jb.route_record) *jb.route_record = jb.route;      // the route this batch's decode takes (torbi_hip.hip)
-    if ((int)blockIdx.x * 256 >= B) return;          // (the whole block: nobody is missed at the barriers below)
-    if (B > kMaxOrdered) return;                     // order_large_* rank this batch
-    int f = b < B ? jb.frames[b] : 1;
-    f = f < 1 ? 1 : (f > T ? T : f);
-    int rank = 0;
-    for (int o0 = 0; o0 < B; o0 += kOrderChunk) {
-        const int n = min(kOrderChunk, B - o0), n4 = (n + 3) / 4 * 4;
-        if (o0) __syncthreads();
-        for (int o = threadIdx.x; o < n4; o += 256) {
-            int g = o < n ? jb.frames[o0 + o] : 0;   // (length 0 ranks behind every item: the chunk's padding counts nothing)
-            s_len[o] = o < n ? (g < 1 ? 1 : (g > T ? T : g)) : 0;
-        }
-        __syncthreads();
-        for (int o = 0; o < n4; o += 4) {
-            const int4 g = *reinterpret_cast<const int4 *>(&s_len[o]);
-            rank += (g.x > f) || (g.x == f && o0 + o < b);
-            rank += (g.y > f) || (g.y == f && o0 + o + 1 < b);
-            rank += (g.z > f) || (g.z == f && o0 + o + 2 < b);
-            rank += (g.w > f) || (g.w == f && o0 + o + 3 < b);
-        }
-    }
-    if (b < B) jb.order[jobs.ascending ? B - 1 - rank : rank] = b;
-}
-
-// Batches above kMaxOrdered items: hist[f] = items of (clamped) length f (zeroed by the host), turned into the first rank
-// of every length by one block, then every item takes the next rank of its length.
-__global__ __launch_bounds__(256) void order_large_count_kernel(OrderJob jb) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= jb.B) return;
-    int f = jb.frames[b];
-    f = f < 1 ? 1 : (f > jb.T ? jb.T : f);
-    atomicAdd(&jb.hist[f], 1);
-}
-
-__global__ __launch_bounds__(1024) void order_large_scan_kernel(OrderJob jb, int ascending) {
-    // hist[f] <- number of items that rank before the items of length f (longer ones; shorter ones when ascending)
-    __shared__ int part[1024];
-    const int T = jb.T, tid = threadIdx.x;
-    const int per = (T + 1024) / 1024;                       // lengths 1..T in 1024 contiguous chunks, in rank order
-    auto length_at = [&](int k) { return ascending ? 1 + k : T - k; };      // k-th length in rank order
-    int sum = 0;
-    for (int k = tid * per; k < (tid + 1) * per && k < T; ++k) sum += jb.hist[length_at(k)];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; }
-    }
-    __syncthreads();
-    int run = part[tid];
-    for (int k = tid * per; k < (tid + 1) * per && k < T; ++k) {
-        const int f = length_at(k), v = jb.hist[f];
-        jb.hist[f] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(256) void order_large_place_kernel(OrderJob jb) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= jb.B) return;
-    int f = jb.frames[b];
-    f = f < 1 ? 1 : (f > jb.T ? jb.T : f);
-    jb.order[atomicAdd(&jb.hist[f], 1)] = b;
-}
-
-// ... and the group's TILES by descending length of their longest item: workgroup w decodes tile_map[w].  The GPU hands
-// workgroup i to shader engine i mod 32 and waits, in launch order, for a free CU THERE (tools/dispatch_probe.hip,
-// tools/resident_wgtime.py): with batch-major numbering the rank-c tiles of all batches -- all of one length -- meet on
-// one engine, the engine of the longest tiles is the one the first workgroup beyond the 256th waits for, and nothing
-// behind it starts until those finish (measured: 28.3 ms for a ragged 16-batch group that has 16.5 ms of work per CU).
-// Ranked across the whole group, every engine holds an even spread of lengths and frees a CU early.
-// One thread per tile; grid = ceil(tiles / 256); O(tiles^2) compares.  Runs after order_items_kernel.
-// (Every tile's length is two dependent loads, frames[order[.]]: the block fetches them once, kOrderChunk tiles at a time,
-// into the LDS and ranks from there -- a thread that fetched all of them itself took 60 us for 256 tiles.)
-__global__ __launch_bounds__(256) void order_tiles_kernel(OrderJobs jobs) {
-    __shared__ __align__(16) int s_len[kOrderChunk];
-    const int w = blockIdx.x * 256 + threadIdx.x;
-    if (w < 128) jobs.stats[w] = 0u;                 // the forward launch that follows accumulates into them
-    for (int k = w; k < jobs.nflags; k += gridDim.x * 256) jobs.flags[k] = 0u;     // cluster flags and tickets start at zero
-    if ((int)blockIdx.x * 256 >= jobs.tiles) return;          // (the whole block)
-    auto batch_of_tile = [&](int v) {
-        int k = 0;
-        for (int q = 1; q < jobs.n; ++q)
-            if (v >= jobs.job[q].tile0) k = q;
-        return k;
-    };
-    auto tile_length = [&](int k, int j) {
-        const OrderJob &jb = jobs.job[k];
-        // the longest item of tile j: its first in descending order, its last (within the batch) in ascending order
-        const int last = jobs.ni * j + jobs.ni - 1 < jb.B ? jobs.ni * j + jobs.ni - 1 : jb.B - 1;
-        int f = jb.frames[jb.order[jobs.ascending ? last : jobs.ni * j]];
-        return f < 1 ? 1 : (f > jb.T ? jb.T : f);
-    };
-    const bool live = w < jobs.tiles;
-    const int k = live ? batch_of_tile(w) : 0;
-    const int j = w - jobs.job[k].tile0;
-    const int mine = live ? tile_length(k, j) : 1;
-    int rank = 0;
-    for (int v0 = 0; v0 < jobs.tiles; v0 += kOrderChunk) {
-        const int n = min(kOrderChunk, jobs.tiles - v0), n4 = (n + 3) / 4 * 4;
-        if (v0) __syncthreads();
-        for (int v = threadIdx.x; v < n4; v += 256) {
-            const int kv = v < n ? batch_of_tile(v0 + v) : 0;
-            s_len[v] = v < n ? tile_length(kv, v0 + v - jobs.job[kv].tile0) : 0;      // (0: behind every tile, counts nothing)
-        }
-        __syncthreads();
-        for (int v = 0; v < n4; v += 4) {
-            const int4 g = *reinterpret_cast<const int4 *>(&s_len[v]);
-            rank += (g.x > mine) || (g.x == mine && v0 + v < w);
-            rank += (g.y > mine) || (g.y == mine && v0 + v + 1 < w);
-            rank += (g.z > mine) || (g.z == mine && v0 + v + 2 < w);
-            rank += (g.w > mine) || (g.w == mine && v0 + v + 3 < w);
-        }
-    }
-    if (live) jobs.tile_map[jobs.ascending ? jobs.tiles - 1 - rank : rank] = (k << 20) | j;
-}
-
 // every word of the exchange slots a cluster launch will use := kAbsentBits (grid-stride, 16 bytes per thread and step)
 __global__ __launch_bounds__(256) void absent_kernel(uint4 *__restrict__ slots, size_t granules) {
     const uint4 a = {kAbsentBits, kAbsentBits, kAbsentBits, kAbsentBits};
@@ -332,35 +188,23 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void *base, un
 
 // build-time ablations for tools/variants_probe.py (timing only, results are wrong): bit 0 fixed scan depth of 11 blocks
 // (no termination test), 1 no posterior reads from the LDS, 2 no quad broadcasts, 3 no history stores, 4 no top-list
-// inserts, 5 no observation loads, 6 no seeds, 7 no exchange stores (cluster form).  RESIDENT_EXTRA_VALU=n adds n independent v_add_f32 per entry pair (results
-// unchanged): how much of the run time is the vector instruction stream
+// inserts, 5 no observation loads, 6 no seeds, 7 no exchange stores (cluster form).  (A probe that padded every entry pair
+// with independent v_add_f32 answered how much of the run time is the vector instruction stream: HISTORY.md 4.9.)
 #ifndef RESIDENT_ABL
 #define RESIDENT_ABL 0
 #endif
 // Cluster form: the pause (64-cycle units) between two attempts of a wave at slices that were not there yet
-#ifndef CLUSTER_POLL_SLEEP
-#define CLUSTER_POLL_SLEEP 4
-#endif
-#ifndef CLUSTER_ROUND
-#define CLUSTER_ROUND 8                // 16-byte pieces of the other members' slices a thread asks for at once
-#endif
-#ifndef RESIDENT_EXTRA_VALU
-#define RESIDENT_EXTRA_VALU 0
-#endif
-// RESIDENT_HORIZON: which of the termination tests -- all valid, one behind every block -- a wave pass evaluates.  A pass
-// walks max(1, n - RESIDENT_HORIZON_SLACK) blocks before its first test, n = the blocks the same row group's scan walked at
+constexpr int kClusterPollSleep = 4;
+constexpr int kClusterRound = 8;       // 16-byte pieces of the other members' slices a thread asks for at once
+// The test horizon: which of the termination tests -- all valid, one behind every block -- a wave pass evaluates.  A pass
+// walks max(1, n - kHorizonSlack) blocks before its first test, n = the blocks the same row group's scan walked at
 // the previous timestep (1 at t = 1), and tests behind every block from there on.  A row group's depth moves little from one
 // timestep to the next and no pass of the benchmark ends before block 9: the tests in front of the horizon decide nothing
 // (tools/scan_horizon_sim.py, profiles/scan_horizon_sim.txt: slack 2 walks 0.7 % more blocks and leaves 2.7 of 11.8 tests).
 // A scan that overshoots stops at its first test and lowers the next horizon by the slack.  Results do not depend on it:
 // examining more entries never changes a maximum, and a scan still stops only behind a test that says so.
-#ifndef RESIDENT_HORIZON
-#define RESIDENT_HORIZON 1
-#endif
-#ifndef RESIDENT_HORIZON_SLACK
-#define RESIDENT_HORIZON_SLACK 2
-#endif
-// RESIDENT_MASK_CLOSED: the whole-tile form (not CLUSTER, not REPAIR, up to eight passes) walks the blocks behind a pass's
+constexpr int kHorizonSlack = 2;
+// The closed-row mask (kMask in the kernel): the whole-tile form (not CLUSTER, not REPAIR, up to eight passes) walks the blocks behind a pass's
 // first evaluated test with the lanes of closed rows switched off.  A termination test finds a lane closed when the bound says that no later
 // entry can raise any of its four maxima (or the lane is past S); a lane quad -- the 16 items of one next-state (8-item
 // tiles: of two) -- is closed when all four lanes are, and its posterior reads, broadcasts, adds and maxima would be for
@@ -369,54 +213,24 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_of(const void *base, un
 // statistics, outputs -- runs on every lane as before.  The wave stays in lock step, so no instruction is saved: what goes
 // is the LDS traffic and the lane work of the closed quads (tools/scan_mask_sim.py: 12.7 % of a pass's posterior reads on the
 // benchmark's rows).  The open set is one SGPR pair, no vector register.  Results do not depend on it.
-#ifndef RESIDENT_MASK_CLOSED
-#define RESIDENT_MASK_CLOSED 1
-#endif
 
-// RESIDENT_PRIO: wave priorities of the whole-tile form (not CLUSTER, not REPAIR; 0 = none).  Co-resident waves of a SIMD
-// issue by priority, then age: with none set the oldest wave of a SIMD runs ahead, parks at the timestep's second barrier and
-// leaves the youngest to finish alone.  1: every pass sets the wave's priority from the passes it still has in this timestep
+// Wave priorities of the whole-tile form (not CLUSTER, not REPAIR).  Co-resident waves of a SIMD issue by priority, then
+// age: with none set the oldest wave of a SIMD runs ahead, parks at the timestep's second barrier and leaves the youngest
+// to finish alone.  Every pass sets the wave's priority from the passes it still has in this timestep
 // (>= 6 -> 3, 4-5 -> 2, 2-3 -> 1, <= 1 -> 0), so a wave that lags outranks one that leads and a wave with one pass more than
 // its neighbours is a level ahead of them at the same pass index; 0 from the last pass through the barriers and the
-// write-back.  2: priority 1 for the whole time loop for the waves with the larger pass count, 0 for the others.
-// RESIDENT_PRIO_CAP: the highest level of form 1 (the kernels of the other stream that run inside this launch stay at 0).
-#ifndef RESIDENT_PRIO
-#define RESIDENT_PRIO 1
-#endif
-#ifndef RESIDENT_PRIO_CAP
-#define RESIDENT_PRIO_CAP 3
-#endif
-__device__ __forceinline__ int prio_level(int left) {
-    const int level = left >= 6 ? 3 : left >= 4 ? 2 : left >= 2 ? 1 : 0;
-    return level < RESIDENT_PRIO_CAP ? level : RESIDENT_PRIO_CAP;
-}
-// RESIDENT_DEPTH: entry pairs of posterior reads (two ds_read_b128 each) a wave keeps requested ahead of the pair it
-// evaluates.  2: pairs h + 1 and h + 2, also across a block boundary -- the first TWO pairs of the next block are requested
-// before the termination test decides whether they are needed (that block is loaded, and its entries name rows of the tile,
-// padding included).  Eight more registers: only the instances scan_depth() names take it.
-#ifndef RESIDENT_DEPTH
-#define RESIDENT_DEPTH 1
-#endif
-// RESIDENT_SPLIT_ADDS: the eight adds of an entry pair go to eight temporaries before the four maxima read them (left to
-// itself the compiler funnels a pair's first four candidates through one register, every v_max3 behind its own add)
-#ifndef RESIDENT_SPLIT_ADDS
-#define RESIDENT_SPLIT_ADDS 0
-#endif
-// RESIDENT_RELOAD_ITEMS: the whole-tile instances of more than twelve waves do not hold their lanes' four item numbers in
-// registers: a pass reads them from the LDS (one ds_read_b128) where it forms its observation addresses and again where it
+// write-back (the kernels of the other stream that run inside this launch stay at 0).  A static form -- priority 1 for the
+// whole time loop for the waves with the larger pass count -- was no faster than none, and levels capped at 1 gained half
+// as much (profiles/scan_pipeline_ab.txt).
+__device__ __forceinline__ int prio_level(int left) { return left >= 6 ? 3 : left >= 4 ? 2 : left >= 2 ? 1 : 0; }
+// A wave keeps ONE entry pair of posterior reads (two ds_read_b128) requested ahead of the pair it evaluates.  Two pairs
+// ahead (+2.5 %, eight more registers) and the eight adds of a pair split into eight temporaries ahead of the four maxima
+// (+1 %) were slower: profiles/scan_pipeline_ab.txt, profiles/scan_pipeline_kernel_registers.txt.
+// Item numbers (kReloadItems in the kernel): the whole-tile instances of more than twelve waves do not hold their lanes'
+// four item numbers in registers: a pass reads them from the LDS (one ds_read_b128) where it forms its observation addresses and again where it
 // forms its history addresses.  With sixteen waves (four a SIMD) the one-seed instance then takes 111 registers instead of
 // the 128 its launch bound caps it at: 4 x 112 allocated leave 64 of a SIMD's 512 for the other stream's backtrace and
 // preparation kernels, which otherwise wait for the whole forward launch (HISTORY.md).
-#ifndef RESIDENT_RELOAD_ITEMS
-#define RESIDENT_RELOAD_ITEMS 1
-#endif
-// The instances whose register allocation takes the third pair in flight: at most 168 registers allocated and no more
-// scratch than at depth 1 (tools/kernel_registers.py, profiles/scan_pipeline_kernel_registers.txt).  One seed per item: all
-// but the 8-item form with eleven passes and the cluster form with six; three seeds: the one-pass cluster forms only.
-constexpr int scan_depth(int MAXP, int KR, bool CLUSTER, int NI) {
-    const bool fits = KR == 1 ? !(MAXP == 11 && NI == 8) && !(MAXP == 6 && CLUSTER) : MAXP == 1;
-    return RESIDENT_DEPTH >= 2 && fits ? 2 : 1;
-}
 
 #ifdef RESIDENT_STAMP
 // build-time instrumentation (tools/resident_stamps.py): per-wave cycle sums of the phases of a timestep
@@ -434,7 +248,8 @@ __device__ unsigned long long g_wgtime[1024 * 4];        // per workgroup: start
 // The whole forward pass of 16 items.  grid = tiles of every batch of the group, block = 64 * KW,
 // dynamic LDS = lds_bytes(S).  MAXP = ceil(ceil(S/16) / KW) row-group passes per wave and timestep.
 // ---------------------------------------------------------------------------------------
-// PIPE: the posterior reads of an entry pair are issued while the previous pair's adds/maxima run (two pairs of
+// PIPE (always true; the parameter stays because the printed instance names carry it): the posterior reads of an entry
+// pair are issued while the previous pair's adds/maxima run (two pairs of
 // ds_read_b128 in flight per wave, also across list blocks: the first pair of the next block is read before the
 // termination test decides whether it is needed) -- with one timestep per launch the scan was a third of the
 // kernel and this bought nothing (tools/prune_proto5.hip); here the scan IS the kernel.
@@ -449,6 +264,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     constexpr int kNI = NI, G = NI / 4, EPL = kBlk / G, kRowGroup = 64 / G;     // (shadow the namespace-wide 16-item values)
     constexpr int kR = KR, kTop = KR + 1;
     static_assert(NI == 16 || NI == 8, "tiles of 16 or 8 items");
+    static_assert(PIPE, "the scan is pipelined: there is no unpipelined body");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S4 = (S + 3) / 4 * 4;
     u64 *top = reinterpret_cast<u64 *>(lds + (size_t)kNI * S4);       // [16][kTop] this timestep's largest outputs
@@ -513,10 +329,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
             if (lane == 0) smisc[2] = same ? 1 : 0;
         }
         __syncthreads();
-#ifndef CLUSTER_LOCAL_EXCHANGE
-#define CLUSTER_LOCAL_EXCHANGE 1             // (0: write-through exchange whatever the placement -- experiments)
-#endif
-        local = CLUSTER_LOCAL_EXCHANGE && smisc[2] != 0;
+        local = smisc[2] != 0;
     }
     const int code = grp.tile_map[cid];
     const Batch &bat = grp.batch[code >> 20];
@@ -573,8 +386,8 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     const unsigned xbytes = (unsigned)cluster_slot_bytes(S);
     static_assert(kTop <= kMaxTop, "a member publishes at most kMaxTop list entries per item");
     // items of this lane: tile items 4g .. 4g+3; items past the batch read a valid one's observations and store nothing
-    // (RESIDENT_RELOAD_ITEMS: the instances of more than twelve waves read them from `sitem` pass by pass instead)
-    constexpr bool kReloadItems = RESIDENT_RELOAD_ITEMS && KW > 12 && !CLUSTER;
+    // (the whole-tile instances of more than twelve waves read them from `sitem` pass by pass instead)
+    constexpr bool kReloadItems = KW > 12 && !CLUSTER;
     int ib[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) ib[it] = sitem[4 * g + it];
@@ -602,13 +415,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     // A cluster member whose waves scan ONE row group per timestep (MAXP == 1) meets the same sorted rows every
     // timestep: their first two list blocks stay in registers, and the next timestep's observations are requested
     // before the wait for the other members (everything a pass needs that does not depend on the exchange).
-#ifndef RESIDENT_FIXED8
-#define RESIDENT_FIXED8 1
-#endif
-#ifndef RESIDENT_FIXED16
-#define RESIDENT_FIXED16 1
-#endif
-    constexpr bool FIXED = CLUSTER && MAXP == 1 && (NI == 16 ? RESIDENT_FIXED16 : RESIDENT_FIXED8);
+    constexpr bool FIXED = CLUSTER && MAXP == 1;
     ListBlock<EPL> head0, head1;
     float obnext[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (FIXED) {
@@ -626,7 +433,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     // scan statistics for adaptive path selection (every 16th timestep): how many 16-entry list blocks a wave pass
     // walks.  The benchmark needs 10.6 of the 90 a row holds; near 90 nothing is being pruned and the dense kernel wins.
     unsigned stat_blocks = 0, stat_passes = 0;
-    // RESIDENT_HORIZON: blocks each of this wave's passes walks before its first termination test (wave-uniform)
+    // the test horizon: blocks each of this wave's passes walks before its first termination test (wave-uniform)
     int horizon[MAXP];
 #pragma unroll
     for (int p = 0; p < MAXP; ++p) horizon[p] = 1;
@@ -655,13 +462,10 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     unsigned long long last = __builtin_readcyclecounter();
 #endif
 
-    // RESIDENT_PRIO: passes this wave makes per timestep (wave-uniform).  Not with eleven passes: the levels are made for
+    // wave priorities: passes this wave makes per timestep (wave-uniform).  Not with eleven passes: the levels are made for
     // eight, and with the extra code the eleven-pass loop is past what the compiler unrolls (pend[] would go to scratch)
-    constexpr int kPrio = (CLUSTER || REPAIR || MAXP > 8) ? 0 : RESIDENT_PRIO;
+    constexpr bool kPrio = !CLUSTER && !REPAIR && MAXP <= 8;
     const int npass = __builtin_amdgcn_readfirstlane(wave < nrg ? (nrg - wave + KW - 1) / KW : 0);
-    if constexpr (kPrio == 2) {
-        if (npass > nrg / KW) __builtin_amdgcn_s_setprio(1);
-    }
 
     for (int t = 1; t < fmax; ++t) {
         __syncthreads();      // tile = posterior row t-1, mtop = its largest entries, `top` is empty
@@ -701,7 +505,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         for (int p = 0; p < MAXP; ++p) {
             const int rg = rg_lo + wave + KW * p + opaque;  // wave-uniform
             if (rg < rg_hi) {
-                if constexpr (kPrio == 1) {
+                if constexpr (kPrio) {
                     const int left = npass - p;         // this pass included
                     const int level = prio_level(left);
                     if (p == 0 || level != prio_level(left + 1)) {
@@ -739,9 +543,6 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                         seedt[it][r] = (RESIDENT_ABL & 64) ? -1.0f : tt[(unsigned)(seedo[it][r] + jr)];   // trans[jr][i_r]
 
                 float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#if RESIDENT_EXTRA_VALU
-                float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-#endif
                 struct PairData { float4 p0, p1; float t0, t1; };
                 // entry pair H (0..7) of a block: owner lane O = H / 2 of the quad, its e[H % 2]
                 auto issue = [&](auto Hc, const ListBlock<EPL> &blk, PairData &d) {
@@ -766,83 +567,34 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     }
                 };
                 auto math = [&](const PairData &d) {
-#if RESIDENT_EXTRA_VALU
-                    // probe: extra independent full-rate adds per entry pair (is the vector ALU the limit?)
-#pragma unroll
-                    for (int x = 0; x < RESIDENT_EXTRA_VALU; ++x) asm volatile("v_add_f32 %0, %0, %1" : "+v"(dummy[x & 3]) : "v"(d.t0));
-#endif
-                    if (RESIDENT_SPLIT_ADDS) {
-                        float a0 = d.t0 + d.p0.x, a1 = d.t0 + d.p0.y, a2 = d.t0 + d.p0.z, a3 = d.t0 + d.p0.w;
-                        float b0 = d.t1 + d.p1.x, b1 = d.t1 + d.p1.y, b2 = d.t1 + d.p1.z, b3 = d.t1 + d.p1.w;
-                        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
-                        best[0] = fmaxf(fmaxf(best[0], a0), b0);
-                        best[1] = fmaxf(fmaxf(best[1], a1), b1);
-                        best[2] = fmaxf(fmaxf(best[2], a2), b2);
-                        best[3] = fmaxf(fmaxf(best[3], a3), b3);
-                        return;
-                    }
                     best[0] = fmaxf(fmaxf(best[0], d.t0 + d.p0.x), d.t1 + d.p1.x);
                     best[1] = fmaxf(fmaxf(best[1], d.t0 + d.p0.y), d.t1 + d.p1.y);
                     best[2] = fmaxf(fmaxf(best[2], d.t0 + d.p0.z), d.t1 + d.p1.z);
                     best[3] = fmaxf(fmaxf(best[3], d.t0 + d.p0.w), d.t1 + d.p1.w);
                 };
-                PairData ahead;            // PIPE: pair 0 of the block `consume` is about to be called on
-                PairData ahead1;           // ... and its pair 1 (depth 2)
-                constexpr int kDepth = PIPE ? scan_depth(MAXP, KR, CLUSTER, NI) : 1;
-                // all 8 pairs of `blk`; PIPE: pair 0 is already in `ahead`, and pair 0 of `after` is left there
-                // (depth 2: pairs 0 and 1, in `ahead` and `ahead1`)
+                PairData ahead;            // pair 0 of the block `consume` is about to be called on
+                // all 8 pairs of `blk`: pair 0 is already in `ahead`, and pair 0 of `after` is left there
                 auto consume = [&](const ListBlock<EPL> &blk, const ListBlock<EPL> &after) {
-                    if constexpr (kDepth == 2) {
-                        PairData fresh;
-#define TORBI_STAGE(H_, BLK_)                                                                  \
-                        issue(std::integral_constant<int, (H_ + 2) % 8>(), BLK_, fresh);       \
-                        __builtin_amdgcn_sched_barrier(0);                                     \
-                        math(ahead);                                                           \
-                        __builtin_amdgcn_sched_barrier(0);                                     \
-                        ahead = ahead1;                                                        \
-                        ahead1 = fresh;
-                        TORBI_STAGE(0, blk)
-                        TORBI_STAGE(1, blk)
-                        TORBI_STAGE(2, blk)
-                        TORBI_STAGE(3, blk)
-                        TORBI_STAGE(4, blk)
-                        TORBI_STAGE(5, blk)
-                        TORBI_STAGE(6, after)
-                        TORBI_STAGE(7, after)
+                    PairData other;
+#define TORBI_STAGE(H_, CUR_, NXT_)                                               \
+                    issue(std::integral_constant<int, H_ + 1>(), blk, NXT_);      \
+                    __builtin_amdgcn_sched_barrier(0);                            \
+                    math(CUR_);                                                   \
+                    __builtin_amdgcn_sched_barrier(0);
+                    TORBI_STAGE(0, ahead, other)
+                    TORBI_STAGE(1, other, ahead)
+                    TORBI_STAGE(2, ahead, other)
+                    TORBI_STAGE(3, other, ahead)
+                    TORBI_STAGE(4, ahead, other)
+                    TORBI_STAGE(5, other, ahead)
+                    TORBI_STAGE(6, ahead, other)
 #undef TORBI_STAGE
-                    } else if (PIPE) {
-                        PairData other;
-#define TORBI_STAGE(H_, CUR_, NXT_)                                                   \
-                        issue(std::integral_constant<int, H_ + 1>(), blk, NXT_);      \
-                        __builtin_amdgcn_sched_barrier(0);                            \
-                        math(CUR_);                                                   \
-                        __builtin_amdgcn_sched_barrier(0);
-                        TORBI_STAGE(0, ahead, other)
-                        TORBI_STAGE(1, other, ahead)
-                        TORBI_STAGE(2, ahead, other)
-                        TORBI_STAGE(3, other, ahead)
-                        TORBI_STAGE(4, ahead, other)
-                        TORBI_STAGE(5, other, ahead)
-                        TORBI_STAGE(6, ahead, other)
-#undef TORBI_STAGE
-                        issue(std::integral_constant<int, 0>(), after, ahead);
-                        __builtin_amdgcn_sched_barrier(0);
-                        math(other);
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else {
-                        PairData d;
-                        issue(std::integral_constant<int, 0>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 1>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 2>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 3>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 4>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 5>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 6>(), blk, d); math(d);
-                        issue(std::integral_constant<int, 7>(), blk, d); math(d);
-                    }
+                    issue(std::integral_constant<int, 0>(), after, ahead);
+                    __builtin_amdgcn_sched_barrier(0);
+                    math(other);
+                    __builtin_amdgcn_sched_barrier(0);
                 };
-                if (PIPE) issue(std::integral_constant<int, 0>(), cur, ahead);
-                if constexpr (kDepth == 2) issue(std::integral_constant<int, 1>(), cur, ahead1);
+                issue(std::integral_constant<int, 0>(), cur, ahead);
                 int nblk = 1;                              // wave-uniform
                 consume(cur, nxt);
                 load_list_block(cur, row, 2 * kBlk);
@@ -852,21 +604,21 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
 #pragma unroll
                         for (int r = 0; r < kR; ++r) best[it] = fmaxf(best[it], seedv[it][r] + seedt[it][r]);
                 };
-                const int first_test = RESIDENT_HORIZON ? horizon[p] : 1;
-                // RESIDENT_MASK_CLOSED: the lanes of the quads that still have an open pair (wave-uniform: an SGPR pair).
+                const int first_test = horizon[p];
+                // the closed-row mask: the lanes of the quads that still have an open pair (wave-uniform: an SGPR pair).
                 // Every lane until the pass's first evaluated test; from there on each test takes the closed quads out.
                 // INVARIANT: within a pass this set only shrinks (`best` only grows, the list's `tn` only falls, and the
                 // `&=` below holds it whatever the arithmetic does).  The read-ahead depends on it: a masked consume()
                 // requests pair 0 of the NEXT block under ITS mask, so the next block's mask must be a subset of it --
                 // a quad that came back would evaluate a pair it never read.  A closed lane's `ahead` is stale and its
                 // `best` final; neither is touched again before the epilogue reads `best`.
-                // (not with eleven passes, like RESIDENT_PRIO: with the extra code the compiler no longer unrolls that pass
-                // loop and pend[] goes to scratch)
-                constexpr bool kMask = RESIDENT_MASK_CLOSED && !CLUSTER && !REPAIR && MAXP <= 8 && !(RESIDENT_ABL & 1);
+                // (not with eleven passes, like the wave priorities: with the extra code the compiler no longer unrolls that
+                // pass loop and pend[] goes to scratch)
+                constexpr bool kMask = !CLUSTER && !REPAIR && MAXP <= 8 && !(RESIDENT_ABL & 1);
                 u64 open = ~0ull;
                 auto more = [&](const ListBlock<EPL> &blk) {
                     if (RESIDENT_ABL & 1) return nblk < 11;
-                    if (RESIDENT_HORIZON && nblk < first_test) return true;
+                    if (nblk < first_test) return true;
                     const float tn = group_bcast<G, 0>(blk.e[0].x);
                     const bool mine = jv && ((tn + thr[0] > best[0]) | (tn + thr[1] > best[1]) | (tn + thr[2] > best[2]) |
                                              (tn + thr[3] > best[3]));
@@ -907,8 +659,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     load_list_block(cur, row, kk + 3 * kBlk);
                 }
                 if ((t & 15) == 1) { stat_blocks += (unsigned)nblk; stat_passes += 1u; }
-                if (RESIDENT_HORIZON)
-                    horizon[p] = __builtin_amdgcn_readfirstlane(max(1, nblk - RESIDENT_HORIZON_SLACK));
+                horizon[p] = __builtin_amdgcn_readfirstlane(max(1, nblk - kHorizonSlack));
                 RSTAMP(3);
                 // the four items' list thresholds are read together (one LDS round trip, not four in a row)
                 u64 last4[4];
@@ -918,9 +669,6 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                 items_now(out);
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-#if RESIDENT_EXTRA_VALU
-                    if (dummy[it] == 12345.678f) best[it] = 0.f;
-#endif
                     const float o = ob[it] + best[it];                     // post'[j] = obs[t,j] + max
                     odd = odd || nonfinite::odd(o);
                     pend[p][it] = o;
@@ -1019,7 +767,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                     const bool keyed = want_keys;
                     v4u key0 = {0u, 0u, 0u, 0u}, key1 = {0u, 0u, 0u, 0u};
                     const int kat = (int)xrow + (km * kNI * kMaxTop + 2 * ks) * 16;
-                    constexpr int kRound = CLUSTER_ROUND;
+                    constexpr int kRound = kClusterRound;
                     unsigned spins = 0;
                     unsigned long long since = 0ull;
                     bool gave_up = false;
@@ -1050,7 +798,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                                 want_keys = false;
                             if (!__any(missing != 0u || want_keys)) break;
                             RCOUNT(9, 1);
-                            __builtin_amdgcn_s_sleep(CLUSTER_POLL_SLEEP);
+                            __builtin_amdgcn_s_sleep(kClusterPollSleep);
                             if ((spins++ & 15u) == 0u) {
                                 const unsigned long long now = wall_clock64();
                                 if (since == 0ull) since = now;
@@ -1082,7 +830,6 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         publish_top(t);
         RSTAMP(6);
     }
-    if constexpr (kPrio == 2) __builtin_amdgcn_s_setprio(0);
     if constexpr (CLUSTER) {
         if (tid == 0 && smisc[1]) {
             atomicAdd(&grp.stats[127], 1u);     // workgroups that gave up waiting (0 on any sane run)

@@ -1202,18 +1202,16 @@ hipError_t launch_resident_kernel(const resident::Group &grp, const resident::Cl
 // waves per workgroup of the whole-tile, one-seed, 16-item instance at 73 .. 96 row groups (1153 .. 1536 states).  Twelve
 // waves of eight passes hold 137 registers each, three to a SIMD; sixteen waves of six passes hold 111, FOUR to a SIMD, and
 // still leave 64 of its 512 registers to the other stream's backtrace and preparation (resident_forward.hpp,
-// RESIDENT_RELOAD_ITEMS): a launch group's forward pass 13.6 -> 13.1 ms at 8 x 512 x 200 x 1440 (HISTORY.md).  Taken where
+// kReloadItems): a launch group's forward pass 13.6 -> 13.1 ms at 8 x 512 x 200 x 1440 (HISTORY.md).  Taken where
 // the launch's tiles fill more than half the compute units -- the condition under which AUTO picks whole tiles; launches of
 // fewer tiles keep twelve waves.  Fifteen waves (up to 90 row groups: every wave six passes at 1440 states, three waves on
 // one SIMD) measured between the two and are reachable through the switch only.
 // TORBI_HIP_WHOLE_TILE_WAVES=12|15|16 names the instance whatever the tile count (read per launch: the tests switch it); a
 // count that does not cover the launch's row groups is ignored, as is any for three seeds or 8-item tiles.
-#ifndef TORBI_WHOLE_TILE_WAVES
-#define TORBI_WHOLE_TILE_WAVES 16
-#endif
 inline int whole_tile_waves(int nrg, int tiles, int cus) {
+    constexpr int kFullWaves = 16;                 // where the tiles fill more than half the compute units
     if (nrg <= 72 || nrg > 96) return 12;
-    int waves = 2 * tiles > cus ? TORBI_WHOLE_TILE_WAVES : 12;
+    int waves = 2 * tiles > cus ? kFullWaves : 12;
     if (const char *e = getenv("TORBI_HIP_WHOLE_TILE_WAVES")) {
         const int asked = atoi(e);
         if (asked == 12 || asked == 15 || asked == 16) waves = asked;

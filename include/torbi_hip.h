@@ -835,6 +835,43 @@ int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames,
                           float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int N, int device,
                           void *stream);
 
+/*
+ * Max-marginals (added within ABI 17): the largest log score of any complete path of item b that is in state j at frame t,
+ * on the model torbi_hip_viterbi_decode decodes (torbi_amd/margins.py, MARGINALS.md).  Inputs as there: observation
+ * (B, T, S) log scores, batch_frames (B,) int32 (F: clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.
+ * All sums in float32 with one rounding each:
+ *     alpha_0[j] = fl(obs_0[j] + initial[j])
+ *     alpha_t[j] = fl(obs_t[j] + max_i fl(alpha_{t-1}[i] + transition[j][i]))                1 <= t < F
+ *     beta_{F-1}[i] = +0
+ *     beta_t[i]  = max_j fl(transition[j][i] + fl(obs_{t+1}[j] + beta_{t+1}[j]))             0 <= t < F-1
+ *     m_t[j]     = fl(alpha_t[j] + beta_t[j])   for t < F,   -inf   for F <= t < T
+ *     score      = max_j alpha_{F-1}[j]
+ * marginals_out (B, T, S) fp32: m; scores_out (B,) fp32: the score, the bits of rank 0 of torbi_hip_k_best.  A maximum of
+ * floats without NaN does not depend on its order, so the values are defined exactly; only the sign of a zero is not
+ * (m_{F-1} is stored as alpha_{F-1}).  -inf is an ordinary value: a state no path reaches or leaves has m = -inf, not NaN.
+ * A NaN or +inf in anything an item reads (initial, the matrix when F_b >= 2, its observation rows t < F_b) gives that item
+ * NaN in every m_t, t < F_b, and a NaN score; its rows t >= F_b stay -inf.  An item's values never depend on other items'
+ * data.  Sums of finite inputs that overflow float32 are outside this contract.
+ *
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_max_marginals_workspace_size(B, T, S, uniform)
+ * bytes: with uniform == 0 the matrix transposed, two beta rows per item and B + 1 alarm words; else three scalars per item
+ * and frame and the alarm words.  It holds no (B, T, S) region: alpha is kept in marginals_out.  The size query answers 256
+ * for dimensions below 1 or S > 16384.
+ * The general route takes one launch per frame and pass (2 (T - 1) step launches), the uniform route three launches; no
+ * allocation and no host synchronisation: a call can be captured into a graph.
+ * The uniform entry point takes a matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))) and returns the
+ * values of torbi_hip_max_marginals on that matrix.
+ * TORBI_HIP_EINVAL for a null pointer, B < 0, T < 1 or S < 1; TORBI_HIP_ERANGE for S > 16384, B * T > 2^32 or
+ * B * T * S > 2^40; TORBI_HIP_EWORKSPACE for a workspace that is too small.  B == 0 returns 0.
+ */
+size_t torbi_hip_max_marginals_workspace_size(int B, int T, int S, int uniform);
+int torbi_hip_max_marginals(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                            float *marginals_out, float *scores_out, void *workspace, size_t workspace_bytes, int B, int T,
+                            int S, int device, void *stream);
+int torbi_hip_max_marginals_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                    const float *initial, float *marginals_out, float *scores_out, void *workspace,
+                                    size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,13 @@ SYMBOLS = {
     'torbi_hip_sample_band': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p,
         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_max_marginals_workspace_size': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_max_marginals': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_max_marginals_uniform': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
 }
 
 MAX_BATCHES = 16        # TORBI_HIP_MAX_BATCHES

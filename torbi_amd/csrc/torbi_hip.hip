@@ -51,6 +51,7 @@
 #include "k_best_band.hpp"
 #include "sample.hpp"
 #include "sample_band.hpp"
+#include "max_marginals.hpp"
 
 namespace {
 
@@ -3230,6 +3231,95 @@ int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames,
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(kb::kb_walk_kernel<false>, dim3(B), dim3(64), 0, st, batch_frames, l.ptrs, l.final_, l.count, l.flag,
                        indices_out, scores_out, T, S, k);
+    return (int)hipGetLastError();
+}
+
+// ---- max-marginals: the best path score through every frame and state (max_marginals.hpp) ----
+
+size_t torbi_hip_max_marginals_workspace_size(int B, int T, int S, int uniform) {
+    if (B < 1 || T < 1 || S < 1 || S > mm::kMaxStates) return 256;
+    return mm::layout(nullptr, B, T, S, uniform != 0).total;
+}
+
+static int mm_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *marginals,
+                      const void *scores, const void *ws, size_t ws_bytes, int B, int T, int S, int uniform) {
+    if (B < 0 || T < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!obs || !frames || !matrix || !initial || !marginals || !scores || !ws) return TORBI_HIP_EINVAL;
+    if (S > mm::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (size_t)B * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
+    if (ws_bytes < torbi_hip_max_marginals_workspace_size(B, T, S, uniform)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+int torbi_hip_max_marginals(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                            float *marginals_out, float *scores_out, void *workspace, size_t workspace_bytes, int B, int T,
+                            int S, int device, void *stream) {
+    const int rc = mm_args_ok(observation, batch_frames, transition, initial, marginals_out, scores_out, workspace,
+                              workspace_bytes, B, T, S, 0);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const mm::Layout l = mm::layout(fb_base(workspace), B, T, S, false);
+    hipError_t e;
+    if ((e = hipMemsetAsync(l.alarm, 0, ((size_t)B + 1) * sizeof(int32_t), st)) != hipSuccess) return (int)e;
+    if (T > 1) {
+        hipLaunchKernelGGL(mm::mm_prepare_kernel, dim3((S + 31) / 32, (S + 31) / 32), dim3(256), 0, st, transition, l.at,
+                           l.alarm + B, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(mm::mm_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, marginals_out,
+                       l.alarm, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const dim3 grid((B + mm::kItemTile - 1) / mm::kItemTile, (S + mm::kRowTile - 1) / mm::kRowTile);
+    const int groups = mm::step_groups((long)grid.x * grid.y);
+    auto step = [&](auto backward, const float *panel, int t) {
+        by_value<1, 2, 4>(groups, [&](auto kg) {
+            auto *kernel = &mm::mm_step_kernel<decltype(backward)::value, decltype(kg)::value>;
+            hipLaunchKernelGGL(kernel, grid, dim3(mm::kThreads * decltype(kg)::value), 0, st, observation, batch_frames, panel,
+                               marginals_out, l.beta, l.alarm, t, B, T, S);
+        });
+        return hipGetLastError();
+    };
+    for (int t = 1; t < T; ++t)
+        if ((e = step(std::false_type(), l.at, t)) != hipSuccess) return (int)e;
+    for (int t = T - 2; t >= 0; --t)
+        if ((e = step(std::true_type(), transition, t)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mm::mm_final_kernel, dim3(B), dim3(256), 0, st, batch_frames, l.alarm, marginals_out, scores_out, B, T, S);
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_max_marginals_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                    const float *initial, float *marginals_out, float *scores_out, void *workspace,
+                                    size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = mm_args_ok(observation, batch_frames, initial /* (no matrix) */, initial, marginals_out, scores_out,
+                              workspace, workspace_bytes, B, T, S, 1);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const mm::Layout l = mm::layout(fb_base(workspace), B, T, S, true);
+    hipError_t e;
+    if ((e = hipMemsetAsync(l.alarm, 0, ((size_t)B + 1) * sizeof(int32_t), st)) != hipSuccess) return (int)e;
+    const size_t rows = (size_t)B * T;
+    const bool vec = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(observation) | reinterpret_cast<uintptr_t>(marginals_out) |
+                                     reinterpret_cast<uintptr_t>(initial)) & 15) == 0;
+    by_flag(vec, [&](auto vec_) {
+        auto *kernel = &mm::mm_uniform_rows_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames, initial, l.rows,
+                           l.alarm, B, T, S);
+    });
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mm::mm_uniform_scan_kernel, dim3((B + 63) / 64), dim3(64), 0, st, batch_frames, l.rows, l.c, l.ubeta,
+                       l.alarm, scores_out, uniform_value, !(uniform_value < INFINITY) ? 1 : 0, B, T);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const size_t passes = (rows * S / (vec ? 4 : 1) + 255) / 256;
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>(passes, 1), (size_t)cu_count(device) * 32);
+    by_flag(vec, [&](auto vec_) {
+        auto *kernel = &mm::mm_uniform_write_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, observation, batch_frames, initial, l.c, l.ubeta, l.alarm,
+                           marginals_out, B, T, S);
+    });
     return (int)hipGetLastError();
 }
 

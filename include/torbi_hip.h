@@ -872,6 +872,33 @@ int torbi_hip_max_marginals_uniform(const float *observation, const int32_t *bat
                                     const float *initial, float *marginals_out, float *scores_out, void *workspace,
                                     size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
+/*
+ * Max-marginals on a band (added within ABI 17): the values of torbi_hip_max_marginals, by ==, for a matrix that holds ONE
+ * value outside a band, at the cost of the band (MARGINALS.md, "Band route").  The caller states the band --
+ * transition[j][i] with j - reach_left <= i <= j + reach_right -- and promises that every entry outside it equals
+ * `background` bit for bit.  Rounding is monotone, so the out-of-band candidates of a state are one sum,
+ * fl(max over the out-of-band states + background), taken from a prefix and a suffix maximum of the previous row.
+ * The promise is checked on the device without waiting for it: where it is broken, every item, whatever its frames, gets NaN
+ * in its rows t < F_b and a NaN score.  The non-finite rule is torbi_hip_max_marginals's.
+ *
+ * torbi_hip_max_marginals_band_covers reads no device and answers 1 for B >= 1, T >= 1, S % 4 == 0, 64 <= S <= 3072,
+ * reaches >= 0 with reach_left + reach_right + 4 <= 512, a background that is neither NaN nor +inf, and one item's rows
+ * fitting the LDS.
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_max_marginals_band_workspace_size bytes: the
+ * diagonals [reach_left + reach_right + 1][S], B + 1 alarm words and the verdict word; no (B, T, S) region and no beta rows.
+ * The size query answers 256 for dimensions below 1, S > 16384, a negative reach or a window above 512.
+ * Four launches whatever T (verdict, prepare, every frame of both passes, final); no allocation, no host synchronisation.
+ * TORBI_HIP_EINVAL for a null pointer, a negative reach, B < 0, T < 1 or S < 1; TORBI_HIP_ERANGE as torbi_hip_max_marginals;
+ * TORBI_HIP_EUNSUPPORTED where _covers answers 0; TORBI_HIP_EWORKSPACE for a workspace that is too small.  B == 0 returns 0.
+ * All are answered before a device is touched.
+ */
+int torbi_hip_max_marginals_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_max_marginals_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_max_marginals_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                 const float *initial, int reach_left, int reach_right, float background, float *marginals_out,
+                                 float *scores_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int device,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,11 @@ and the yardsticks, in the same process on the same inputs:
     temporary holds at most 2^28 values; its values are compared with the HIP route's
   * the every-cell dense decode (torbi_amd.decode(..., path='dense')) of the same shape: twice its time is the cost of the
     same cell count, 2 B (T - 1) S^2, in the project's most tuned kernel
+
+With --band, the band rows alone: margins.forward_backward_max_banded against the dense route on the same inputs in the same
+process, for the pitch band of --half-widths (12: 23 diagonals, 88: 175) in both forms of its background (-inf and
+log(tiny)) at every batch of --batches, by the same method; the band route moves 20 B T S bytes (the observation read twice,
+the marginals written, read and written again).
 """
 import argparse
 import json
@@ -77,8 +82,45 @@ def torch_max_marginals(obs, trans, init):
     return m, score
 
 
+def band_rows(T, S, repeats, batches, half_widths):
+    """The band route (margins.forward_backward_max_banded) against the dense route on the same inputs in the same process:
+    the pitch band of `half_width` (2 * half_width - 1 diagonals) in both forms of its background, -inf and log(tiny), at
+    every batch of `batches`.  `wins`: the dense median exceeds the band median by more than the dense route's own spread
+    (max - min); `equal`: the two routes' values agree by == with equal NaN positions."""
+    dev = torch.device('cuda:0')
+    rows = []
+    for B in batches:
+        obs, _, init = (torch.from_numpy(x).to(dev) for x in synth.problem(B, T, S, seed=1))
+        frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+        dense_ws = torch.empty(margins.max_marginals_workspace_bytes(B, T, S), dtype=torch.uint8, device=dev)
+        for half_width in half_widths:
+            reach = half_width - 1
+            band_ws = torch.empty(margins.max_marginals_banded_workspace_bytes(B, T, S, reach, reach), dtype=torch.uint8, device=dev)
+            for tiny in (False, True):
+                matrix = synth.banded_transition(S, half_width, tiny=tiny)
+                background = float(matrix[0, S - 1])
+                trans = torch.from_numpy(matrix).to(dev)
+                dense = timed(lambda: margins.forward_backward_max(obs, frames, trans, init, workspace=dense_ws), repeats)
+                band = timed(lambda: margins.forward_backward_max_banded(obs, frames, trans, init, reach, reach, background,
+                                                                         workspace=band_ws), repeats)
+                want = margins.forward_backward_max(obs, frames, trans, init, workspace=dense_ws)
+                got = margins.forward_backward_max_banded(obs, frames, trans, init, reach, reach, background, workspace=band_ws)
+                equal = all(bool(((g == w) | (torch.isnan(g) & torch.isnan(w))).all()) for g, w in zip(got, want))
+                nan = int(torch.isnan(got[0]).sum())
+                del want, got
+                rows.append({'batch': B, 'diagonals': 2 * reach + 1, 'background': background, 'dense_ms': dense, 'band_ms': band,
+                             'speedup': dense['median'] / band['median'], 'equal': equal, 'nan_values': nan,
+                             'wins': dense['median'] - band['median'] > dense['max'] - dense['min'],
+                             'band_workspace_bytes': band_ws.numel(),
+                             'band_gbps_of_20_B_T_S': 20.0 * B * T * S / band['median'] / 1e6})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--band', action='store_true', help='the band rows alone (MARGINALS.md, "Band route")')
+    ap.add_argument('--batches', type=int, nargs='+', default=[1, 8, 512])
+    ap.add_argument('--half-widths', type=int, nargs='+', default=[12, 88])
     ap.add_argument('--B', type=int, default=512)
     ap.add_argument('--T', type=int, default=500)
     ap.add_argument('--S', type=int, default=1440)
@@ -87,6 +129,10 @@ def main():
     ap.add_argument('--skip-torch', action='store_true')
     args = ap.parse_args()
     B, T, S = args.B, args.T, args.S
+    if args.band:
+        print(json.dumps({'device': torch.cuda.get_device_name(0), 'frames_states': [T, S], 'repeats': args.repeats,
+                          'band_rows': band_rows(T, S, args.repeats, args.batches, args.half_widths)}))
+        return
     dev = torch.device('cuda:0')
     obs, trans, init = (torch.from_numpy(x).to(dev) for x in synth.problem(B, T, S, seed=1))
     frames = torch.full((B,), T, dtype=torch.int32, device=dev)

@@ -52,6 +52,7 @@
 #include "sample.hpp"
 #include "sample_band.hpp"
 #include "max_marginals.hpp"
+#include "max_marginals_band.hpp"
 
 namespace {
 
@@ -3320,6 +3321,70 @@ int torbi_hip_max_marginals_uniform(const float *observation, const int32_t *bat
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, observation, batch_frames, initial, l.c, l.ubeta, l.alarm,
                            marginals_out, B, T, S);
     });
+    return (int)hipGetLastError();
+}
+
+// ---- max-marginals on a band with one constant outside it (max_marginals_band.hpp) ----
+
+int torbi_hip_max_marginals_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device) {
+    (void)device;
+    if (B < 1 || T < 1 || reach_left < 0 || reach_right < 0) return 0;
+    if (S % 4 != 0 || S < mmb::kMinStates || S > mmb::kMaxStates || (long long)reach_left + reach_right + 4 > mmb::kMaxWindow)
+        return 0;
+    if (mmb::lds_bytes(1, S, reach_left, reach_right) > (size_t)mmb::kMaxLdsBytes) return 0;
+    return background_ok(background) ? 1 : 0;
+}
+
+size_t torbi_hip_max_marginals_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > mm::kMaxStates || reach_left < 0 || reach_right < 0 ||
+        (long long)reach_left + reach_right + 4 > mmb::kMaxWindow)
+        return 256;
+    return mmb::layout(nullptr, B, S, reach_left, reach_right).total;
+}
+
+// Items per workgroup of mmb_kernel<G>: from mmb::kMaxGroup, halved while the rows and scans of G items do not fit the LDS,
+// then while the launch has fewer than mmb::kWorkgroups workgroups.  The rule reads the shape and the band only.
+static int mm_band_items(int B, int S, int reach_left, int reach_right) {
+    return items_per_workgroup(mmb::kMaxGroup, B, 1, mmb::kWorkgroups, [&](int g) {
+        return mmb::lds_bytes(g, S, reach_left, reach_right) <= (size_t)mmb::kMaxLdsBytes;
+    });
+}
+
+int torbi_hip_max_marginals_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                 const float *initial, int reach_left, int reach_right, float background, float *marginals_out,
+                                 float *scores_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int device,
+                                 void *stream) {
+    if (B < 0 || T < 1 || S < 1 || reach_left < 0 || reach_right < 0) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !marginals_out || !scores_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (S > mm::kMaxStates || (size_t)B * T * S > (size_t)1 << 40 || (size_t)B * T > (size_t)1 << 32) return TORBI_HIP_ERANGE;
+    if (!torbi_hip_max_marginals_band_covers(B, T, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
+    if (workspace_bytes < torbi_hip_max_marginals_band_workspace_size(B, T, S, reach_left, reach_right)) return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const mmb::Layout l = mmb::layout(fb_base(workspace), B, S, reach_left, reach_right);
+    hipError_t e;
+    if ((e = hipMemsetAsync(l.alarm, 0, ((size_t)B + 1) * sizeof(int32_t), st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mmb::mmb_verdict_kernel, dim3(1), dim3(1), 0, st, l.ok);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mmb::mmb_prepare_kernel, dim3(S), dim3(mmb::kPrepareThreads), 0, st, transition, l.diag, l.ok, l.alarm + B,
+                       background, reach_left, reach_right, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int G = mm_band_items(B, S, reach_left, reach_right);
+    const size_t lds = mmb::lds_bytes(G, S, reach_left, reach_right);
+    e = by_flag(background != -INFINITY, [&](auto scan) { return by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &mmb::mmb_kernel<decltype(g)::value, decltype(scan)::value>;
+        const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+        if (granted != hipSuccess) return granted;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(mmb::kThreads), lds, st, observation, batch_frames, l.diag, initial,
+                           background, reach_left, reach_right, marginals_out, scores_out, l.alarm, B, T, S);
+        return hipGetLastError();
+    }); });
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mmb::mmb_final_kernel, dim3(B), dim3(256), 0, st, batch_frames, l.alarm, l.ok, marginals_out, scores_out,
+                       B, T, S);
     return (int)hipGetLastError();
 }
 

@@ -899,6 +899,46 @@ int torbi_hip_max_marginals_band(const float *observation, const int32_t *batch_
                                  float *scores_out, void *workspace, size_t workspace_bytes, int B, int T, int S, int device,
                                  void *stream);
 
+/*
+ * Path statistics (added within ABI 17): the exact log score and the transition counts of GIVEN state paths, on the model
+ * torbi_hip_viterbi_decode decodes (torbi_amd/paths.py, PATHS.md).  indices (B, K, T) int32: K paths per item; inputs
+ * otherwise as torbi_hip_max_marginals (F: batch_frames clamped to [1, T]; transition [next][prev]).  A path q of item b is
+ * scored by the decoder's alpha recurrence followed along it, all sums in float32 with one rounding each:
+ *     s_0   = fl(obs_0[q_0] + initial[q_0])
+ *     s_t   = fl(obs_t[q_t] + fl(s_{t-1} + transition[q_t][q_{t-1}]))                         1 <= t < F
+ *     score = s_{F-1}
+ * so the score of a path torbi_hip_k_best returns at any rank is that rank's score bit for bit.  The score reads the cells on
+ * the path and no others: a NaN, +inf or -inf on the path propagates by plain IEEE arithmetic, one elsewhere in the item
+ * does not matter, and there is no item-level non-finite rule.  Columns t >= F are never read.
+ * A path that holds an index outside [0, S) at a column t < F is VOID (the -1 ranks of torbi_hip_k_best, the -1 rows of
+ * torbi_hip_sample): its score is -inf and it adds nothing to any count.
+ * Counts, with path_weights w (B, K) fp32 (NULL: all ones), in the orientation of torbi_hip_forward_backward_counts:
+ *     transition_counts_out[j][i] = sum over b, k of w[b][k] * #{1 <= t < F : q_t = j, q_{t-1} = i}          (S, S) fp32
+ *     initial_counts_out[j]       = sum over b, k of w[b][k] * [q_0 = j]                                     (S,)   fp32
+ * accumulated in float64 (the weights converted exactly, hardware float64 atomics) and rounded to float32 once: unweighted
+ * counts, and counts under weights that are small multiples of a power of two, are exact whatever the order of the adds;
+ * with general non-negative weights the result is within one float32 ulp of the exact sum.
+ *
+ * transition == NULL: the matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))).
+ * scores_out == NULL: counts only; then observation, transition and initial may be NULL (nothing of the model is read).
+ * transition_counts_out == NULL and initial_counts_out == NULL (both): scores only; then the workspace size is 0 and a NULL
+ * workspace is accepted.
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_path_statistics_workspace_size(B, T, S, K,
+ * counts) bytes: the S * S + S float64 accumulators, which the call zeroes itself on the stream; 0 with counts == 0, 256
+ * for dimensions below 1 or S > 16384.
+ * One launch for every path (one wavefront per path), plus with counts one memset before and one rounding launch behind it;
+ * no allocation and no host synchronisation: a call can be captured into a graph, and the graph is linear.
+ * TORBI_HIP_EINVAL for any other null pointer (one count output without the other, no output at all, a missing workspace
+ * with counts), B < 0, T < 1, S < 1 or K < 1; TORBI_HIP_ERANGE for S > 16384, B * K > 2^31 - 4, B * K * T > 2^40 or
+ * B * T * S > 2^40; TORBI_HIP_EWORKSPACE for a workspace that is too small.  All are answered before anything is launched.
+ * B == 0 launches nothing and returns 0.
+ */
+size_t torbi_hip_path_statistics_workspace_size(int B, int T, int S, int K, int counts);
+int torbi_hip_path_statistics(const float *observation, const int32_t *batch_frames, const float *transition, float uniform_value,
+                              const float *initial, const int32_t *indices, const float *path_weights, float *scores_out,
+                              float *transition_counts_out, float *initial_counts_out, void *workspace, size_t workspace_bytes,
+                              int B, int T, int S, int K, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,7 @@
 #include "sample_band.hpp"
 #include "max_marginals.hpp"
 #include "max_marginals_band.hpp"
+#include "path_statistics.hpp"
 
 namespace {
 
@@ -3385,6 +3386,45 @@ int torbi_hip_max_marginals_band(const float *observation, const int32_t *batch_
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mmb::mmb_final_kernel, dim3(B), dim3(256), 0, st, batch_frames, l.alarm, l.ok, marginals_out, scores_out,
                        B, T, S);
+    return (int)hipGetLastError();
+}
+
+// ---- path statistics: exact scores and counts of given state paths (path_statistics.hpp) ----
+
+size_t torbi_hip_path_statistics_workspace_size(int B, int T, int S, int K, int counts) {
+    if (!counts) return 0;
+    if (B < 1 || T < 1 || S < 1 || K < 1 || S > ps::kMaxStates) return 256;
+    return ps::layout(nullptr, S, true).total;
+}
+
+int torbi_hip_path_statistics(const float *observation, const int32_t *batch_frames, const float *transition, float uniform_value,
+                              const float *initial, const int32_t *indices, const float *path_weights, float *scores_out,
+                              float *transition_counts_out, float *initial_counts_out, void *workspace, size_t workspace_bytes,
+                              int B, int T, int S, int K, int device, void *stream) {
+    if (B < 0 || T < 1 || S < 1 || K < 1) return TORBI_HIP_EINVAL;
+    const bool counting = transition_counts_out != nullptr;
+    if (counting != (initial_counts_out != nullptr) || (!counting && !scores_out)) return TORBI_HIP_EINVAL;
+    if (!batch_frames || !indices || (scores_out && (!observation || !initial)) || (counting && !workspace))
+        return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    const size_t paths = (size_t)B * K;
+    if (S > ps::kMaxStates || paths > ((size_t)1 << 31) - ps::kWaves || paths * T > (size_t)1 << 40 ||
+        (size_t)B * T * S > (size_t)1 << 40)
+        return TORBI_HIP_ERANGE;
+    if (workspace_bytes < torbi_hip_path_statistics_workspace_size(B, T, S, K, counting ? 1 : 0)) return TORBI_HIP_EWORKSPACE;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const ps::Layout l = ps::layout(counting ? fb_base(workspace) : nullptr, S, counting);
+    hipError_t e;
+    if (counting && (e = hipMemsetAsync(l.x, 0, l.zeroed, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(ps::ps_kernel, dim3((unsigned)((paths + ps::kWaves - 1) / ps::kWaves)), dim3(ps::kThreads), 0, st,
+                       observation, batch_frames, transition, uniform_value, initial, indices, path_weights, scores_out, l.x, l.i,
+                       B, T, S, K);
+    if ((e = hipGetLastError()) != hipSuccess || !counting) return (int)e;
+    const size_t passes = ((size_t)S * S + S + 255) / 256;
+    const unsigned blocks = (unsigned)std::min<size_t>(passes, (size_t)cu_count(device) * 32);
+    hipLaunchKernelGGL(ps::ps_round_kernel, dim3(blocks), dim3(256), 0, st, l.x, l.i, transition_counts_out, initial_counts_out, S);
     return (int)hipGetLastError();
 }
 

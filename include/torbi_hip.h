@@ -939,6 +939,44 @@ int torbi_hip_path_statistics(const float *observation, const int32_t *batch_fra
                               float *transition_counts_out, float *initial_counts_out, void *workspace, size_t workspace_bytes,
                               int B, int T, int S, int K, int device, void *stream);
 
+/*
+ * Path entropy (added within ABI 17): the entropy, in nats, of the posterior over whole state paths of every item,
+ *     H_b = - sum over every path q of item b of P(q | o_b) log P(q | o_b),
+ * on the model torbi_hip_forward_backward takes (torbi_amd/entropy.py, ENTROPY.md): observation (B, T, S) log scores,
+ * batch_frames (B,) int32 (F: clamped to [1, T]), transition (S, S) log [next][prev] (-inf a zero probability; it need not
+ * be stochastic), initial (S,) log.  The forward-only recursion of Hernando, Crespi and Cybenko on the scaled forward pass,
+ * with E = exp(transition), G = E o transition (0 where transition = -inf), p_t the filtered distribution, xlogx(0) = 0:
+ *     h_0 = 0,   u_t[j] = p_t[j] h_t[j] - xlogx(p_t[j]),   d = E p_{t-1}
+ *     h_t[j] = log d[j] + ((E u_{t-1})[j] - (G p_{t-1})[j]) / d[j]        (0 where d[j] = 0)
+ *     prefix_t = sum_j u_t[j]   (the entropy of q_0 .. q_t given o_0 .. o_t),   H = prefix_{F-1}
+ * entropy_out (B,) fp32: H.  prefix_out (B, T) fp32 or null: prefix_t, 0 for t >= F_b.  loglik_out (B,) fp32: the
+ * log-likelihood of torbi_hip_forward_backward.  Products in float32 on the matrix pipe; the sums over states that give
+ * prefix_t and the sum over frames that gives the log-likelihood in float64, rounded once.  The entropy is what the
+ * arithmetic gives: it is not clamped at 0.  A NaN or +inf in anything an item reads (initial, the matrix when F_b >= 2, its
+ * observation rows t < F_b) gives that item a NaN log-likelihood, a NaN entropy and NaN prefix entries t < F_b; an item of
+ * total probability 0 has log-likelihood -inf and the same NaNs.  An item's bits never depend on other items' data, on the
+ * batch size or on what the workspace held.
+ *
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_path_entropy_workspace_size(B, T, S, uniform)
+ * bytes: with uniform == 0 two padded copies of the matrix, four scalars per item and frame, and four rows and two rows of
+ * 32-row partial sums per item; else two float64 per item and frame.  It holds no (B, T, S) region.  The size query answers
+ * 256 for dimensions below 1 or S > 16384.
+ * The general route takes two launches per frame, the uniform route two launches; no allocation and no host synchronisation:
+ * a call can be captured into a graph.
+ * The uniform entry point takes a matrix whose every entry is `uniform_value` (torbi_amd passes fl(log(1/S))): frames are
+ * independent there, prefix_t is the running sum of the entropies of softmax(obs_s) (s = 0: softmax(initial + obs_0)).
+ * TORBI_HIP_EINVAL for a null pointer other than prefix_out, B < 0, T < 1 or S < 1; TORBI_HIP_ERANGE for S > 16384,
+ * B * T > 2^32, B * T * S > 2^40 or B > 32 * 65535; TORBI_HIP_EWORKSPACE for a workspace that is too small.  All are
+ * answered before a device is touched.  B == 0 launches nothing and returns 0.
+ */
+size_t torbi_hip_path_entropy_workspace_size(int B, int T, int S, int uniform);
+int torbi_hip_path_entropy(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                           float *entropy_out, float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                           int B, int T, int S, int device, void *stream);
+int torbi_hip_path_entropy_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                   const float *initial, float *entropy_out, float *prefix_out, float *loglik_out,
+                                   void *workspace, size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ from . import synth
 from . import distributed
 from . import margins
 from . import paths
+from . import entropy
 from . import timer
 from .pipeline import DecodePipeline
 from .state import reset as reset_path_state
@@ -41,4 +42,4 @@ __all__ = ['decode', 'decode_batches', 'decode_cpu', 'chunk', 'decode_uniform', 
            'expected_counts_banded_workspace_bytes', 'band_counts_to_dense', 'counts_route', 'stream_route', 'decode_k_best_banded',
            'decode_k_best_banded_workspace_bytes', 'k_best_route', 'sample_paths', 'forward_sample',
            'forward_sample_workspace_bytes', 'forward_sample_banded', 'forward_sample_banded_workspace_bytes', 'sample_route',
-           'StreamPosteriors', 'stream_posterior_route', 'margins', 'paths']
+           'StreamPosteriors', 'stream_posterior_route', 'margins', 'paths', 'entropy']

@@ -185,6 +185,13 @@ SYMBOLS = {
     'torbi_hip_path_statistics': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_path_entropy_workspace_size': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_path_entropy': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_path_entropy_uniform': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
 }
 
 MAX_BATCHES = 16        # TORBI_HIP_MAX_BATCHES
@@ -281,7 +288,7 @@ def run(name, observation, frames, inputs, outputs, need, dims, workspace=None):
     """One call of a C entry of the form NAME(observation, batch_frames, inputs..., outputs..., workspace, workspace_bytes,
     dims..., device, stream) on the device of `observation` (float32, contiguous); returns `outputs`.  `frames` goes there
     as contiguous int32 and a tensor among `inputs`, which are in the entry's order, as contiguous float32 -- one already
-    in place is not copied --, a number or None as it is.  `need`: (the entry that answers the workspace's size, its
+    in place is not copied --, a number or None as it is; None among `outputs` is a null pointer.  `need`: (the entry that answers the workspace's size, its
     arguments); `workspace`: the caller's, checked, else a fresh one.  An empty batch (dims[0] == 0) launches nothing."""
     if dims[0] == 0:
         return outputs
@@ -298,7 +305,7 @@ def run(name, observation, frames, inputs, outputs, need, dims, workspace=None):
             v = v.data_ptr()
         args.append(v)
     for t in outputs:
-        args.append(t.data_ptr())
+        args.append(None if t is None else t.data_ptr())       # (an output the entry may go without: a null pointer)
     check(getattr(lib, name)(*args, workspace.data_ptr(), workspace.numel(), *dims, index, stream), name)
     return outputs
 

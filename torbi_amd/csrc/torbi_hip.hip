@@ -54,6 +54,7 @@
 #include "max_marginals.hpp"
 #include "max_marginals_band.hpp"
 #include "path_statistics.hpp"
+#include "path_entropy.hpp"
 
 namespace {
 
@@ -3425,6 +3426,98 @@ int torbi_hip_path_statistics(const float *observation, const int32_t *batch_fra
     const size_t passes = ((size_t)S * S + S + 255) / 256;
     const unsigned blocks = (unsigned)std::min<size_t>(passes, (size_t)cu_count(device) * 32);
     hipLaunchKernelGGL(ps::ps_round_kernel, dim3(blocks), dim3(256), 0, st, l.x, l.i, transition_counts_out, initial_counts_out, S);
+    return (int)hipGetLastError();
+}
+
+// ---- path entropy: the entropy of the posterior over whole state paths (path_entropy.hpp) ----
+
+size_t torbi_hip_path_entropy_workspace_size(int B, int T, int S, int uniform) {
+    if (B < 1 || T < 1 || S < 1 || S > pe::kMaxStates) return 256;
+    return pe::layout(nullptr, B, T, S, uniform != 0).total;
+}
+
+static int pe_args_ok(const void *obs, const void *frames, const void *matrix, const void *initial, const void *entropy,
+                      const void *loglik, const void *ws, size_t ws_bytes, int B, int T, int S, int uniform) {
+    if (B < 0 || T < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!obs || !frames || !matrix || !initial || !entropy || !loglik || !ws) return TORBI_HIP_EINVAL;
+    if (!fb_shape_in_range(B, T, S)) return TORBI_HIP_ERANGE;
+    if (ws_bytes < torbi_hip_path_entropy_workspace_size(B, T, S, uniform)) return TORBI_HIP_EWORKSPACE;
+    return TORBI_HIP_OK;
+}
+
+int torbi_hip_path_entropy(const float *observation, const int32_t *batch_frames, const float *transition, const float *initial,
+                           float *entropy_out, float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                           int B, int T, int S, int device, void *stream) {
+    const int rc = pe_args_ok(observation, batch_frames, transition, initial, entropy_out, loglik_out, workspace,
+                              workspace_bytes, B, T, S, 0);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const pe::Layout l = pe::layout(fb_base(workspace), B, T, S, false);
+    float *const prefix = prefix_out ? prefix_out : l.prefix;
+    const size_t xrow = (size_t)B * fb::padded_states(S), prow = (size_t)B * fb::partials_of(S);
+    hipError_t e;
+    if (T > 1) {
+        const size_t n = (size_t)fb::padded_rows(S) * fb::padded_states(S);
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(pe::pe_prepare_kernel, dim3(grid), dim3(256), 0, st, transition, l.E, l.G, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    const size_t nrows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pe::pe_first_kernel, dim3(B, (S + 255) / 256), dim3(256), 0, st, observation, initial, l.m, l.p, l.u,
+                       l.partial, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    // One step launch: 32 x 32 tiles (states x items).  With at least two tiles per compute unit, four waves per tile stage
+    // the operands through LDS; with fewer, the waves read their chunks from global memory.  K is split over pe::waves_of(S)
+    // waves in both forms, chunk by chunk alike, so an item's bits do not depend on the form, that is on the batch size.
+    const unsigned tiles = (unsigned)((S + 31) / 32) * (unsigned)((B + 31) / 32);
+    const dim3 grid((S + 31) / 32, (B + 31) / 32);
+    const int KS = pe::waves_of(S);
+    const bool staged = KS == pe::kMaxWaves && tiles >= 2u * cu_count(device);
+    for (int t = 0; t < T; ++t) {
+        const int now = t & 1, before = now ^ 1;
+        if (t > 0) {
+            by_flag(staged, [&](auto staged_) {
+                auto *kernel = &pe::pe_step_kernel<decltype(staged_)::value>;
+                hipLaunchKernelGGL(kernel, grid, dim3(64 * KS), 0, st, observation, batch_frames, l.E, l.G, l.m, l.p + before * xrow,
+                                   l.u + before * xrow, l.p + now * xrow, l.u + now * xrow, l.partial + now * prow, t, B, T, S, KS);
+            });
+            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        }
+        hipLaunchKernelGGL(pe::pe_item_kernel, dim3(B), dim3(256), 0, st, batch_frames, l.partial + now * prow, l.p + now * xrow,
+                           l.u + now * xrow, l.c, prefix, t, T, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(pe::pe_final_kernel, dim3(B), dim3(256), 0, st, batch_frames, l.m, l.c, prefix, entropy_out, loglik_out, T);
+    return (int)hipGetLastError();
+}
+
+int torbi_hip_path_entropy_uniform(const float *observation, const int32_t *batch_frames, float uniform_value,
+                                   const float *initial, float *entropy_out, float *prefix_out, float *loglik_out,
+                                   void *workspace, size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = pe_args_ok(observation, batch_frames, initial /* (no matrix) */, initial, entropy_out, loglik_out, workspace,
+                              workspace_bytes, B, T, S, 1);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const pe::Layout l = pe::layout(fb_base(workspace), B, T, S, true);
+    const size_t rows = (size_t)B * T;
+    const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(observation) & 15) == 0;
+    by_flag(vec, [&](auto vec_) {
+        auto *kernel = &pe::pe_uniform_rows_kernel<decltype(vec_)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames, initial, l.rowh,
+                           l.lse, B, T, S);
+    });
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pe::pe_uniform_scan_kernel, dim3((B + 63) / 64), dim3(64), 0, st, batch_frames, l.rowh, l.lse,
+                       uniform_value, entropy_out, prefix_out, loglik_out, B, T);
     return (int)hipGetLastError();
 }
 

@@ -977,6 +977,39 @@ int torbi_hip_path_entropy_uniform(const float *observation, const int32_t *batc
                                    const float *initial, float *entropy_out, float *prefix_out, float *loglik_out,
                                    void *workspace, size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
+/*
+ * Path entropy on a band with one value outside it (added within ABI 17; torbi_amd/entropy.py forward_entropy_banded,
+ * ENTROPY.md "Band route"): what torbi_hip_path_entropy computes, for a matrix of which the caller states a band
+ *     transition[j][i] ([next][prev]) with j - reach_left <= i <= j + reach_right
+ * and promises that every entry outside it equals `background` bit for bit, as for torbi_hip_forward_backward_band.  With
+ * ebg = exp(background) and gbg = ebg * background (both 0 for -inf) every product of the recursion splits into the band
+ * and one constant,
+ *     (E x)[j] = sum_{i in band(j)} (E[j][i] - ebg) x[i] + ebg * sum_i x[i],   (G x)[j] likewise with G - gbg and gbg,
+ * so a frame costs 3 W multiplies per state, W = reach_left + reach_right + 1 (reaches clamped to S - 1).  The division by
+ * the row sum is deferred: the kernel carries a_t (sum c_t) and v_t = a_t h_t - xlogx(a_t), from which
+ * prefix_t = (sum_j v_t[j]) / c_t + log c_t in float64.  The outputs, the non-finite rules and the independence of an
+ * item's bits from the batch are torbi_hip_path_entropy's; the values agree with it within the bound of ENTROPY.md, not bit
+ * for bit, and a single-path model gives 0 within that bound, not exactly.  The promise is checked on the device without the
+ * host waiting for it: where it is broken every item has a NaN log-likelihood, a NaN entropy and NaN prefix entries t < F_b.
+ *
+ * torbi_hip_path_entropy_band_covers reads no device and answers 1 for 1 <= S <= 4096, min(W, S) <= 64, a background that is
+ * neither NaN nor +inf, B >= 1, T >= 1 within torbi_hip_path_entropy's limits, and one item's rows within the kernel's LDS.
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_path_entropy_band_workspace_size bytes: the two
+ * sets of diagonals [W][S up to 64], three scalars per item and frame (row maxima, row sums, the prefix where prefix_out is
+ * null) and the promise flag.  It holds no (B, T, S) region.  The size query answers 256 for dimensions below 1, a negative
+ * reach or S > 4096.
+ * Four launches whatever T, no allocation and no host synchronisation: a call can be captured into a graph.
+ * TORBI_HIP_EINVAL for a null pointer other than prefix_out, a negative reach, B < 0, T < 1 or S < 1; TORBI_HIP_ERANGE for a
+ * shape beyond torbi_hip_path_entropy's limits; TORBI_HIP_EUNSUPPORTED where _covers answers 0; TORBI_HIP_EWORKSPACE for a
+ * workspace that is too small; in that order and all before a device is touched.  B == 0 launches nothing and returns 0.
+ */
+int torbi_hip_path_entropy_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_path_entropy_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_path_entropy_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S,
+                                int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

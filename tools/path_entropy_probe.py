@@ -16,6 +16,11 @@ and in the same process on the same inputs:
 and, measured but asserted nowhere, the error against the float64 host route on a deliberately mismatched input: softmax rows
 of scale 12 whose peak jumps anywhere among the states, under the -inf pitch band of 23 diagonals, where the filtered
 distribution underflows float32 (--mismatched-items items, 0 to skip).
+
+With --band, the band rows alone (ENTROPY.md, "Band route"): entropy.forward_entropy_banded against the dense route on the
+same inputs in the same process, for the pitch band of --half-widths (12: 23 diagonals, 88: 175) in both forms of its
+background (-inf and log(tiny)) at every batch of --batches, by the same method.  A band the band route does not cover (175
+diagonals: beyond its window of 64 entries) has a dense time and no band time.
 """
 import argparse
 import json
@@ -129,19 +134,71 @@ def shape_rows(B, T, S, repeats, torch_repeats):
     return out
 
 
+def band_rows(T, S, repeats, batches, half_widths):
+    """The band route (entropy.forward_entropy_banded) against the dense route on the same inputs in the same process: the
+    pitch band of `half_width` (2 * half_width - 1 diagonals) in both forms of its background, -inf and log(tiny), at every
+    batch of `batches`.  `wins`: the dense median exceeds the band median by more than the dense route's own spread
+    (max - min); `difference_in_units`: the worst |H_band - H_dense| and the same for the prefix entries in units of
+    1e-6 |H| + 1e-6 F (each route is within 20 units of float64 on the test shapes)."""
+    dev = torch.device('cuda:0')
+    rows = []
+    for B in batches:
+        obs, _, init = (torch.from_numpy(x).to(dev) for x in synth.problem(B, T, S, seed=1))
+        frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+        dense_ws = torch.empty(entropy.path_entropy_workspace_bytes(B, T, S), dtype=torch.uint8, device=dev)
+        upto = torch.arange(1, T + 1, dtype=torch.float64, device=dev)[None, :]
+        for half_width in half_widths:
+            reach = half_width - 1
+            for tiny in (False, True):
+                matrix = synth.banded_transition(S, half_width, tiny=tiny)
+                background = float(matrix[0, S - 1])
+                trans = torch.from_numpy(matrix).to(dev)
+                dense = timed(lambda: entropy.forward_entropy(obs, frames, trans, init, workspace=dense_ws), repeats)
+                row = {'batch': B, 'diagonals': 2 * reach + 1, 'background': background, 'dense_ms': dense,
+                       'covered': bool(entropy._covered(B, T, S, reach, reach, background))}
+                rows.append(row)
+                if not row['covered']:
+                    continue
+                band_ws = torch.empty(entropy.path_entropy_banded_workspace_bytes(B, T, S, reach, reach), dtype=torch.uint8,
+                                      device=dev)
+                run = lambda prefix=False: entropy.forward_entropy_banded(obs, frames, trans, init, reach, reach, background,
+                                                                          workspace=band_ws, prefix=prefix)
+                band = timed(run, repeats)
+                want = [x.double() for x in entropy.forward_entropy(obs, frames, trans, init, workspace=dense_ws, prefix=True)]
+                got = [x.double() for x in run(prefix=True)]
+                units = lambda g, w, f: float(((g - w).abs() / (1e-6 * w.abs() + 1e-6 * f)).max())
+                row.update({'band_ms': band, 'speedup': dense['median'] / band['median'],
+                            'wins': dense['median'] - band['median'] > dense['max'] - dense['min'],
+                            'difference_in_units': [units(got[0], want[0], T), units(got[2], want[2], upto)],
+                            'worst_difference_of_L': float((got[1] - want[1]).abs().max()),
+                            'nan_values': int(sum(torch.isnan(x).sum() for x in got)),
+                            'entropy_min_max': [float(want[0].min()), float(want[0].max())],
+                            'band_workspace_bytes': band_ws.numel()})
+                del want, got
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--band', action='store_true', help='the band rows alone (ENTROPY.md, "Band route")')
+    ap.add_argument('--batches', type=int, nargs='+', default=[1, 8, 512])
+    ap.add_argument('--half-widths', type=int, nargs='+', default=[12, 88])
     ap.add_argument('--shapes', type=int, nargs=3, action='append', metavar=('B', 'T', 'S'))
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--torch-repeats', type=int, default=3)
     ap.add_argument('--mismatched-items', type=int, default=8)
     ap.add_argument('--out', default=None, help='also write the JSON here')
     args = ap.parse_args()
-    shapes = args.shapes or [[512, 500, 1440], [1, 500, 1440]]
-    out = {'device': torch.cuda.get_device_name(0), 'repeats': args.repeats,
-           'shapes': [shape_rows(B, T, S, args.repeats, args.torch_repeats) for B, T, S in shapes]}
-    if args.mismatched_items:
-        out['mismatched'] = mismatched(args.mismatched_items, 500, 1440)
+    if args.band:
+        T, S = (args.shapes or [[0, 500, 1440]])[0][1:]
+        out = {'device': torch.cuda.get_device_name(0), 'frames_states': [T, S], 'repeats': args.repeats,
+               'band_rows': band_rows(T, S, args.repeats, args.batches, args.half_widths)}
+    else:
+        shapes = args.shapes or [[512, 500, 1440], [1, 500, 1440]]
+        out = {'device': torch.cuda.get_device_name(0), 'repeats': args.repeats,
+               'shapes': [shape_rows(B, T, S, args.repeats, args.torch_repeats) for B, T, S in shapes]}
+        if args.mismatched_items:
+            out['mismatched'] = mismatched(args.mismatched_items, 500, 1440)
     text = json.dumps(out)
     if args.out:
         with open(args.out, 'w') as fh:

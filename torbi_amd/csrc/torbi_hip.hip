@@ -55,6 +55,7 @@
 #include "max_marginals_band.hpp"
 #include "path_statistics.hpp"
 #include "path_entropy.hpp"
+#include "path_entropy_band.hpp"
 
 namespace {
 
@@ -3519,6 +3520,60 @@ int torbi_hip_path_entropy_uniform(const float *observation, const int32_t *batc
     hipLaunchKernelGGL(pe::pe_uniform_scan_kernel, dim3((B + 63) / 64), dim3(64), 0, st, batch_frames, l.rowh, l.lse,
                        uniform_value, entropy_out, prefix_out, loglik_out, B, T);
     return (int)hipGetLastError();
+}
+
+// ---- path entropy on a band with one constant outside it (path_entropy_band.hpp) ----
+
+int torbi_hip_path_entropy_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device) {
+    if (!torbi_hip_forward_backward_band_covers(B, T, S, reach_left, reach_right, background, device)) return 0;
+    // (one item's rows: true of every shape the window admits, peb::kMaxLdsBytes says why)
+    return peb::lds_bytes(1, S, fbb::band_of(S, reach_left, reach_right).halo) <= (size_t)peb::kMaxLdsBytes ? 1 : 0;
+}
+
+size_t torbi_hip_path_entropy_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > peb::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return peb::layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+// Items per workgroup of pe_band_kernel<G>: fb_band_tile's rule with the pairs in the place of the rows.
+static int pe_band_tile(int B, int S, int halo, int cus) {
+    return items_per_workgroup(peb::kMaxGroup, B, 1, cus, [&](int G) { return peb::lds_bytes(G, S, halo) <= (size_t)peb::kMaxLdsBytes; });
+}
+
+int torbi_hip_path_entropy_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S,
+                                int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && entropy_out && loglik_out && workspace,
+        torbi_hip_path_entropy_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_path_entropy_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const peb::Layout l = peb::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const float ebg = exp_background(background), gbg = background == -INFINITY ? 0.f : ebg * background;
+    hipError_t e;
+    if ((e = peb::prepare_and_verify(transition, l, ebg, gbg, background, S, st)) != hipSuccess) return (int)e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, observation, batch_frames, initial,
+                       l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const int G = pe_band_tile(B, S, l.halo, cu_count(device));
+    const size_t lds = peb::lds_bytes(G, S, l.halo);
+    float *const prefix = prefix_out ? prefix_out : l.prefix;
+    e = by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &peb::pe_band_kernel<decltype(g)::value>;
+        const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+        if (granted != hipSuccess) return granted;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(peb::kThreads), lds, st, observation, batch_frames, initial, l.Df,
+                           l.Dg, l.m, l.c, l.flag, prefix, entropy_out, loglik_out, ebg, gbg, l.reach_left, l.reach_right, l.W,
+                           l.Sd, B, T, S);
+        return hipGetLastError();
+    });
+    return (int)e;
 }
 
 }  // extern "C"

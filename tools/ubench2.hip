@@ -12,10 +12,14 @@ template <int MODE>
 __global__ __launch_bounds__(1024) void valu(float *out, int iters, float seed) {
     float a[16], b[16];
     float2v pa[16], pb[16], pc[16];
+    unsigned ia[16], ib[16];                   // the integer rows (MODE 8 .. 11): what address arithmetic is made of
+    unsigned long long la[16], lb[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         a[k] = seed + threadIdx.x + k; b[k] = seed * k;
         pa[k] = float2v{a[k], b[k]}; pb[k] = float2v{b[k], a[k]}; pc[k] = pa[k];
+        ia[k] = (unsigned)seed * 2654435761u + threadIdx.x + k; ib[k] = ia[k] | 1u;
+        la[k] = ((unsigned long long)ia[k] << 20) + k; lb[k] = la[k] ^ ib[k];
     }
     for (int it = 0; it < iters; ++it) {
         if (MODE == 0) {          // v_add_f32
@@ -62,11 +66,27 @@ __global__ __launch_bounds__(1024) void valu(float *out, int iters, float seed) 
 #define X(k) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(pa[k]) : "v"(pb[k]));
             REP16(X) REP16(X)
 #undef X
+        } else if (MODE == 8) {   // v_mul_lo_u32
+#define X(k) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(ia[k]) : "v"(ib[k]));
+            REP16(X) REP16(X)
+#undef X
+        } else if (MODE == 9) {   // v_mad_u64_u32: 32 x 32 + 64 -> 64 (item * T * S + ...)
+#define X(k) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(la[k]) : "v"(ia[k]), "v"(ib[k]) : "vcc");
+            REP16(X) REP16(X)
+#undef X
+        } else if (MODE == 10) {  // v_mad_i64_i32
+#define X(k) asm volatile("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(la[k]) : "v"(ia[k]), "v"(ib[k]) : "vcc");
+            REP16(X) REP16(X)
+#undef X
+        } else if (MODE == 11) {  // v_lshl_add_u64: (64 << 2) + 64 (pointer + 4 * element offset)
+#define X(k) asm volatile("v_lshl_add_u64 %0, %0, 2, %1" : "+v"(la[k]) : "v"(lb[k]));
+            REP16(X) REP16(X)
+#undef X
         }
     }
     float s = 0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) s += a[k] + pa[k].x + pa[k].y + pc[k].x + pc[k].y;
+    for (int k = 0; k < 16; ++k) s += a[k] + pa[k].x + pa[k].y + pc[k].x + pc[k].y + (float)ia[k] + (float)la[k];
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
@@ -109,5 +129,9 @@ int main() {
     run<4>("pk_add+max3 (32 cells)", 32, out, CUS);
     run<5>("add,add,max3 (32 cells)", 48, out, CUS);
     run<6>("add+max (16 cells)", 32, out, CUS);
+    run<8>("v_mul_lo_u32", 32, out, CUS);
+    run<9>("v_mad_u64_u32", 32, out, CUS);
+    run<10>("v_mad_i64_i32", 32, out, CUS);
+    run<11>("v_lshl_add_u64", 32, out, CUS);
     return 0;
 }

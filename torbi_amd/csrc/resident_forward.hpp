@@ -129,11 +129,11 @@ constexpr unsigned long long kClusterWaitTicks = 25000000ull;
 inline bool supported(int S) { return S >= 64 && S <= pruned::kMaxS; }
 
 // dynamic LDS: posterior tile [S4][16] + running top lists (64-bit keys) + decoded top lists + frame counts + items
-// + 4 control words (cluster ticket, gave-up flag)
+// + 4 control words (cluster ticket, gave-up flag) + the items' element offsets into obs / hist (64-bit)
 inline size_t lds_bytes(int S, int ktop = kTop) {
     const size_t S4 = ((size_t)S + 3) / 4 * 4, ni = (size_t)tile_items(S);
     return sizeof(float) * ni * S4 + sizeof(u64) * kNI * ktop + (sizeof(float) + sizeof(int)) * kNI * ktop +
-           2 * sizeof(int) * kNI + 4 * sizeof(int);
+           2 * sizeof(int) * kNI + 4 * sizeof(int) + sizeof(u64) * kNI;
 }
 
 // row groups (16 next-states) member m of R scans: [m * nrg / R, (m + 1) * nrg / R)
@@ -226,11 +226,14 @@ __device__ __forceinline__ int prio_level(int left) { return left >= 6 ? 3 : lef
 // A wave keeps ONE entry pair of posterior reads (two ds_read_b128) requested ahead of the pair it evaluates.  Two pairs
 // ahead (+2.5 %, eight more registers) and the eight adds of a pair split into eight temporaries ahead of the four maxima
 // (+1 %) were slower: profiles/scan_pipeline_ab.txt, profiles/scan_pipeline_kernel_registers.txt.
-// Item numbers (kReloadItems in the kernel): the whole-tile instances of more than twelve waves do not hold their lanes'
-// four item numbers in registers: a pass reads them from the LDS (one ds_read_b128) where it forms its observation addresses and again where it
-// forms its history addresses.  With sixteen waves (four a SIMD) the one-seed instance then takes 111 registers instead of
-// the 128 its launch bound caps it at: 4 x 112 allocated leave 64 of a SIMD's 512 for the other stream's backtrace and
-// preparation kernels, which otherwise wait for the whole forward launch (HISTORY.md).
+// Item bases (`sbase` in the kernel): no instance holds its lanes' four items in registers, and none multiplies by an item
+// number inside the time loop.  The tile's table of element offsets item * T * S -- obs and hist have one shape, one table
+// serves both -- is written once at kernel entry; a pass reads its lane's four 64-bit offsets from the LDS (two
+// ds_read_b128) where it forms its observation addresses and again where it forms its history addresses, and an address is
+// pointer + (base + t * S + state), t * S formed once per timestep on the scalar side.  Read where they are used, not ahead
+// of the pass and kept: with sixteen waves (four a SIMD) the one-seed instance takes 111 registers instead of the 128 its
+// launch bound caps it at: 4 x 112 allocated leave 64 of a SIMD's 512 for the other stream's backtrace and preparation
+// kernels, which otherwise wait for the whole forward launch (HISTORY.md).
 
 #ifdef RESIDENT_STAMP
 // build-time instrumentation (tools/resident_stamps.py): per-wave cycle sums of the phases of a timestep
@@ -273,6 +276,9 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     int *sframes = mtopi + kNI * kTop;                                // [16] frames per item (0 past the batch)
     int *sitem = sframes + kNI;                                       // [16] item numbers (a valid one past the batch)
     int *smisc = sitem + kNI;                                         // [0] cluster ticket, [1] gave up waiting
+    u64 *sbase = reinterpret_cast<u64 *>(smisc + 4);                  // [16] element offset item * T * S into obs and hist
+    static_assert(((sizeof(u64) + sizeof(float) + sizeof(int)) * kNI * kTop + 2 * sizeof(int) * kNI + 4 * sizeof(int)) % 16 == 0,
+                  "sbase is read 16 bytes at a time (the tile in front of the lists is whole 64-byte rows)");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -348,6 +354,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         }
         sframes[tid] = f;
         sitem[tid] = item;
+        sbase[tid] = (u64)item * T * S;
     }
     if (tid < kNI * kTop) top[tid] = 0ull;
     __syncthreads();
@@ -385,22 +392,14 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     const unsigned xrow = (unsigned)S4 * kNI * (unsigned)sizeof(float);
     const unsigned xbytes = (unsigned)cluster_slot_bytes(S);
     static_assert(kTop <= kMaxTop, "a member publishes at most kMaxTop list entries per item");
-    // items of this lane: tile items 4g .. 4g+3; items past the batch read a valid one's observations and store nothing
-    // (the whole-tile instances of more than twelve waves read them from `sitem` pass by pass instead)
-    constexpr bool kReloadItems = KW > 12 && !CLUSTER;
-    int ib[4];
-#pragma unroll
-    for (int it = 0; it < 4; ++it) ib[it] = sitem[4 * g + it];
-    auto items_now = [&](int (&now)[4]) {
-        if constexpr (kReloadItems) {
-            int at = 4 * g;
-            asm volatile("" : "+v"(at));        // (read here, not ahead of the pass and kept)
-            const int4 v = *reinterpret_cast<const int4 *>(sitem + at);
-            now[0] = v.x; now[1] = v.y; now[2] = v.z; now[3] = v.w;
-        } else {
-#pragma unroll
-            for (int it = 0; it < 4; ++it) now[it] = ib[it];
-        }
+    // items of this lane: tile items 4g .. 4g+3; items past the batch read a valid one's observations and store nothing.
+    // Their element offsets into obs / hist come from `sbase` where a pass needs them
+    auto bases_now = [&](u64 (&now)[4]) {
+        int at = 4 * g;
+        asm volatile("" : "+v"(at));        // (read here, not ahead of the pass and kept)
+        const ulonglong2 lo = *reinterpret_cast<const ulonglong2 *>(sbase + at);
+        const ulonglong2 hi = *reinterpret_cast<const ulonglong2 *>(sbase + at + 2);
+        now[0] = lo.x; now[1] = lo.y; now[2] = hi.x; now[3] = hi.y;
     };
 
     float pend[MAXP][4];
@@ -426,8 +425,10 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         load_list_block(head0, row, 0);
         load_list_block(head1, row, kBlk);
         if (fmax > 1) {
+            u64 in[4];
+            bases_now(in);
 #pragma unroll
-            for (int it = 0; it < 4; ++it) obnext[it] = obs[((size_t)ib[it] * T + 1) * S + jr];
+            for (int it = 0; it < 4; ++it) obnext[it] = obs[in[it] + ((u64)S + (unsigned)jr)];
         }
     }
     // scan statistics for adaptive path selection (every 16th timestep): how many 16-entry list blocks a wave pass
@@ -470,6 +471,7 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
     for (int t = 1; t < fmax; ++t) {
         __syncthreads();      // tile = posterior row t-1, mtop = its largest entries, `top` is empty
         RSTAMP(0);
+        const u64 tS = (u64)t * S;      // element offset of row t within an item (wave-uniform: the scalar side)
 
         // seeds and bound of this lane's four items: the kR largest posteriors are explicit candidates, the
         // (kR+1)-th bounds every other one.  Items that have ended (t >= frames) get thr = -inf: their bound
@@ -501,7 +503,9 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
         // where they would cost ~10 registers per pass)
         int opaque = 0;
         asm volatile("" : "+s"(opaque));
-#pragma unroll
+        // (unrolled by COUNT: a bare `unroll` is dropped above a size the eleven-pass loops sit at, and pend[] of a loop
+        // that stays rolled goes to scratch -- with the table addresses the one-seed 8-item instance fell on that side)
+#pragma unroll MAXP
         for (int p = 0; p < MAXP; ++p) {
             const int rg = rg_lo + wave + KW * p + opaque;  // wave-uniform
             if (rg < rg_hi) {
@@ -529,11 +533,11 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                 } else {
                     load_list_block(cur, row, 0);
                     load_list_block(nxt, row, kBlk);
-                    int in[4];
-                    items_now(in);
+                    u64 in[4];
+                    bases_now(in);
 #pragma unroll
                     for (int it = 0; it < 4; ++it)
-                        ob[it] = (RESIDENT_ABL & 32) ? 0.5f * it : obs[((size_t)in[it] * T + t) * S + jr];
+                        ob[it] = (RESIDENT_ABL & 32) ? 0.5f * it : obs[in[it] + (tS + (unsigned)jr)];
                 }
                 float seedt[4][kR ? kR : 1];
 #pragma unroll
@@ -665,14 +669,14 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
                 u64 last4[4];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) last4[it] = top[(4 * g + it) * kTop + kTop - 1];
-                int out[4];
-                items_now(out);
+                u64 out[4];
+                bases_now(out);
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
                     const float o = ob[it] + best[it];                     // post'[j] = obs[t,j] + max
                     odd = odd || nonfinite::odd(o);
                     pend[p][it] = o;
-                    if (jv && live[it] && !(RESIDENT_ABL & 8)) hist[((size_t)out[it] * T + t) * S + jr] = o;
+                    if (jv && live[it] && !(RESIDENT_ABL & 8)) hist[out[it] + (tS + (unsigned)jr)] = o;
                     const u64 key = top_key(o, jr);
                     if (jv && key > last4[it] && !(RESIDENT_ABL & 16)) top_insert<kTop>(top + (4 * g + it) * kTop, key);
                 }
@@ -736,8 +740,10 @@ __global__ __launch_bounds__(64 * KW) void resident_forward_kernel(Group grp, Cl
             if (t + 1 < fmax) {
                 const int jj = kRowGroup * (rg_lo + wave) + jl;
                 const int jr = (rg_lo + wave < rg_hi && jj < S) ? jj : S - 1;
+                u64 in[4];
+                bases_now(in);
 #pragma unroll
-                for (int it = 0; it < 4; ++it) obnext[it] = obs[((size_t)ib[it] * T + t + 1) * S + jr];
+                for (int it = 0; it < 4; ++it) obnext[it] = obs[in[it] + (tS + (u64)S + (unsigned)jr)];
             }
         }
         if constexpr (CLUSTER) {

@@ -1207,7 +1207,7 @@ hipError_t launch_resident_kernel(const resident::Group &grp, const resident::Cl
 // waves per workgroup of the whole-tile, one-seed, 16-item instance at 73 .. 96 row groups (1153 .. 1536 states).  Twelve
 // waves of eight passes hold 137 registers each, three to a SIMD; sixteen waves of six passes hold 111, FOUR to a SIMD, and
 // still leave 64 of its 512 registers to the other stream's backtrace and preparation (resident_forward.hpp,
-// kReloadItems): a launch group's forward pass 13.6 -> 13.1 ms at 8 x 512 x 200 x 1440 (HISTORY.md).  Taken where
+// "Item bases"): a launch group's forward pass 13.6 -> 13.1 ms at 8 x 512 x 200 x 1440 (HISTORY.md).  Taken where
 // the launch's tiles fill more than half the compute units -- the condition under which AUTO picks whole tiles; launches of
 // fewer tiles keep twelve waves.  Fifteen waves (up to 90 row groups: every wave six passes at 1440 states, three waves on
 // one SIMD) measured between the two and are reachable through the switch only.

@@ -164,6 +164,20 @@ def test_nan_and_all_inf_items_beside_clean_items_of_a_workgroup():
     assert np.isfinite(got[1][10]).all()
 
 
+@pytest.mark.parametrize('value', [np.nan, np.inf], ids=['nan', 'plus_inf'])
+@pytest.mark.parametrize('background', [-math.inf, -20.], ids=['inf', 'm20'])
+def test_nan_or_plus_inf_in_the_matrix_inside_the_band(background, value):
+    """The matrix flag of the band route's prepare launch: the promise holds, and the lists are the dense route's and the
+    host's (an item of one frame reads no matrix and keeps its scores)."""
+    B, T, S, k, reach = 5, 4, 64, 2, (2, 2)
+    obs, trans, init = bc.model(B, T, S, 12, reach, background)
+    trans[10, 11] = value
+    frames = ragged(B, T, 3)
+    got = all_three(obs, frames, trans, init, k, reach, background)
+    assert np.isnan(got[1][0]).all() and (got[0][0] == -1).all()           # T frames
+    assert np.isfinite(got[1][B - 1, 0]) and got[0][B - 1, 0, 0] >= 0         # one frame
+
+
 @pytest.mark.parametrize('tiny', [False, True], ids=['inf', 'tiny'])
 def test_k_one_is_decode(tiny):
     B, T, S = 7, 12, 1440

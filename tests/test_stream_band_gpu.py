@@ -558,6 +558,61 @@ def test_prepare_extracts_the_diagonals_and_judges_the_promise():
         assert prepare(narrow, r=right - 1) == 0
 
 
+def prepared(lib, trans, S, left, right, bg):
+    """torbi_hip_stream_band_prepare on `trans` (numpy): (diagonals, the three words around the verdict).  The call gets the
+    middle word; NaN diagonals and SENTINEL words before it."""
+    diag = torch.full((left + right + 1, S), math.nan, device=DEV)
+    ok = torch.full((3,), SENTINEL, dtype=torch.int32, device=DEV)
+    matrix = torch.from_numpy(trans).to(DEV)
+    abi_call(lib, 'torbi_hip_stream_band_prepare', matrix.data_ptr(), S, left, right, ctypes.c_float(float(bg)), diag.data_ptr(),
+             ok[1:].data_ptr(), 0, ctypes.c_void_p(0))
+    return diag.cpu().numpy(), ok.tolist()
+
+
+@pytest.mark.parametrize('background', ['minus_inf', 'log_tiny'])
+def test_prepare_with_a_left_reach_past_the_matrix(background):
+    """reach_left = 70 at 64 states: diagonals 0 .. 6 name no column at all and are 0 throughout, no row has a column left of
+    its band, and the promise holds."""
+    lib = _lib.load()
+    S, left, right, bg = 64, 70, 3, BACKGROUNDS[background]
+    trans = band_matrix(S, left, right, bg, seed=7)
+    diag, ok = prepared(lib, trans, S, left, right, bg)
+    assert ok == [SENTINEL, 1, SENTINEL]
+    assert np.array_equal(diag, diagonals(trans, left, right))
+    assert not diag[:left - (S - 1)].any() and diag[left - (S - 1)].any()
+
+
+@pytest.mark.parametrize('background', ['minus_inf', 'log_tiny'])
+def test_prepare_with_more_diagonals_than_threads(background):
+    """W = 502 diagonals for the 256 threads of a row's workgroup, 576 states: the diagonal loop strides, and so does the
+    loop over the row."""
+    lib = _lib.load()
+    S, left, right, bg = 576, 250, 251, BACKGROUNDS[background]
+    trans = band_matrix(S, left, right, bg, seed=8)
+    diag, ok = prepared(lib, trans, S, left, right, bg)
+    assert ok == [SENTINEL, 1, SENTINEL]
+    assert np.array_equal(diag, diagonals(trans, left, right))
+    broken = trans.copy()
+    broken[10, 10 + right + 1] = np.float32(-1.)
+    assert prepared(lib, broken, S, left, right, bg)[1] == [SENTINEL, 0, SENTINEL]
+
+
+@pytest.mark.parametrize('background', ['minus_inf', 'log_tiny'])
+def test_prepare_copies_nan_and_plus_inf_inside_the_band_and_writes_one_word(background):
+    """The streaming route has no matrix alarm: a NaN and a +inf inside the band arrive in the diagonals by their bits, the
+    promise holds, and the verdict is the only word written beside the diagonals."""
+    lib = _lib.load()
+    S, left, right, bg = 64, 2, 5, BACKGROUNDS[background]
+    trans = band_matrix(S, left, right, bg, seed=9)
+    trans[10, 11] = np.nan
+    trans[20, 19] = np.inf
+    diag, ok = prepared(lib, trans, S, left, right, bg)
+    assert ok == [SENTINEL, 1, SENTINEL]
+    want = diagonals(trans, left, right)
+    assert np.isnan(want[left + 1, 10]) and np.isposinf(want[left - 1, 20])
+    assert np.array_equal(diag.view(np.int32), want.view(np.int32))
+
+
 @pytest.mark.parametrize('violation', ['capacity', 'out_capacity', 'base_slot'])
 def test_c_abi_leaves_a_stream_whose_info_does_not_fit(violation):
     """torbi_hip_stream_band_push / _flush called directly: counts_out = -1 for the stream whose info does not fit, its

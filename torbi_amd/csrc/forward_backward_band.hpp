@@ -26,6 +26,7 @@
 // t = tid, tid + 1024, ... in fp64, a butterfly per wave, the 16 wave sums in order.  No float atomics, vector stores only.
 #pragma once
 
+#include "band_diagonals.hpp"
 #include "forward_backward.hpp"
 
 namespace fbb {
@@ -105,16 +106,11 @@ __global__ void fb_band_prepare_kernel(const float *__restrict__ A, float *__res
     }
 }
 
-// ---- the promise: every entry outside the band equals `background` bit for bit; one wave per matrix row ----
+// ---- the promise: every entry outside the band equals `background` bit for bit (band_diagonals.hpp); one wave per matrix row ----
 __global__ __launch_bounds__(64) void fb_band_verify_kernel(const float *__restrict__ A, int32_t *__restrict__ flag,
                                                             float background, int reach_left, int reach_right, int S) {
     const int j = blockIdx.x, lane = threadIdx.x;
-    const float *row = A + (size_t)j * S;
-    const unsigned want = __float_as_uint(background);
-    bool broken = false;
-    for (int i = lane; i < S; i += 64)
-        if ((i < j - reach_left || i > j + reach_right) && __float_as_uint(row[i]) != want) broken = true;
-    if (broken) *flag = 1;
+    if (banddiag::stray_in_row(A + (size_t)j * S, j, reach_left, reach_right, S, __float_as_uint(background), lane, 64)) *flag = 1;
 }
 
 // host: the two launches above, in this order -- what every band entry and the streaming prepare do to a matrix first

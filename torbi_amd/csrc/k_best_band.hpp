@@ -19,30 +19,28 @@
 // a thread owns next-states j = tid + threads * m and keeps the G lists of one state in registers.  Each frame writes its
 // pointer rows ([B][T-1][k][S], (i << 5) | r: kb_walk_kernel's format), and an item's last frame writes its lists where
 // kb_final_kernel reads them.  The diagonals diag[kk][j] = A[j][j - reach_left + kk], [W][S], come from
-// kb_band_prepare_kernel and stream from L2, each load shared by the G items.
+// banddiag::prepare_kernel (band_diagonals.hpp; its alarm word is the matrix flag kb_final_kernel reads) and stream from L2,
+// each load shared by the G items.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
+#include "band_diagonals.hpp"
 #include "k_best.hpp"
 #include "wave_reduce.hpp"
 
 namespace kbb {
 
-using kb::bad_value;
 using kb::insert;
 using kb::kth_of;
 using kb::list_length;
 
 constexpr int kMaxGroup = 4;                      // items per workgroup: instances <KMAX, 4 | 2 | 1> with G * KMAX <= 16
 constexpr int kMaxThreads = 768;                  // twelve waves, three to a SIMD: up to 168 VGPRs each
-constexpr int kMaxLdsBytes = 159 * 1024;          // of the 160 KB: the reduction's partials go beside the dynamic part
-constexpr int kMinStates = 64, kMaxStates = 3072; // (what viterbi.band_over can answer: S % 4 == 0 as well)
-constexpr int kMaxWindow = 512;                   // reach_left + reach_right + 4 <= kMaxWindow
+constexpr int kMaxLdsBytes = banddiag::kMaxLdsBytes;   // (the reduction's partials go beside the dynamic part)
 constexpr int kWorkgroups = 256;                  // G is halved until the launch has this many (one per CU of an MI355X)
-constexpr int kPrepareThreads = 256;
 
 __host__ __device__ inline size_t row_words(int S, int reach_left, int reach_right) { return (size_t)S + reach_left + reach_right; }
 
@@ -78,31 +76,6 @@ inline Layout layout(char *base, int B, int T, int S, int k, int reach_left, int
     l.ok = a.take<int32_t>(1);
     l.total = a.bytes + 256;                     // (room to align the caller's base)
     return l;
-}
-
-// Row j of the matrix per workgroup: diag[kk][j] = A[j][j - reach_left + kk] (0 where that column does not exist: the
-// forward never uses it); ok[0] = 0 where an entry outside the band differs from `background` in any bit (ok[0] set to 1
-// before); flag[0] = 1 where the row holds a NaN or +inf (zeroed before): the matrix flag kb_final_kernel reads.
-__global__ __launch_bounds__(kPrepareThreads) void kb_band_prepare_kernel(const float *__restrict__ trans, float *__restrict__ diag,
-                                                                          int32_t *__restrict__ ok, int32_t *__restrict__ flag,
-                                                                          float background, int reach_left, int reach_right,
-                                                                          int S) {
-    const int j = blockIdx.x, tid = threadIdx.x;
-    const int W = reach_left + reach_right + 1;
-    const float *row = trans + (size_t)j * S;
-    for (int kk = tid; kk < W; kk += kPrepareThreads) {
-        const int i = j - reach_left + kk;
-        diag[(size_t)kk * S + j] = (i >= 0 && i < S) ? row[i] : 0.f;
-    }
-    const int want = __float_as_int(background);
-    bool stray = false, bad = false;
-    for (int i = tid; i < S; i += kPrepareThreads) {
-        const float a = row[i];
-        bad |= bad_value(a);
-        if ((i < j - reach_left || i > j + reach_right) && __float_as_int(a) != want) stray = true;
-    }
-    if (stray) ok[0] = 0;
-    if (bad) flag[0] = 1;
 }
 
 // after kb_final_kernel: a broken promise (ok[0] == 0) flags every item, whatever its frames

@@ -13,9 +13,10 @@
 //                                 fl(background + max(pre[i-rr-1], suf[i+rl+1])) )        pre / suf over w
 // A row without an out-of-band column gets -inf from the second term.  Everything else is max_marginals.hpp's contract.
 //
-// Per call: mmb_prepare_kernel (the diagonals Df[k][j] = A[j][j - rl + k], [W][S]; the promise about the entries outside the
-// band, one stray bit clears ok[0]; the matrix alarm), ONE mmb_kernel<G, SCAN> launch that runs every frame of both passes,
-// mmb_final_kernel (NaN rows and a NaN score for alarmed items, and for every item where the promise is broken).
+// Per call: banddiag::prepare_kernel (band_diagonals.hpp: the diagonals Df[k][j] = A[j][j - rl + k], [W][S]; the promise about
+// the entries outside the band, one stray bit clears ok[0]; the matrix alarm), ONE mmb_kernel<G, SCAN> launch that runs every
+// frame of both passes, mmb_final_kernel (NaN rows and a NaN score for alarmed items, and for every item where the promise is
+// broken).
 //
 // mmb_kernel: a workgroup of kThreads owns G whole items, a thread owns states tid, tid + kThreads, ... of every item of the
 // tile in both passes, so it reads back only alpha values it stored itself.  The previous row of each item (alpha_{t-1}
@@ -33,6 +34,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "band_diagonals.hpp"
 #include "scratch.hpp"
 #include "wave_reduce.hpp"
 
@@ -41,11 +43,8 @@ namespace mmb {
 constexpr int kMaxGroup = 4;                      // items per workgroup: instances <4>, <2>, <1>
 constexpr int kThreads = 1024;                    // sixteen waves hide the L2 latency of the diagonals: at most 128 VGPRs
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxLdsBytes = 159 * 1024;          // of the 160 KB: the wave totals go beside the dynamic part
-constexpr int kMinStates = 64, kMaxStates = 3072; // (what viterbi.band_over can answer: S % 4 == 0 as well)
-constexpr int kMaxWindow = 512;                   // reach_left + reach_right + 4 <= kMaxWindow
+constexpr int kMaxLdsBytes = banddiag::kMaxLdsBytes;   // (the wave totals go beside the dynamic part)
 constexpr int kWorkgroups = 256;                  // G is halved until the launch has this many (one per CU of an MI355X)
-constexpr int kPrepareThreads = 256;
 
 __host__ __device__ inline int halo_of(int reach_left, int reach_right) { return reach_left > reach_right ? reach_left : reach_right; }
 __host__ __device__ inline size_t row_words(int S, int halo) { return (size_t)S + 2 * (size_t)halo; }
@@ -73,34 +72,7 @@ inline Layout layout(char *base, int B, int S, int reach_left, int reach_right) 
     return l;
 }
 
-__device__ __forceinline__ bool odd(float x) { return !(x < INFINITY); }     // NaN or +inf
-
-// ok[0] = 1 (a launch of one thread before mmb_prepare_kernel, which only ever writes 0)
-__global__ void mmb_verdict_kernel(int32_t *__restrict__ ok) { ok[0] = 1; }
-
-// Row j of the matrix per workgroup: diag[k][j] = A[j][j - reach_left + k] (0 where that column does not exist: it meets a
-// -inf halo); ok[0] = 0 where an entry outside the band differs from `background` in any bit; matrix_alarm raised where the
-// row holds a NaN or +inf (zeroed before).
-__global__ __launch_bounds__(kPrepareThreads) void mmb_prepare_kernel(const float *__restrict__ trans, float *__restrict__ diag,
-                                                                      int32_t *__restrict__ ok, int32_t *__restrict__ matrix_alarm,
-                                                                      float background, int reach_left, int reach_right, int S) {
-    const int j = blockIdx.x, tid = threadIdx.x;
-    const int W = reach_left + reach_right + 1;
-    const float *row = trans + (size_t)j * S;
-    for (int k = tid; k < W; k += kPrepareThreads) {
-        const int i = j - reach_left + k;
-        diag[(size_t)k * S + j] = (i >= 0 && i < S) ? row[i] : 0.f;
-    }
-    const int want = __float_as_int(background);
-    bool stray = false, bad = false;
-    for (int i = tid; i < S; i += kPrepareThreads) {
-        const float a = row[i];
-        bad |= odd(a);
-        if ((i < j - reach_left || i > j + reach_right) && __float_as_int(a) != want) stray = true;
-    }
-    if (stray) ok[0] = 0;
-    if (bad) *matrix_alarm = 1;
-}
+using banddiag::nonfinite;                        // NaN or +inf
 
 // inclusive maximum over the lanes of a wave, towards higher lanes (UP) or lower ones
 template <bool UP>
@@ -264,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void mmb_kernel(const float *__restrict__
             for (int g = 0; g < G; ++g) {
                 if (!live[g]) continue;
                 const size_t at = ((size_t)(b0 + g) * T + t) * S + j;
-                seen[g] |= odd(o[g]) || odd(pi);
+                seen[g] |= nonfinite(o[g]) || nonfinite(pi);
                 const float a = o[g] + (t == 0 ? pi : acc[g]);
                 marg[at] = a;
                 nxt[(size_t)g * RW + j] = a;

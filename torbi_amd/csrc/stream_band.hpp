@@ -22,13 +22,15 @@
 //     carried [B][S]      fp32   the newest posterior row
 // A push is two launches (stream_band_forward_kernel, stream_band_walk_kernel<false, LAG>), a flush one
 // (stream_band_walk_kernel<true>).  The diagonals diag[k][j] = A[j][j - reach_left + k], [W][S], are extracted once per
-// matrix by stream_band_prepare_kernel, which also checks the caller's promise about the entries outside the band.
+// matrix by banddiag::prepare_kernel (band_diagonals.hpp), which also checks the caller's promise about the entries outside
+// the band.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
+#include "band_diagonals.hpp"
 #include "stream.hpp"
 
 namespace stream_band {
@@ -43,9 +45,7 @@ using stream::take_better;
 using stream::wave_final_state;
 
 constexpr int kMaxGroup = 4;                    // streams per workgroup: instances <1>, <2>, <4>
-constexpr int kMaxLdsBytes = 159 * 1024;   // of the 160 KB: the kernel's few static words go beside the dynamic part
-constexpr int kMinStates = 64, kMaxStates = 3072;          // (what viterbi.band_over can answer: S % 4 == 0 as well)
-constexpr int kMaxWindow = 512;                 // reach_left + reach_right + 4 <= kMaxWindow
+constexpr int kMaxLdsBytes = banddiag::kMaxLdsBytes;
 constexpr int kForwardThreads = 1024;           // of the forward kernel: sixteen waves hide the L2 latency of the diagonals
 
 // floats of one stream's row with its NaN halos
@@ -55,28 +55,6 @@ __host__ __device__ inline size_t row_words(int S, int reach_left, int reach_rig
 // pre value [S] fp32, pre index [S] int32, suf value [S], suf index [S]
 __host__ __device__ inline size_t lds_bytes(int G, int S, int reach_left, int reach_right) {
     return ((size_t)2 * G * row_words(S, reach_left, reach_right) + (size_t)4 * G * S) * 4;
-}
-
-// ok[0] = 1 (a launch of one thread before stream_band_prepare_kernel, which only ever writes 0)
-__global__ void stream_band_verdict_kernel(int32_t *__restrict__ ok) { ok[0] = 1; }
-
-// Row j of the matrix per workgroup: diag[k][j] = A[j][j - reach_left + k] (0 where that column does not exist: the forward
-// meets it with a NaN halo), and ok[0] = 0 where an entry outside the band differs from `background` in any bit.
-__global__ __launch_bounds__(kThreads) void stream_band_prepare_kernel(const float *__restrict__ trans, float *__restrict__ diag,
-                                                                       int32_t *__restrict__ ok, float background,
-                                                                       int reach_left, int reach_right, int S) {
-    const int j = blockIdx.x, tid = threadIdx.x;
-    const int W = reach_left + reach_right + 1;
-    const float *row = trans + (size_t)j * S;
-    for (int k = tid; k < W; k += kThreads) {
-        const int i = j - reach_left + k;
-        diag[(size_t)k * S + j] = (i >= 0 && i < S) ? row[i] : 0.f;
-    }
-    const int want = __float_as_int(background);
-    bool bad = false;
-    for (int i = tid; i < S; i += kThreads)
-        if ((i < j - reach_left || i > j + reach_right) && __float_as_int(row[i]) != want) bad = true;
-    if (bad) ok[0] = 0;
 }
 
 // inclusive scan of take_better over the lanes of a wave, towards higher lanes (UP) or lower ones
@@ -91,7 +69,7 @@ __device__ __forceinline__ void wave_scan(float &v, int &i, int lane) {
 }
 
 // G streams of a tile: the band recurrence over `frames` new rows each, all frames of the push in one launch.
-// obs (B, Tc, S); diag [W][S] (stream_band_prepare_kernel).  A thread owns next-states j = tid + 1024 * m; the G streams share
+// obs (B, Tc, S); diag [W][S] (banddiag::prepare_kernel).  A thread owns next-states j = tid + 1024 * m; the G streams share
 // every load of a diagonal entry.  Per frame: both scans of the G previous rows (each thread a run of consecutive states,
 // the runs joined by a wave scan and the sixteen wave totals), then the band.
 template <int G>

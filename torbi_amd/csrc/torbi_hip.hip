@@ -2303,8 +2303,7 @@ static StreamBandState stream_band_state(void *state, int B, int S, int capacity
 
 // the shapes and bands the band route takes (no wider than what torbi_hip_band_reach_over's callers ask about)
 static bool stream_band_shape(int S, int reach_left, int reach_right) {
-    return S % 4 == 0 && S >= stream_band::kMinStates && S <= stream_band::kMaxStates && reach_left >= 0 && reach_right >= 0 &&
-           (long long)reach_left + reach_right + 4 <= stream_band::kMaxWindow &&
+    return banddiag::shape_ok(S, reach_left, reach_right) &&
            stream_band::lds_bytes(1, S, reach_left, reach_right) <= (size_t)stream_band::kMaxLdsBytes;
 }
 
@@ -2326,7 +2325,7 @@ int torbi_hip_stream_band_tile(int B, int S, int reach_left, int reach_right, in
 
 size_t torbi_hip_stream_band_diagonals_bytes(int S, int reach_left, int reach_right) {
     if (S < 1 || reach_left < 0 || reach_right < 0) return 0;
-    return ((size_t)reach_left + reach_right + 1) * S * sizeof(float);
+    return banddiag::diagonals_bytes(S, reach_left, reach_right);
 }
 
 int torbi_hip_stream_band_prepare(const float *transition, int S, int reach_left, int reach_right, float background,
@@ -2335,13 +2334,9 @@ int torbi_hip_stream_band_prepare(const float *transition, int S, int reach_left
     if (!torbi_hip_stream_band_covers(1, S, reach_left, reach_right, background, device)) return TORBI_HIP_EUNSUPPORTED;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(stream_band::stream_band_verdict_kernel, dim3(1), dim3(1), 0, st, ok_out);
-    hipError_t e;
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(stream_band::stream_band_prepare_kernel, dim3(S), dim3(stream_band::kThreads), 0, st, transition,
-                       diagonals_out, ok_out, background, reach_left, reach_right, S);
-    return (int)hipGetLastError();
+    // (no matrix alarm on this route: the verdict is the only word written beside the diagonals)
+    return (int)banddiag::prepare(transition, diagonals_out, ok_out, nullptr, background, reach_left, reach_right, S,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int torbi_hip_stream_band_push(const float *observation, int Tc, const int32_t *info, const float *diagonals, const float *initial,
@@ -2389,7 +2384,7 @@ int torbi_hip_stream_band_flush(const int32_t *info, void *state, size_t state_b
     // (the flush reads no matrix: `info` stands in for torbi_hip_stream_flush's)
     const int code = stream_args_ok(info, info, state, state_bytes, capacity, indices_out, out_capacity, counts_out, B, S);
     if (code != TORBI_HIP_OK) return code;
-    if (S % 4 != 0 || S < stream_band::kMinStates || S > stream_band::kMaxStates) return TORBI_HIP_EUNSUPPORTED;
+    if (!banddiag::states_ok(S)) return TORBI_HIP_EUNSUPPORTED;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
     const StreamBandState ss = stream_band_state(state, B, S, capacity);
@@ -3168,15 +3163,14 @@ int torbi_hip_k_best_uniform(const float *observation, const int32_t *batch_fram
 int torbi_hip_k_best_band_covers(int B, int T, int S, int k, int reach_left, int reach_right, float background, int device) {
     (void)device;
     if (B < 1 || T < 1 || k < 1 || k > kb::kMaxK || reach_left < 0 || reach_right < 0) return 0;
-    if (S % 4 != 0 || S < kbb::kMinStates || S > kbb::kMaxStates || (long long)reach_left + reach_right + 4 > kbb::kMaxWindow)
-        return 0;
+    if (!banddiag::shape_ok(S, reach_left, reach_right)) return 0;
     if (kbb::lds_bytes(1, S, k, reach_left, reach_right) > (size_t)kbb::kMaxLdsBytes) return 0;
     return background_ok(background) ? 1 : 0;
 }
 
 size_t torbi_hip_k_best_band_workspace_bytes(int B, int T, int S, int k, int reach_left, int reach_right) {
-    if (B < 1 || T < 1 || S < 1 || S > kb::kMaxStates || k < 1 || k > kb::kMaxK || reach_left < 0 || reach_right < 0 ||
-        (long long)reach_left + reach_right + 4 > kbb::kMaxWindow)
+    // (S up to the dense route's limit: the byte count of a shape the band route does not cover is still an answer)
+    if (B < 1 || T < 1 || S < 1 || S > kb::kMaxStates || k < 1 || k > kb::kMaxK || !banddiag::window_ok(reach_left, reach_right))
         return 256;
     return kbb::layout(nullptr, B, T, S, k, reach_left, reach_right).total;
 }
@@ -3206,11 +3200,8 @@ int torbi_hip_k_best_band(const float *observation, const int32_t *batch_frames,
     const kbb::Layout l = kbb::layout(fb_base(workspace), B, T, S, k, reach_left, reach_right);
     hipError_t e;
     if ((e = hipMemsetAsync(l.flag, 0, sizeof(int32_t), st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(stream_band::stream_band_verdict_kernel, dim3(1), dim3(1), 0, st, l.ok);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kbb::kb_band_prepare_kernel, dim3(S), dim3(kbb::kPrepareThreads), 0, st, transition, l.diag, l.ok, l.flag,
-                       background, reach_left, reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = banddiag::prepare(transition, l.diag, l.ok, l.flag, background, reach_left, reach_right, S, st)) != hipSuccess)
+        return (int)e;
     int KMAX = 1;
     while (KMAX < k) KMAX *= 2;
     const int G = kb_band_items(B, S, k, KMAX, reach_left, reach_right);
@@ -3332,16 +3323,14 @@ int torbi_hip_max_marginals_uniform(const float *observation, const int32_t *bat
 int torbi_hip_max_marginals_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device) {
     (void)device;
     if (B < 1 || T < 1 || reach_left < 0 || reach_right < 0) return 0;
-    if (S % 4 != 0 || S < mmb::kMinStates || S > mmb::kMaxStates || (long long)reach_left + reach_right + 4 > mmb::kMaxWindow)
-        return 0;
+    if (!banddiag::shape_ok(S, reach_left, reach_right)) return 0;
     if (mmb::lds_bytes(1, S, reach_left, reach_right) > (size_t)mmb::kMaxLdsBytes) return 0;
     return background_ok(background) ? 1 : 0;
 }
 
 size_t torbi_hip_max_marginals_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
-    if (B < 1 || T < 1 || S < 1 || S > mm::kMaxStates || reach_left < 0 || reach_right < 0 ||
-        (long long)reach_left + reach_right + 4 > mmb::kMaxWindow)
-        return 256;
+    // (S up to the dense route's limit, as torbi_hip_k_best_band_workspace_bytes)
+    if (B < 1 || T < 1 || S < 1 || S > mm::kMaxStates || !banddiag::window_ok(reach_left, reach_right)) return 256;
     return mmb::layout(nullptr, B, S, reach_left, reach_right).total;
 }
 
@@ -3370,11 +3359,8 @@ int torbi_hip_max_marginals_band(const float *observation, const int32_t *batch_
     const mmb::Layout l = mmb::layout(fb_base(workspace), B, S, reach_left, reach_right);
     hipError_t e;
     if ((e = hipMemsetAsync(l.alarm, 0, ((size_t)B + 1) * sizeof(int32_t), st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mmb::mmb_verdict_kernel, dim3(1), dim3(1), 0, st, l.ok);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mmb::mmb_prepare_kernel, dim3(S), dim3(mmb::kPrepareThreads), 0, st, transition, l.diag, l.ok, l.alarm + B,
-                       background, reach_left, reach_right, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = banddiag::prepare(transition, l.diag, l.ok, l.alarm + B, background, reach_left, reach_right, S, st)) != hipSuccess)
+        return (int)e;
     const int G = mm_band_items(B, S, reach_left, reach_right);
     const size_t lds = mmb::lds_bytes(G, S, reach_left, reach_right);
     e = by_flag(background != -INFINITY, [&](auto scan) { return by_value<4, 2, 1>(G, [&](auto g) {

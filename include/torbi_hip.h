@@ -683,6 +683,31 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
                                     int T, int S, int device, void *stream);
 
 /*
+ * Wide band route of forward-backward (added within ABI 17): torbi_hip_forward_backward_band's quantities, contract, promise
+ * and non-finite rules for a band of up to 512 entries, by a kernel of its own (csrc/forward_backward_wide_band.hpp: the band
+ * packed once per call in the order the lanes read it, a lane owning 4 states x the items of its tile).  The rounding
+ * differs from the other routes'; an item's bits do not depend on how many items share its workgroup, nor on the batch.
+ *
+ * torbi_hip_forward_backward_wide_band_covers: 1 where the entry point takes the call -- 1 <= S <= 4096,
+ * reach_left + reach_right + 1 <= 512 with the reaches clamped to S - 1 (narrow bands included), the LDS rows of one item
+ * fit, a background that is neither NaN nor +inf, B and T within torbi_hip_forward_backward's limits --, else 0.  It and
+ * _workspace_size answer without a device.  _tile: the items per workgroup a call of B items takes on `device` (1, 2 or 4;
+ * 0 for arguments out of range).  The environment variable TORBI_HIP_WIDE_BAND_ITEMS (1, 2 or 4, where the tile fits the
+ * LDS) overrides that choice for a call; results do not depend on it (tools/posterior_wide_band_probe.py times every tile).
+ * workspace: torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, reach_left, reach_right) bytes, no
+ * initialisation and no alignment.  Four launches per call whatever T is, no host synchronisation: with a caller-owned
+ * workspace a call can be captured into a graph.  Errors as torbi_hip_forward_backward_band.
+ */
+int torbi_hip_forward_backward_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                int device);
+size_t torbi_hip_forward_backward_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_wide_band_tile(int B, int S, int reach_left, int reach_right, int device);
+int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                         const float *initial, int reach_left, int reach_right, float background,
+                                         float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                                         int B, int T, int S, int device, void *stream);
+
+/*
  * Expected counts on a band (added within ABI 17): torbi_hip_forward_backward_band on the same inputs, which writes
  * posterior_out and loglik_out bit for bit as that call does, and in addition the counts of
  * torbi_hip_forward_backward_counts inside the band, diagonal by diagonal, and the initial counts:

@@ -44,6 +44,7 @@
 #include "stream_posterior.hpp"
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
+#include "forward_backward_wide_band.hpp"
 #include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
 #include "counts.hpp"
@@ -2947,6 +2948,72 @@ int torbi_hip_forward_backward_band(const float *observation, const int32_t *bat
                            l.flag, posterior_out, loglik_out, ebg, l.reach_left, l.reach_right, l.W, l.Sd, B, T, S);
     });
     return (int)hipGetLastError();
+}
+
+// ---- forward-backward on a wide band (forward_backward_wide_band.hpp) ----
+
+// Items per workgroup of fb_wide_band_kernel<G>, from what was measured on the pitch matrix (POSTERIOR.md, "Wide band
+// route", the G rule): every workgroup re-reads the pack every frame, so a tile of 4 where the batch still gives every
+// compute unit a workgroup, and below that the largest tile that leaves no compute unit without one.
+static int fb_wide_band_tile(int B, const fbw::Plan &plan, int cus) {
+    return items_per_workgroup(fbw::kMaxGroup, B, 1, cus, [&](int G) { return fbw::lds_bytes(G, plan) <= (size_t)fbw::kMaxLdsBytes; });
+}
+
+int torbi_hip_forward_backward_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                int device) {
+    (void)device;
+    if (B < 1 || T < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    if (!background_ok(background)) return 0;
+    if (!fb_shape_in_range(B, T, S)) return 0;
+    const fbw::Plan plan = fbw::plan_of(S, reach_left, reach_right);
+    return plan.W <= fbw::kMaxWindow && fbw::lds_bytes(1, plan) <= (size_t)fbw::kMaxLdsBytes ? 1 : 0;
+}
+
+size_t torbi_hip_forward_backward_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbw::layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_wide_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return fb_wide_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
+}
+
+int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                         const float *initial, int reach_left, int reach_right, float background,
+                                         float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                                         int B, int T, int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && workspace,
+        torbi_hip_forward_backward_wide_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbw::Layout l = fbw::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const float ebg = exp_background(background);
+    hipError_t e;
+    if ((e = fbw::pack_and_verify(transition, l, ebg, background, S, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    int G = fb_wide_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_WIDE_BAND_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2 || g == 4) && fbw::lds_bytes(g, l) <= (size_t)fbw::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = fbw::lds_bytes(G, l);
+    e = by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbw::fb_wide_band_kernel<decltype(g)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(fbw::kThreads), lds, st, observation, batch_frames, initial, l.P[0],
+                           l.P[1], l.m, l.c, l.flag, posterior_out, loglik_out, ebg, static_cast<const fbw::Plan &>(l), B, T, S);
+        return hipGetLastError();
+    });
+    return (int)e;
 }
 
 // ---- expected counts on a band (counts_band.hpp) ----

@@ -8,7 +8,8 @@ For t < F_b (log space, A indexed [next, prev]):
     L_b = logsumexp_j log alpha_{F-1}[j]          gamma_t[j]     = exp(log alpha_t[j] + log beta_t[j] - L_b)
 
 The HIP route is csrc/forward_backward.hpp behind torbi_hip_forward_backward / _uniform (include/torbi_hip.h), and for a
-matrix that holds one value outside a band csrc/forward_backward_band.hpp behind torbi_hip_forward_backward_band;
+matrix that holds one value outside a band csrc/forward_backward_band.hpp behind torbi_hip_forward_backward_band (up to 64
+in-band entries) and csrc/forward_backward_wide_band.hpp behind torbi_hip_forward_backward_wide_band (up to 512);
 `gpu=None` runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and
 the numbers.
 """
@@ -177,7 +178,8 @@ def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[to
         (posterior (B, T, S) float32, log_likelihood (B,) float32) on the device; rows t >= F_b are 0
 
     Raises where the band route does not cover the call (torbi_hip_forward_backward_band_covers: up to 4096 states, at most
-    64 in-band entries in a matrix row, a background that is neither NaN nor +inf).
+    64 in-band entries in a matrix row, a background that is neither NaN nor +inf).  `forward_backward_wide_banded` takes
+    bands of up to 512 entries.
     """
     shape = _shapes('forward_backward_banded', observation, batch_frames, transition, initial)
     obs, frames, left, right, background = _banded_operands('forward_backward_banded', 'forward_backward', _covered, shape, (),
@@ -185,10 +187,64 @@ def forward_backward_banded(observation: torch.Tensor, batch_frames: Optional[to
     return _run_band(obs, frames, transition, initial, left, right, background, workspace)
 
 
+def forward_backward_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_wide_banded` needs for a (B, T, S) problem with this band."""
+    return int(_lib.load().torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
+
+
+def _wide_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_forward_backward_wide_band_covers: the wide band route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_forward_backward_wide_band_covers(B, T, S, int(reach_left), int(reach_right), background,
+                                                                        index))
+
+
+def _run_wide_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
+    """One call of the wide band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
+    `frames` there: (posterior, log_likelihood)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    return _lib.run('torbi_hip_forward_backward_wide_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
+                    ('torbi_hip_forward_backward_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
+                    workspace)
+
+
+def forward_backward_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                                 initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
+                                 workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_backward_banded` for a band of up to 512 entries, by a kernel of its own (POSTERIOR.md, "Wide band route").
+
+    Arguments, promise, outputs and non-finite rules are `forward_backward_banded`'s; the rounding differs.  `workspace`:
+    optional uint8 device tensor of >= `forward_backward_wide_banded_workspace_bytes(B, T, S, reach_left, reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_forward_backward_wide_band_covers: up to 4096 states,
+    reach_left + reach_right + 1 <= 512 after clamping to S - 1, a background that is neither NaN nor +inf).
+    """
+    shape = _shapes('forward_backward_wide_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands('forward_backward_wide_banded', 'forward_backward', _wide_covered,
+                                                            shape, (), observation, batch_frames, reach_left, reach_right,
+                                                            background)
+    return _run_wide_band(obs, frames, transition, initial, left, right, background, workspace)
+
+
+# Where 'auto' takes a band that only the wide route covers: the classes of (batch, band width as a share of the row) that
+# tools/posterior_wide_band_probe.py measured faster than the dense call on the same inputs, the wide route's slowest call
+# under the dense route's fastest (POSTERIOR.md, "Wide band route", measurements).  Each entry: (smallest batch, largest
+# batch, diagonals of 1440 states).  Measured at 500 frames x 1440 states on 175 diagonals, -inf and log(tiny) outside: 1, 8,
+# 64, 512 and 4096 items; the wide route won all ten (1.3 x at one item, 3.2 x at 512, 3.6 x at 4096).  A wider band or a
+# larger batch is not measured and stays dense.
+_AUTO_WIDE_BAND = ((1, 4096, 175),)
+
+
+def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
+               for low, high, diagonals in _AUTO_WIDE_BAND)
+
+
 def _band(route, trans, original, B, T, S, index):
     """(reach_left, reach_right, background) where `route` sends the device matrix `trans` (`inputs.device_matrix`; also
-    `original`, the tensor the look is remembered with) to the band route ('auto' takes every band
-    torbi_hip_forward_backward_band_covers takes), else None."""
+    `original`, the tensor the look is remembered with) to the NARROW band route alone ('auto' takes every band
+    torbi_hip_forward_backward_band_covers takes), else None.  `state_posteriors` asks `_band_run`, which knows both band
+    routes; this is the planner of the narrow one as tests/test_band_route_cpu.py holds it to the other features'."""
     if route == 'dense':
         return None
     plan = band_route.plan(trans, original, _covered, 'torbi_hip_forward_backward_band_covers', dict(batch=B, frames=T, states=S),
@@ -196,11 +252,29 @@ def _band(route, trans, original, B, T, S, index):
     return band_route.choose(route, *plan, None, "state_posteriors(route='band')")
 
 
+def _band_run(route, trans, original, B, T, S, index):
+    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix to a band route, else None.  One
+    plan over both routes' covers, so one look at the matrix.  A band torbi_hip_forward_backward_band_covers takes runs
+    `_run_band` under 'auto' and 'band', bit for bit as before there was a wide route; a band only
+    torbi_hip_forward_backward_wide_band_covers takes runs `_run_wide_band`, under 'band' always and under 'auto' in a class
+    of `_AUTO_WIDE_BAND`."""
+    if route == 'dense':
+        return None
+    either = lambda *call: _covered(*call) or _wide_covered(*call)
+    band, why = band_route.plan(trans, original, either, 'torbi_hip_forward_backward_wide_band_covers',
+                                dict(batch=B, frames=T, states=S), index)
+    narrow = band is not None and _covered(B, T, S, *band, index)
+    pays = None if narrow else lambda left, right, background: _wide_band_pays(B, S, left, right)
+    band = band_route.choose(route, band, why, pays, "state_posteriors(route='band')")
+    return None if band is None else (_run_band if narrow else _run_wide_band, band)
+
+
 def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
                     log_probs: bool = False) -> str:
     """The route `state_posteriors(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
     (batch, frames, states) observation: 'uniform' (no matrix: the closed form), 'band' (one value outside a band:
-    `forward_backward_banded`) or 'dense' (`forward_backward`)."""
+    `forward_backward_banded`, or `forward_backward_wide_banded` for a band beyond its 64 entries in a class that was
+    measured faster) or 'dense' (`forward_backward`)."""
     if transition is None:
         return 'uniform'
     if tuple(transition.shape) != (states, states):
@@ -209,7 +283,7 @@ def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int,
         return 'dense'
     device = inputs._compute_device(gpu)
     trans = inputs.device_matrix(transition, log_probs, device)
-    return 'dense' if _band('auto', trans, trans, int(batch), int(frames), states, device.index or 0) is None else 'band'
+    return 'dense' if _band_run('auto', trans, trans, int(batch), int(frames), states, device.index or 0) is None else 'band'
 
 
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
@@ -243,9 +317,10 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     if gpu is None:
         gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
         return gamma.to(torch.float32), L.to(torch.float32)
-    band = None if uniform is not None else _band(route, transition, transition, B, T, S, device.index or 0)
+    band = None if uniform is not None else _band_run(route, transition, transition, B, T, S, device.index or 0)
     if band is not None:
-        return _run_band(obs, frames, transition, initial, *band)
+        run, band = band
+        return run(obs, frames, transition, initial, *band)
     return _run(obs, frames, transition, uniform, initial)
 
 

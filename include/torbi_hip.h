@@ -744,6 +744,35 @@ int torbi_hip_forward_backward_counts_band(const float *observation, const int32
                                            size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
 /*
+ * Expected counts on a wide band (added within ABI 17): torbi_hip_forward_backward_counts_band's arguments, outputs, skipping
+ * rule, broken-promise rule and in-band-only rule for a finite background, for every band
+ * torbi_hip_forward_backward_wide_band covers (csrc/counts_wide_band.hpp).  posterior_out and loglik_out are bit for bit
+ * those of torbi_hip_forward_backward_wide_band on the same inputs.  The passes' launch also stores two operand rows per
+ * (item, frame), w_t and a_t g_b / c_t, and one launch on the f32 matrix pipe sums their banded outer products: a workgroup
+ * owns 64 next states, a window of 256 prev states and one of KS contiguous shares of the (item, frame) rows, KS =
+ * _shares(B, T, S, reach_left, reach_right), a function of the shape alone (0 for arguments out of range); the shares are
+ * added in order.  The bits depend on the inputs and the shape only (and, for posterior_out, on nothing else either); no
+ * float atomics.
+ *
+ * _covers: what torbi_hip_forward_backward_wide_band_covers answers.  It, _workspace_size and _shares answer without a
+ * device.  workspace: torbi_hip_forward_backward_counts_wide_band_workspace_size(...) bytes (256 for arguments out of range),
+ * no initialisation and no alignment: the wide route's regions, then the operand rows Wop and Aop, B x T x (S up to 4) fp32
+ * each -- together twice the posterior output; a caller short of memory splits the batch, the counts are additive over
+ * items --, then KS planes of S x W fp32, every region starting on a multiple of 256 bytes.
+ * Seven launches per call whatever T is, no host synchronisation: with a caller-owned workspace a call can be captured into a
+ * graph.  Errors as torbi_hip_forward_backward_counts_band.
+ */
+int torbi_hip_forward_backward_counts_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                       int device);
+size_t torbi_hip_forward_backward_counts_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_counts_wide_band_shares(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_counts_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                                const float *initial, int reach_left, int reach_right, float background,
+                                                const float *item_weights, float *posterior_out, float *loglik_out,
+                                                float *band_counts_out, float *initial_counts_out, void *workspace,
+                                                size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
+/*
  * k-best Viterbi decoding (added within ABI 17): the k best state sequences of every item with their exact scores, on the
  * model torbi_hip_viterbi_decode decodes (torbi_amd/k_best.py, KBEST.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log; 1 <= k <= 32.

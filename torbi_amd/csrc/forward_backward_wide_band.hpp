@@ -33,6 +33,10 @@
 // The order of every sum of an item is fixed by (S, band) alone: dquads ascending and diagonals ascending within a slice,
 // slices ascending, then fb_band_kernel's butterflies.  An item's bits depend neither on G nor on its tile nor on the batch.
 // No float atomics, vector stores only, nothing waits across workgroups.
+//
+// The body of the launch is wide_passes<G, COUNTS>.  fb_wide_band_kernel<G> is its `false` arm.  The `true` arm,
+// fb_wide_band_operands_kernel<G>, also leaves the two factors of every pair of the expected counts in the workspace
+// (counts_wide_band.hpp); it is a second kernel, by counts_band.hpp's reasoning: the posterior route keeps its instances.
 #pragma once
 
 #include "forward_backward_band.hpp"
@@ -55,8 +59,10 @@ constexpr int kBlockStates = 256;            // states of a wave: 64 lanes x 4
 // ISA: none.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FBW_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
+#define FBW_INLINE __device__ __forceinline__ __attribute__((target("no-packed-fp32-ops")))
 #else
 #define FBW_KERNEL __global__
+#define FBW_INLINE __device__ __forceinline__
 #endif
 
 // (__syncthreads, spelled out: a function of another target is not inlined into these kernels unless it is forced)
@@ -237,15 +243,15 @@ __device__ __forceinline__ void band_phase(const Tile<G> &tile, const Plan &p, i
         *reinterpret_cast<f4 *>(tile.slice + ((size_t)sl * G + g) * p.S4 + x0) = f4{acc[g][0], acc[g][1], acc[g][2], acc[g][3]};
 }
 
-// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, plan) ----
-template <int G>
-FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
-                                                                const float *__restrict__ initial, const float *__restrict__ Pf,
-                                                                const float *__restrict__ Pb, const float *__restrict__ m,
-                                                                float *__restrict__ cbuf, const int32_t *__restrict__ flag,
-                                                                float *__restrict__ post, float *__restrict__ loglik, float ebg,
-                                                                Plan p, int B, int T, int S) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+// ---- both passes of G items of one workgroup, the body of the two kernels below.  COUNTS (counts_wide_band.hpp): backward
+// phase B also stores the two operand rows of the counts, Wop[b][t][j] = w_t[j] and Aop[b][t][j] = a_t[j] * (g_b / c_t), rows
+// of S4 floats; `false` is the posterior kernel as it was, and nothing of `true` touches a value `false` computes ----
+template <int G, bool COUNTS>
+FBW_INLINE void wide_passes(unsigned char *lds_raw, const float *__restrict__ obs, const int32_t *__restrict__ frames,
+                            const float *__restrict__ initial, const float *__restrict__ Pf, const float *__restrict__ Pb,
+                            const float *__restrict__ m, float *__restrict__ cbuf, const int32_t *__restrict__ flag,
+                            const float *__restrict__ weights, float *__restrict__ post, float *__restrict__ loglik,
+                            float *__restrict__ Wop, float *__restrict__ Aop, float ebg, const Plan &p, int B, int T, int S) {
     constexpr int kEarly = early_states(G);
     Tile<G> tile(lds_raw, p, S);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -341,12 +347,13 @@ FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_kernel(const float *__r
     float *const cur = rows + p.left4[1];
     for (int t = Fmax - 1; t >= 0; --t) {
         const bool step = t < Fmax - 1;
-        float mt[G], ct[G], early_o[kEarly > 0 ? kEarly : 1][G], early_a[kEarly > 0 ? kEarly : 1][G];
+        float mt[G], ct[G], gc[COUNTS ? G : 1], early_o[kEarly > 0 ? kEarly : 1][G], early_a[kEarly > 0 ? kEarly : 1][G];
         auto scalars = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
                 ct[g] = t < F[g] ? cbuf[(size_t)(b0 + g) * T + t] : 1.f;
+                if (COUNTS) gc[g] = (weights && b0 + g < B ? weights[b0 + g] : 1.f) / ct[g];
             }
         };
         if (kEarly > 0) scalars();
@@ -385,6 +392,11 @@ FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_kernel(const float *__r
                 }
                 const float w = (expf(o - mm) * beta) / c;               // (w_0 is never read)
                 post[at_j] = isfinite(tile.Ls[g]) ? (a * beta) / c : NAN;
+                if (COUNTS) {
+                    const size_t at_c = ((size_t)(b0 + g) * T + t) * S4 + j;
+                    Wop[at_c] = w;
+                    Aop[at_c] = a * gc[g];
+                }
                 cur[g * stride + j] = w;
                 acc[g] += w;
             }
@@ -405,6 +417,31 @@ FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_kernel(const float *__r
     }
 }
 
+// ---- the posteriors: grid ceil(B / G), dynamic LDS lds_bytes(G, plan) ----
+template <int G>
+FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
+                                                                const float *__restrict__ initial, const float *__restrict__ Pf,
+                                                                const float *__restrict__ Pb, const float *__restrict__ m,
+                                                                float *__restrict__ cbuf, const int32_t *__restrict__ flag,
+                                                                float *__restrict__ post, float *__restrict__ loglik, float ebg,
+                                                                Plan p, int B, int T, int S) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    wide_passes<G, false>(lds_raw, obs, frames, initial, Pf, Pb, m, cbuf, flag, nullptr, post, loglik, nullptr, nullptr, ebg, p, B,
+                          T, S);
+}
+
+// ---- the posteriors and the operand rows of the counts: the same grid and LDS ----
+template <int G>
+FBW_KERNEL __launch_bounds__(kThreads) void fb_wide_band_operands_kernel(
+    const float *__restrict__ obs, const int32_t *__restrict__ frames, const float *__restrict__ initial,
+    const float *__restrict__ Pf, const float *__restrict__ Pb, const float *__restrict__ m, float *__restrict__ cbuf,
+    const int32_t *__restrict__ flag, const float *__restrict__ weights, float *__restrict__ post, float *__restrict__ loglik,
+    float *__restrict__ Wop, float *__restrict__ Aop, float ebg, Plan p, int B, int T, int S) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    wide_passes<G, true>(lds_raw, obs, frames, initial, Pf, Pb, m, cbuf, flag, weights, post, loglik, Wop, Aop, ebg, p, B, T, S);
+}
+
 #undef FBW_KERNEL
+#undef FBW_INLINE
 
 }  // namespace fbw

@@ -47,6 +47,7 @@
 #include "forward_backward_wide_band.hpp"
 #include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
+#include "counts_wide_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
 #include "k_best_band.hpp"
@@ -2979,6 +2980,44 @@ int torbi_hip_forward_backward_wide_band_tile(int B, int S, int reach_left, int 
     return fb_wide_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
 }
 
+// What both wide entries launch: the pack with the check of the promise, the row maxima, then both passes of every item in
+// one launch.  With `Wop` and `Aop` (the counts entry) the instance that also stores the operand rows of the counts.
+static hipError_t fb_wide_band_passes(const fbw::Layout &l, const float *observation, const int32_t *batch_frames,
+                                      const float *transition, const float *initial, float background, const float *item_weights,
+                                      float *posterior_out, float *loglik_out, float *Wop, float *Aop, int B, int T, int S,
+                                      int device, hipStream_t st) {
+    const float ebg = exp_background(background);
+    hipError_t e;
+    if ((e = fbw::pack_and_verify(transition, l, ebg, background, S, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    int G = fb_wide_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_WIDE_BAND_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2 || g == 4) && fbw::lds_bytes(g, l) <= (size_t)fbw::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = fbw::lds_bytes(G, l);
+    const dim3 grid((B + G - 1) / G), block(fbw::kThreads);
+    const fbw::Plan &plan = l;
+    return by_value<4, 2, 1>(G, [&](auto g) {
+        if (Wop) {
+            auto *kernel = &fbw::fb_wide_band_operands_kernel<decltype(g)::value>;
+            const hipError_t le = ensure_dynamic_lds(kernel, lds);
+            if (le != hipSuccess) return le;
+            hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, initial, l.P[0], l.P[1], l.m, l.c, l.flag,
+                               item_weights, posterior_out, loglik_out, Wop, Aop, ebg, plan, B, T, S);
+        } else {
+            auto *kernel = &fbw::fb_wide_band_kernel<decltype(g)::value>;
+            const hipError_t le = ensure_dynamic_lds(kernel, lds);
+            if (le != hipSuccess) return le;
+            hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, initial, l.P[0], l.P[1], l.m, l.c, l.flag,
+                               posterior_out, loglik_out, ebg, plan, B, T, S);
+        }
+        return hipGetLastError();
+    });
+}
+
 int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
                                          const float *initial, int reach_left, int reach_right, float background,
                                          float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
@@ -2989,31 +3028,61 @@ int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t
         torbi_hip_forward_backward_wide_band_covers(B, T, S, reach_left, reach_right, background, device),
         torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
     if (rc != TORBI_HIP_OK || B == 0) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
     const fbw::Layout l = fbw::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
     const DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
-    const float ebg = exp_background(background);
-    hipError_t e;
-    if ((e = fbw::pack_and_verify(transition, l, ebg, background, S, st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, l.m, B, T, S);
+    return (int)fb_wide_band_passes(l, observation, batch_frames, transition, initial, background, nullptr, posterior_out,
+                                    loglik_out, nullptr, nullptr, B, T, S, device, static_cast<hipStream_t>(stream));
+}
+
+// ---- expected counts on a wide band (counts_wide_band.hpp) ----
+
+int torbi_hip_forward_backward_counts_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                       int device) {
+    return torbi_hip_forward_backward_wide_band_covers(B, T, S, reach_left, reach_right, background, device);
+}
+
+size_t torbi_hip_forward_backward_counts_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbw::counts_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_counts_wide_band_shares(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return fbw::counts_plan(B, T, S, fbw::plan_of(S, reach_left, reach_right)).shares;
+}
+
+int torbi_hip_forward_backward_counts_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                                const float *initial, int reach_left, int reach_right, float background,
+                                                const float *item_weights, float *posterior_out, float *loglik_out,
+                                                float *band_counts_out, float *initial_counts_out, void *workspace,
+                                                size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && band_counts_out &&
+            initial_counts_out && workspace,
+        torbi_hip_forward_backward_counts_wide_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_counts_wide_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbw::CountsLayout l = fbw::counts_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    hipError_t e = fb_wide_band_passes(l, observation, batch_frames, transition, initial, background, item_weights, posterior_out,
+                                       loglik_out, l.Wop, l.Aop, B, T, S, device, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_initial_counts_kernel, dim3((S + 255) / 256), dim3(256), 0, st, item_weights, loglik_out,
+                       posterior_out, initial_counts_out, B, T, S);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    int G = fb_wide_band_tile(B, l, cu_count(device));
-    if (const char *forced = getenv("TORBI_HIP_WIDE_BAND_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per G)
-        const int g = atoi(forced);
-        if ((g == 1 || g == 2 || g == 4) && fbw::lds_bytes(g, l) <= (size_t)fbw::kMaxLdsBytes) G = g;
-    }
-    const size_t lds = fbw::lds_bytes(G, l);
-    e = by_value<4, 2, 1>(G, [&](auto g) {
-        auto *kernel = &fbw::fb_wide_band_kernel<decltype(g)::value>;
-        const hipError_t le = ensure_dynamic_lds(kernel, lds);
-        if (le != hipSuccess) return le;
-        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(fbw::kThreads), lds, st, observation, batch_frames, initial, l.P[0],
-                           l.P[1], l.m, l.c, l.flag, posterior_out, loglik_out, ebg, static_cast<const fbw::Plan &>(l), B, T, S);
-        return hipGetLastError();
-    });
-    return (int)e;
+    if ((e = ensure_dynamic_lds(&fbw::fb_wide_counts_kernel, fbw::kCountsLdsBytes)) != hipSuccess) return (int)e;
+    const fbw::CountsPlan &c = l.counts;
+    hipLaunchKernelGGL(fbw::fb_wide_counts_kernel, dim3((unsigned)(c.jblocks * c.chunks * c.shares)), dim3(fbw::kCountsThreads),
+                       fbw::kCountsLdsBytes, st, batch_frames, item_weights, loglik_out, l.Wop, l.Aop, l.partial, c, l.reach_left,
+                       l.reach_right, l.W, l.S4, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fbw::fb_wide_counts_finalize_kernel, dim3((unsigned)(((size_t)l.W * S + 255) / 256)), dim3(256), 0, st,
+                       transition, l.partial, l.flag, band_counts_out, initial_counts_out, c.shares, l.reach_left, l.W, S);
+    return (int)hipGetLastError();
 }
 
 // ---- expected counts on a band (counts_band.hpp) ----

@@ -208,6 +208,18 @@ def _run_wide_band(observation, frames, transition, initial, reach_left, reach_r
                     workspace)
 
 
+def _run_wide_band_counts(observation, frames, transition, initial, reach_left, reach_right, background, item_weights=None,
+                          workspace=None):
+    """`_run_band_counts` on the wide route (torbi_hip_forward_backward_counts_wide_band)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    W = min(reach_left, S - 1) + min(reach_right, S - 1) + 1
+    return _lib.run('torbi_hip_forward_backward_counts_wide_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background, item_weights),
+                    _outputs(B, T, S, observation.device, W),
+                    ('torbi_hip_forward_backward_counts_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
+                    workspace)
+
+
 def forward_backward_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
                                  initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
                                  workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:

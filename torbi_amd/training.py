@@ -10,8 +10,10 @@ so `log_likelihood(...).sum().backward()` gives gamma, X and I, and one Baum-Wel
 states of one previous state).  The HIP route is csrc/counts.hpp behind torbi_hip_forward_backward_counts
 (include/torbi_hip.h), fed by the passes of `forward_backward`, and for a matrix that is -inf outside a band
 csrc/counts_band.hpp behind torbi_hip_forward_backward_counts_band, which gathers the counts of the band's diagonals inside
-the one launch of `forward_backward_banded`; `gpu=None` and CPU tensors run the same scaled recurrence in float64 with torch
-CPU ops.  POSTERIOR.md ("Expected counts", "Band counts") has the contract, the kernels and the numbers.
+the one launch of `forward_backward_banded`, and for a band beyond its reach (up to 512 entries) csrc/counts_wide_band.hpp
+behind torbi_hip_forward_backward_counts_wide_band, a banded rank-K update on the matrix pipe fed by the one launch of
+`forward_backward_wide_banded`; `gpu=None` and CPU tensors run the same scaled recurrence in float64 with torch CPU ops.
+POSTERIOR.md ("Expected counts", "Band counts", "Wide band counts") has the contract, the kernels and the numbers.
 """
 import math
 from typing import Optional, Tuple
@@ -19,7 +21,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib, band_route, inputs
-from .posterior import _banded_operands, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts, _shapes
+from .posterior import (_banded_operands, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts, _run_wide_band,
+                        _run_wide_band_counts, _shapes)
 
 ROUTES = band_route.ROUTES
 
@@ -89,6 +92,45 @@ def forward_backward_counts_banded(observation: torch.Tensor, batch_frames: Opti
     return _run_band_counts(obs, frames, transition, initial, left, right, background, item_weights, workspace)
 
 
+def expected_counts_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_counts_wide_banded` needs for a (B, T, S) problem with this band: what
+    `forward_backward_wide_banded` needs, two regions of B x T x (S up to 4) float32 (together twice the posterior the call
+    returns) and the partial planes of the K shares, S x W float32 each."""
+    return int(_lib.load().torbi_hip_forward_backward_counts_wide_band_workspace_size(B, T, S, int(reach_left),
+                                                                                      int(reach_right)))
+
+
+def forward_backward_counts_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor],
+                                        transition: torch.Tensor, initial: torch.Tensor, reach_left: int, reach_right: int,
+                                        background: float = -math.inf, item_weights: Optional[torch.Tensor] = None,
+                                        workspace: Optional[torch.Tensor] = None):
+    """`forward_backward_counts_banded` for a band of up to 512 entries, by kernels of its own (POSTERIOR.md, "Wide band
+    counts"): the launch of `forward_backward_wide_banded` also stores two operand rows per (item, frame), and a banded
+    rank-K update on the matrix pipe sums their outer products.
+
+    Arguments, promise, outputs, the skipping rule and the in-band-only rule for a finite background are
+    `forward_backward_counts_banded`'s; posterior and log_likelihood are bit for bit those of `forward_backward_wide_banded`;
+    the counts' rounding differs from the other routes'.  `workspace`: optional uint8 device tensor of >=
+    `expected_counts_wide_banded_workspace_bytes(B, T, S, reach_left, reach_right)` bytes (then the call allocates nothing but
+    its outputs and can be captured into a graph).  The operand rows take twice the bytes of the posterior: a caller short
+    of memory splits the batch and adds the counts, which are additive over items.
+
+    Raises where the route does not cover the call (torbi_hip_forward_backward_counts_wide_band_covers: what
+    `forward_backward_wide_banded` covers, narrow bands included).
+    """
+    shape = _shapes('forward_backward_counts_wide_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands(
+        'forward_backward_counts_wide_banded', 'forward_backward_counts', _wide_counts_covered, shape, (), observation,
+        batch_frames, reach_left, reach_right, background, item_weights)
+    return _run_wide_band_counts(obs, frames, transition, initial, left, right, background, item_weights, workspace)
+
+
+def _wide_counts_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_forward_backward_counts_wide_band_covers: the wide band counts route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_forward_backward_counts_wide_band_covers(B, T, S, int(reach_left), int(reach_right),
+                                                                               background, index))
+
+
 def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right: int) -> torch.Tensor:
     """The (S, S) matrix [next, prev] of the (W, S) `band_counts` of `forward_backward_counts_banded`: dense[j, j - reach_left
     + k] = band_counts[k, j], zeros outside the band.  On the tensor's device."""
@@ -105,36 +147,64 @@ def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right
     return dense
 
 
-# The classes of (items, diagonals) route='auto' sends to the band counts route; route='band' takes whatever is covered.
-# Measured on the pitch band (W = 23 at 1440 states, close to the largest plane that is covered) at 1, 8 and 512 items, the
-# band route beat the dense one 3.0 to 8.1 times with a spread below 2.2 % (POSTERIOR.md "Band counts"), so no class is
-# excluded; one that is found to lose goes here, as a function of (reach_left, reach_right, background).
-_auto_takes = None
+# The classes of (items, diagonals) route='auto' sends to a band counts route; route='band' takes whatever is covered.
+# A band of at most 64 entries (the narrow route, where its plane fits): measured on the pitch band (W = 23 at 1440 states,
+# close to the largest plane that is covered) at 1, 8 and 512 items, the band route beat the dense one 3.0 to 8.1 times with
+# a spread below 2.2 % (POSTERIOR.md "Band counts"), so no class is excluded.
+# A wider band (the wide route): the classes tools/counts_wide_band_probe.py measured faster than the dense call on the same
+# inputs, the wide route's slowest call under the dense route's fastest (POSTERIOR.md, "Wide band counts", measurements).
+# Each entry: (smallest batch, largest batch, diagonals of 1440 states), `posterior._AUTO_WIDE_BAND`'s form.  Measured at 500
+# frames x 1440 states on 175 diagonals, -inf outside: 1, 8, 64, 512 and 4096 items; the wide route won all five (1.7 x at one
+# item, 3.6 x at 512 and at 4096).  A wider band or a larger batch is not measured and stays dense.
+_AUTO_WIDE_COUNTS = ((1, 4096, 175),)
+_NARROW_ENTRIES = 64                              # in-band entries of a row the narrow band routes take
+
+
+def _is_wide(S, reach_left, reach_right) -> bool:
+    """The band has more in-band entries in a row than the narrow routes take: its counts are the wide route's."""
+    return min(min(reach_left, S - 1) + min(reach_right, S - 1) + 1, S) > _NARROW_ENTRIES
+
+
+def _band_runs(S, reach_left, reach_right):
+    """(posteriors, counts): the `_run_*` pair of the route that takes this band."""
+    return (_run_wide_band, _run_wide_band_counts) if _is_wide(S, reach_left, reach_right) else (_run_band, _run_band_counts)
 
 
 def _counts_band(trans, original, B, T, S, index, route):
     """(reach_left, reach_right) when `route` sends the counts of the device matrix `trans` (`inputs.plain_matrix`;
-    `original`: the tensor the look is remembered with) to the band route, else None: the matrix is -inf outside a band (so
-    the dense (S, S) result is exactly zero there),
-    torbi_hip_forward_backward_counts_band_covers takes it and, for 'auto', the class was measured faster."""
+    `original`: the tensor the look is remembered with) to a band route, else None: the matrix is -inf outside a band (so
+    the dense (S, S) result is exactly zero there), the band's route covers it -- torbi_hip_forward_backward_counts_band_covers
+    for at most 64 in-band entries, torbi_hip_forward_backward_counts_wide_band_covers for more (`_band_runs` says which) --
+    and, for 'auto', the class was measured faster."""
     if route == 'dense':
         return None
     plan = band_route.plan(trans, original, _counts_take,
-                           'the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers)',
+                           'the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers up to 64 '
+                           'in-band entries, torbi_hip_forward_backward_counts_wide_band_covers beyond)',
                            dict(batch=B, frames=T, states=S), index)
-    band = band_route.choose(route, *plan, _auto_takes, "route='band'")
+    band = band_route.choose(route, *plan, lambda left, right, background: _auto_takes(B, S, left, right), "route='band'")
     return None if band is None else band[:2]
 
 
+def _auto_takes(batch, states, reach_left, reach_right) -> bool:
+    if not _is_wide(states, reach_left, reach_right):
+        return True
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
+               for low, high, diagonals in _AUTO_WIDE_COUNTS)
+
+
 def _counts_take(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    return background == -math.inf and _counts_covered(B, T, S, reach_left, reach_right, background, index)
+    if background != -math.inf:
+        return False
+    covers = _wide_counts_covered if _is_wide(S, reach_left, reach_right) else _counts_covered
+    return covers(B, T, S, reach_left, reach_right, background, index)
 
 
 def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
                  log_probs: bool = False) -> str:
     """The route `expected_counts(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
-    (batch, frames, states) observation: 'band' (`forward_backward_counts_banded`) or 'dense'
-    (`forward_backward_counts`)."""
+    (batch, frames, states) observation: 'band' (`forward_backward_counts_banded`, or `forward_backward_counts_wide_banded`
+    for a band beyond its 64 entries in a class that was measured faster) or 'dense' (`forward_backward_counts`)."""
     if transition is None:
         return 'dense'
     if tuple(transition.shape) != (states, states):
@@ -157,9 +227,11 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     `transition=None` runs the dense route on a matrix filled with fl(log(1/S)).  `gpu` is a HIP device index; None
     computes in float64 on the CPU.  An item whose log-likelihood is not finite adds nothing to the counts.
 
-    route: which device route a given matrix takes.  'auto': the band route where the matrix is -inf outside a band that
-        `forward_backward_counts_banded` covers (`counts_route` answers which), else the dense one; 'dense': always the
-        dense route; 'band': the band route, raising where auto would go dense.  The result is the same (S, S) matrix
+    route: which device route a given matrix takes.  'auto': a band route where the matrix is -inf outside a band that
+        `forward_backward_counts_banded` covers (at most 64 in-band entries) or, in the classes that were measured faster,
+        a wider one that `forward_backward_counts_wide_banded` covers (`counts_route` answers which), else the dense one;
+        'dense': always the dense route; 'band': the band route, raising where the matrix has no such band (a band of at
+        most 64 entries whose plane does not fit raises too).  The result is the same (S, S) matrix
         either way, exactly zero outside the band; the roundings differ.  Ignored by `gpu=None`.  'auto' and 'band' look at
         the matrix (`viterbi.band_over`: one small kernel and a host synchronisation the first time a tensor version is
         seen, for a dense matrix too when S % 4 == 0 and 64 <= S <= 3072); 'dense' does not.
@@ -188,7 +260,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     else:
         band = _counts_band(transition, transition, B, T, S, device.index or 0, route)
     if band is not None:
-        _, L, Xb, I = _run_band_counts(obs, frames, transition, initial, band[0], band[1], -math.inf)
+        _, L, Xb, I = _band_runs(S, *band)[1](obs, frames, transition, initial, band[0], band[1], -math.inf)
         return band_counts_to_dense(Xb, band[0], band[1]), I, L
     _, L, X, I = _run(obs, frames, transition, None, initial, counts=True)
     return X, I, L
@@ -215,7 +287,7 @@ class _LogLikelihood(torch.autograd.Function):
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
             ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
             if ctx.band is not None:
-                gamma, L = _run_band(obs, frames, trans, init, ctx.band[0], ctx.band[1], -math.inf)
+                gamma, L = _band_runs(S, *ctx.band)[0](obs, frames, trans, init, ctx.band[0], ctx.band[1], -math.inf)
             else:
                 gamma, L = _run(obs, frames, trans, None, init)
             ctx.save_for_backward(obs, frames, trans, init, gamma, L)
@@ -239,7 +311,8 @@ class _LogLikelihood(torch.autograd.Function):
             if need_t:
                 if ctx.band is not None:
                     left, right = ctx.band
-                    _, _, Xb, I = _run_band_counts(obs, frames, trans, init, left, right, -math.inf, g.contiguous())
+                    _, _, Xb, I = _band_runs(trans.shape[0], left, right)[1](obs, frames, trans, init, left, right, -math.inf,
+                                                                             g.contiguous())
                     X = band_counts_to_dense(Xb, left, right)
                 elif obs.is_cuda:
                     _, _, X, I = _run(obs, frames, trans, None, init, counts=True, item_weights=g.contiguous())
@@ -273,8 +346,8 @@ def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tenso
     with g_b != 0 makes the transition and initial gradients NaN.  First order only.
 
     route: as `expected_counts` -- where a device matrix is -inf outside a band the band routes cover, 'auto' and 'band'
-    make the forward one `forward_backward_banded` call and the backward one `forward_backward_counts_banded` call (the
-    transition gradient is the (S, S) matrix either way, zero outside the band).  Ignored by CPU tensors.  'auto' and 'band'
+    make the forward one `forward_backward_banded` call and the backward one `forward_backward_counts_banded` call, or their
+    `_wide_banded` siblings for a band of more than 64 entries (the transition gradient is the (S, S) matrix either way, zero outside the band).  Ignored by CPU tensors.  'auto' and 'band'
     look at the matrix in the forward (`viterbi.band_over`: one small kernel and a host synchronisation per new tensor
     version, so once per step of a training loop that updates the matrix); `route='dense'` keeps the forward free of
     host synchronisation.

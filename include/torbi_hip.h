@@ -1064,6 +1064,36 @@ int torbi_hip_path_entropy_band(const float *observation, const int32_t *batch_f
                                 float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T, int S,
                                 int device, void *stream);
 
+/*
+ * Wide band route of path entropy (added within ABI 17; torbi_amd/entropy.py forward_entropy_wide_banded, ENTROPY.md "Wide
+ * band route"): torbi_hip_path_entropy_band's quantities, contract, promise, deferred division and non-finite rules for a
+ * band of up to 512 entries, by a kernel of its own (csrc/path_entropy_wide_band.hpp: E - ebg and G - gbg packed once per
+ * call in the order the lanes read them, a lane owning 4 states x the items of its tile, the rows a_t and v_t in LDS as two
+ * float rows read in aligned 16-byte pieces).  The reductions are torbi_hip_path_entropy_band's; the rounding of the band sums
+ * differs from both other routes', within the same bound.  An item's bits do not depend on how many items share its
+ * workgroup, nor on the batch.
+ *
+ * torbi_hip_path_entropy_wide_band_covers reads no device and answers 1 for 1 <= S <= 4096,
+ * reach_left + reach_right + 1 <= 512 with the reaches clamped to S - 1 (narrow bands included), a background that is
+ * neither NaN nor +inf, B >= 1, T >= 1 within torbi_hip_path_entropy's limits, and one item's rows and slice sums within the
+ * LDS of a compute unit; else 0.  _tile: the items per workgroup a call of B items takes on `device` (1 or 2; 0 for arguments
+ * out of range).  The environment variable TORBI_HIP_WIDE_BAND_ITEMS (1 or 2, where the tile fits the LDS) overrides that
+ * choice for a call; results do not depend on it (tools/path_entropy_wide_band_probe.py times every tile).
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_path_entropy_wide_band_workspace_size bytes: both
+ * packs [256-state blocks][dquads][4 KiB], three scalars per item and frame (row maxima, row sums, the prefix where
+ * prefix_out is null) and the promise flag.  It holds no (B, T, S) region.  The size query answers 256 for dimensions below
+ * 1, a negative reach or S > 4096.
+ * Four launches whatever T, no allocation and no host synchronisation: a call can be captured into a graph.  Errors as
+ * torbi_hip_path_entropy_band, in its order and all before a device is touched.  B == 0 launches nothing and returns 0.
+ */
+int torbi_hip_path_entropy_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_path_entropy_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_path_entropy_wide_band_tile(int B, int S, int reach_left, int reach_right, int device);
+int torbi_hip_path_entropy_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                     const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                     float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                                     int S, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

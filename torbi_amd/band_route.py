@@ -43,8 +43,9 @@ def plan(trans: torch.Tensor, original: torch.Tensor, covers, entry: str, shape:
     the caller's tensor, which the look is remembered with), else (None, the reason).  The structure is what
     `viterbi.band_over` answers -- one look per tensor version; an unseen matrix while a stream is capturing has no band --,
     the shape what the feature's `covers(*shape.values(), reach_left, reach_right, background, index)` takes.  `shape` is the
-    call in the order of that function, batch=, states= and what else it asks about; `entry` names the function and `finite`
-    says what a finite background has to be, both for the reason.  Without `look` only a structure that is already known
+    call in the order of that function, batch=, states= and what else it asks about; `entry` names the function (or is a
+    callable that names it for the band found, where `covers` asks one of two routes) and `finite` says what a finite
+    background has to be, both for the reason.  Without `look` only a structure that is already known
     counts: the look is a small kernel, a host synchronisation and, the first time, a device allocation."""
     states = shape['states']
     if shape['batch'] < 1:
@@ -60,7 +61,8 @@ def plan(trans: torch.Tensor, original: torch.Tensor, covers, entry: str, shape:
                       f'{viterbi.BAND_MAX_WINDOW}, a background that is -inf or {finite})')
     if not covers(*shape.values(), *over, index):
         asked = ', '.join(f'{name}={value}' for name, value in shape.items())
-        return None, f'{entry} turns down {asked}, reach {over[0]}/{over[1]}, background {over[2]}'
+        name = entry(*over) if callable(entry) else entry
+        return None, f'{name} turns down {asked}, reach {over[0]}/{over[1]}, background {over[2]}'
     return over, ''
 
 

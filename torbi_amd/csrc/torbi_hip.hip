@@ -58,6 +58,7 @@
 #include "path_statistics.hpp"
 #include "path_entropy.hpp"
 #include "path_entropy_band.hpp"
+#include "path_entropy_wide_band.hpp"
 
 namespace {
 
@@ -3693,6 +3694,71 @@ int torbi_hip_path_entropy_band(const float *observation, const int32_t *batch_f
         hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(peb::kThreads), lds, st, observation, batch_frames, initial, l.Df,
                            l.Dg, l.m, l.c, l.flag, prefix, entropy_out, loglik_out, ebg, gbg, l.reach_left, l.reach_right, l.W,
                            l.Sd, B, T, S);
+        return hipGetLastError();
+    });
+    return (int)e;
+}
+
+// ---- path entropy on a wide band (path_entropy_wide_band.hpp) ----
+
+// Items per workgroup of pe_wide_band_kernel<G>: fb_wide_band_tile's rule with this kernel's rows and slices.
+static int pe_wide_band_tile(int B, const fbw::Plan &plan, int cus) {
+    return items_per_workgroup(pew::kMaxGroup, B, 1, cus, [&](int G) { return pew::lds_bytes(G, plan) <= (size_t)pew::kMaxLdsBytes; });
+}
+
+int torbi_hip_path_entropy_wide_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device) {
+    (void)device;
+    if (B < 1 || T < 1 || S < 1 || S > pew::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    if (!background_ok(background)) return 0;
+    if (!fb_shape_in_range(B, T, S)) return 0;
+    const fbw::Plan plan = fbw::plan_of(S, reach_left, reach_right);
+    return plan.W <= pew::kMaxWindow && pew::lds_bytes(1, plan) <= (size_t)pew::kMaxLdsBytes ? 1 : 0;
+}
+
+size_t torbi_hip_path_entropy_wide_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > pew::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return pew::layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_path_entropy_wide_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || S > pew::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return pe_wide_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
+}
+
+int torbi_hip_path_entropy_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                     const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                     float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                                     int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && entropy_out && loglik_out && workspace,
+        torbi_hip_path_entropy_wide_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_path_entropy_wide_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const pew::Layout l = pew::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const float ebg = exp_background(background), gbg = background == -INFINITY ? 0.f : ebg * background;
+    hipError_t e;
+    if ((e = pew::pack_and_verify(transition, l, ebg, gbg, background, S, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    int G = pe_wide_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_WIDE_BAND_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2) && pew::lds_bytes(g, l) <= (size_t)pew::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = pew::lds_bytes(G, l);
+    float *const prefix = prefix_out ? prefix_out : l.prefix;
+    const fbw::Plan &plan = l;
+    e = by_value<2, 1>(G, [&](auto g) {
+        auto *kernel = &pew::pe_wide_band_kernel<decltype(g)::value>;
+        const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+        if (granted != hipSuccess) return granted;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(pew::kThreads), lds, st, observation, batch_frames, initial, l.Pf,
+                           l.Pg, l.m, l.c, l.flag, prefix, entropy_out, loglik_out, ebg, gbg, plan, B, T, S);
         return hipGetLastError();
     });
     return (int)e;

@@ -21,8 +21,10 @@ log-likelihood -inf and the same NaNs.  Prefix entries t >= F are 0.  `transitio
 independent: prefix_t is the running sum of the entropies of softmax(o_s), with pi + o_0 at s = 0.
 
 The HIP route is csrc/path_entropy.hpp behind torbi_hip_path_entropy / _uniform (include/torbi_hip.h); for a matrix that
-holds one value outside a band, csrc/path_entropy_band.hpp behind torbi_hip_path_entropy_band (`forward_entropy_banded`,
-`path_entropy(route=)`) runs the same recursion at the cost of the band, within the same bound.  `gpu=None` and host tensors
+holds one value outside a band, csrc/path_entropy_band.hpp behind torbi_hip_path_entropy_band (`forward_entropy_banded`, up
+to 64 in-band entries) and csrc/path_entropy_wide_band.hpp behind torbi_hip_path_entropy_wide_band
+(`forward_entropy_wide_banded`, up to 512) run the same recursion at the cost of the band, within the same bound;
+`path_entropy(route=)` chooses among them.  `gpu=None` and host tensors
 run the recursion in float64 with torch CPU ops.  ENTROPY.md has the contract, the kernels and the numbers.
 
 This module is published as the submodule `torbi_amd.entropy`, like `margins` and `paths`; its functions are not in
@@ -37,7 +39,8 @@ import torch
 from . import _lib, band_route, inputs, posterior
 
 __all__ = ['path_entropy', 'forward_entropy', 'path_entropy_workspace_bytes', 'forward_entropy_banded',
-           'path_entropy_banded_workspace_bytes', 'path_entropy_route']
+           'path_entropy_banded_workspace_bytes', 'forward_entropy_wide_banded', 'path_entropy_wide_banded_workspace_bytes',
+           'path_entropy_route']
 
 
 def path_entropy_workspace_bytes(B: int, T: int, S: int, uniform: bool = False) -> int:
@@ -132,7 +135,8 @@ def forward_entropy_banded(observation: torch.Tensor, batch_frames: Optional[tor
         within that bound, not exactly.
 
     Raises where the band route does not cover the call (torbi_hip_path_entropy_band_covers: up to 4096 states, at most 64
-    in-band entries in a matrix row, a background that is neither NaN nor +inf).
+    in-band entries in a matrix row, a background that is neither NaN nor +inf).  `forward_entropy_wide_banded` takes bands
+    of up to 512 entries.
     """
     shape = posterior._shapes('forward_entropy_banded', observation, batch_frames, transition, initial)
     obs, frames, left, right, background = posterior._banded_operands(
@@ -141,14 +145,65 @@ def forward_entropy_banded(observation: torch.Tensor, batch_frames: Optional[tor
     return _run_band(obs, frames, transition, initial, left, right, background, workspace, prefix)
 
 
+def path_entropy_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_entropy_wide_banded` needs: both packs of the band, three scalars per item and frame
+    and the promise flag.  No (B, T, S) region."""
+    return int(_lib.load().torbi_hip_path_entropy_wide_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
+
+
+def _wide_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_path_entropy_wide_band_covers: the wide band route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_path_entropy_wide_band_covers(B, T, S, int(reach_left), int(reach_right), background,
+                                                                    index))
+
+
+def _run_wide_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, prefix=False):
+    """One call of the wide band route on the device of `observation` (float32, contiguous, log space)."""
+    B, T, S = observation.shape
+    device = observation.device
+    entropy = torch.empty((B,), dtype=torch.float32, device=device)
+    log_likelihood = torch.empty((B,), dtype=torch.float32, device=device)
+    rows = torch.empty((B, T), dtype=torch.float32, device=device) if prefix else None
+    _lib.run('torbi_hip_path_entropy_wide_band', observation, frames, (transition, initial, reach_left, reach_right, background),
+             (entropy, rows, log_likelihood),
+             ('torbi_hip_path_entropy_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S), workspace)
+    return _answer(entropy, log_likelihood, rows, prefix)
+
+
+def forward_entropy_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                                initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
+                                workspace: Optional[torch.Tensor] = None, prefix: bool = False) -> Tuple[torch.Tensor, ...]:
+    """`forward_entropy_banded` for a band of up to 512 entries, by a kernel of its own (ENTROPY.md, "Wide band route").
+
+    Arguments, promise, outputs and non-finite rules are `forward_entropy_banded`'s, and so is the bound; the rounding
+    differs.  `workspace`: optional uint8 device tensor of >= `path_entropy_wide_banded_workspace_bytes(B, T, S, reach_left,
+    reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_path_entropy_wide_band_covers: up to 4096 states,
+    reach_left + reach_right + 1 <= 512 after clamping to S - 1, a background that is neither NaN nor +inf).
+    """
+    shape = posterior._shapes('forward_entropy_wide_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = posterior._banded_operands(
+        'forward_entropy_wide_banded', 'forward_entropy', _wide_covered, shape, (), observation, batch_frames, reach_left,
+        reach_right, background)
+    return _run_wide_band(obs, frames, transition, initial, left, right, background, workspace, prefix)
+
+
 # Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row) that
 # tools/path_entropy_probe.py measured faster than the dense call on the same inputs by more than the dense call's own
 # spread (ENTROPY.md, "Band route", timing).  Each entry: (smallest batch, largest batch, diagonals of 1440 states).
 # Measured at 500 frames x 1440 states, each against the dense call on the same inputs: 1, 8 and 512 items on 23 diagonals,
 # with -inf and with log(tiny) outside the band; the band route won all six (6.0 x at one item, 8.3 x at 512).  The pitch
-# matrix of 175 diagonals lies beyond the 64-entry window of torbi_hip_path_entropy_band_covers and stays dense, as does
-# anything else outside -- a larger batch, a wider band -- which is not measured.
+# matrix of 175 diagonals lies beyond the 64-entry window of torbi_hip_path_entropy_band_covers: `_AUTO_WIDE_BAND` below
+# answers for it.  Anything else outside -- a larger batch, a wider band -- is not measured and stays dense.
 _AUTO_BAND = ((1, 512, 23),)
+# Where 'auto' takes a band of more than 64 entries, which only the wide route covers: the classes that
+# tools/path_entropy_wide_band_probe.py measured faster than the dense call on the same inputs, the wide route's slowest call
+# under the dense route's fastest (ENTROPY.md, "Wide band route", timing).  Measured at 500 frames x 1440 states on 175
+# diagonals, -inf and log(tiny) outside: 1, 8, 64, 512 and 4096 items; the wide route won all ten (2.3 x at one item, 3.5 x at
+# 512, 3.0 x at 4096).  A wider band or a larger batch is not measured and stays dense.
+_AUTO_WIDE_BAND = ((1, 4096, 175),)
+_NARROW_WINDOW = 64          # in-band entries of a matrix row torbi_hip_path_entropy_band_covers takes
 
 
 def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
@@ -156,24 +211,43 @@ def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bo
                for low, high, diagonals in _AUTO_BAND)
 
 
+def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
+               for low, high, diagonals in _AUTO_WIDE_BAND)
+
+
+def _narrow(states, reach_left, reach_right) -> bool:
+    """The band has at most 64 in-band entries in a matrix row: it is the narrow route's to take or to turn down."""
+    return min(reach_left, states - 1) + min(reach_right, states - 1) + 1 <= _NARROW_WINDOW
+
+
 def _band_plan(trans, original, B, T, S, index):
-    """`band_route.plan` for this feature: the shape is what torbi_hip_path_entropy_band_covers takes."""
-    return band_route.plan(trans, original, _covered, 'torbi_hip_path_entropy_band_covers', dict(batch=B, frames=T, states=S),
-                           index)
+    """`band_route.plan` for this feature, over both band routes with one look at the matrix: a band of at most 64 entries
+    is asked of torbi_hip_path_entropy_band_covers, a wider one of torbi_hip_path_entropy_wide_band_covers, and a refusal
+    names the one that was asked."""
+    covers = lambda B, T, S, left, right, background, index: (
+        _covered if _narrow(S, left, right) else _wide_covered)(B, T, S, left, right, background, index)
+    entry = lambda left, right, background: ('torbi_hip_path_entropy_band_covers' if _narrow(S, left, right)
+                                             else 'torbi_hip_path_entropy_wide_band_covers')
+    return band_route.plan(trans, original, covers, entry, dict(batch=B, frames=T, states=S), index)
 
 
 def _band(route, trans, original, B, T, S, index):
-    """The band `route` takes for the device matrix `trans` (also `original`, the tensor the look is remembered with), or
-    None for the dense route (`band_route.choose`)."""
-    return band_route.choose(route, *_band_plan(trans, original, B, T, S, index),
-                             lambda left, right, background: _band_pays(B, S, left, right), "path_entropy(route='band')")
+    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix `trans` (also `original`, the tensor
+    the look is remembered with) to a band route, else None for the dense route (`band_route.choose`).  A band of at most 64
+    entries runs `_run_band` under 'band' and in a class of `_AUTO_BAND` under 'auto', bit for bit as before there was a wide
+    route; a wider one runs `_run_wide_band`, under 'band' always and under 'auto' in a class of `_AUTO_WIDE_BAND`."""
+    pays = lambda left, right, background: (_band_pays if _narrow(S, left, right) else _wide_band_pays)(B, S, left, right)
+    band = band_route.choose(route, *_band_plan(trans, original, B, T, S, index), pays, "path_entropy(route='band')")
+    return None if band is None else (_run_band if _narrow(S, *band[:2]) else _run_wide_band, band)
 
 
 def path_entropy_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: Optional[int] = 0,
                        log_probs: bool = False) -> str:
     """The route `path_entropy(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a (batch,
     frames, states) observation: 'uniform' (no matrix), 'band' (one value outside a band, in a class of batch and band width
-    that was measured faster: `forward_entropy_banded`) or 'dense' (`forward_entropy`)."""
+    that was measured faster: `forward_entropy_banded`, or `forward_entropy_wide_banded` for a band beyond its 64 entries)
+    or 'dense' (`forward_entropy`)."""
     if transition is None:
         return 'uniform'
     states = int(states)
@@ -203,7 +277,8 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
     route: which device route a given matrix takes; the values agree within the bound of ENTROPY.md on every one.  'dense'
         (the default): `forward_entropy`, which never looks at the matrix and synchronises nothing.  'band':
         `forward_entropy_banded` on the band `viterbi.band_over` finds (one look, with a host synchronisation, per tensor
-        version), raising with the reason where the matrix has no covered band.  'auto': the band route where such a band is
+        version), or `forward_entropy_wide_banded` where that band has more than 64 entries of a row, raising with the
+        reason where the matrix has no covered band.  'auto': the band route where such a band is
         found, the call is covered and its class of batch and band width was measured faster than the dense route
         (`path_entropy_route` answers which), else the dense one.  Ignored by `transition=None` except that 'band' raises
         there; `gpu=None` is the host route and refuses 'band'.
@@ -233,7 +308,8 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
         H, L, rows = _host(obs, frames, transition, uniform, initial)
         return _answer(H.to(torch.float32), L.to(torch.float32), rows.to(torch.float32), prefix)
     if band is not None:
-        return _run_band(obs, frames, transition, initial, *band, None, prefix)
+        run, stated = band
+        return run(obs, frames, transition, initial, *stated, None, prefix)
     return _run(obs, frames, transition, uniform, initial, None, prefix)
 
 

@@ -890,6 +890,26 @@ int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames,
                           void *stream);
 
 /*
+ * Posterior path sampling on a wide band (added within ABI 17): torbi_hip_sample_band for a band of up to 512 entries, by
+ * kernels of their own (SAMPLING.md, "Wide band route").  Arguments, the draw rule, the promise, the non-finite rules, the
+ * error codes and the order of the checks are torbi_hip_sample_band's; the order of the slots is the same and the rounding of
+ * the sums differs.  loglik_out: the bits of torbi_hip_forward_backward_wide_band's L.
+ *
+ * torbi_hip_sample_wide_band_covers: 1 where torbi_hip_forward_backward_wide_band_covers answers 1 (narrow bands included) and
+ * 1 <= N <= 4096; it reads no device.  torbi_hip_sample_wide_band_workspace_size:
+ * torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, reach_left, reach_right) plus the filter rows (B, T, S4) fp32,
+ * S4 = S rounded up to 4, on the next 256-byte boundary, whatever N; no initialisation and no alignment of the caller's base.
+ * TORBI_HIP_EUNSUPPORTED where _covers answers 0.  Five launches, no allocation and no host synchronisation: a call can be
+ * captured into a graph.
+ */
+int torbi_hip_sample_wide_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_sample_wide_band_workspace_size(int B, int T, int S, int N, int reach_left, int reach_right);
+int torbi_hip_sample_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                               const float *initial, int reach_left, int reach_right, float background, const float *uniforms,
+                               int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                               int S, int N, int device, void *stream);
+
+/*
  * Max-marginals (added within ABI 17): the largest log score of any complete path of item b that is in state j at frame t,
  * on the model torbi_hip_viterbi_decode decodes (torbi_amd/margins.py, MARGINALS.md).  Inputs as there: observation
  * (B, T, S) log scores, batch_frames (B,) int32 (F: clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.

@@ -12,6 +12,10 @@
       -inf and log(tiny) outside the band), alternated call by call in one process on the same inputs, at 512 x T x 1440 with 1
       and 16 draws, 1 x T x 1440 and 8 x 120 x 1440 with 1 draw (SAMPLING.md, "Band route"); with --trace only the kernel times
       of one call of each (the sampler launches and the filters), a run of its own
+  --wide-band: instead of (a) - (d), forward_sample against forward_sample_wide_banded on the pitch matrix of 175 diagonals
+      (synth.banded_transition(1440, 87.2), -inf and log(tiny) outside the band) at --batches x T x 1440 with 1 and 16 draws,
+      alternated call by call in one process on the same inputs, each with a caller-owned workspace; one JSON line per case
+      (SAMPLING.md, "Wide band route")
 Every time is the median of --repeats calls with its min and max, device synchronised around each call.
 """
 import argparse
@@ -200,8 +204,49 @@ def band_main(args, dev):
     print(json.dumps(out))
 
 
+def wide_band_case(B, T, S, half_width, draws, tiny, repeats, dev):
+    from posterior_probe import peaked_rows
+    reach = int(np.ceil(half_width)) - 1                                  # clip(half_width - |i - j|, 0) is 0 from there on
+    trans = torch.from_numpy(synth.banded_transition(S, half_width, tiny=tiny)).to(dev)
+    background = float(trans[0, S - 1])
+    init = torch.full((S,), float(np.log(1. / S)), device=dev)
+    obs = peaked_rows(B, T, S, dev)
+    frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    wd = torch.empty(torbi_amd.forward_sample_workspace_bytes(B, T, S, max(draws)), dtype=torch.uint8, device=dev)
+    ww = torch.empty(torbi_amd.forward_sample_wide_banded_workspace_bytes(B, T, S, max(draws), reach, reach), dtype=torch.uint8,
+                     device=dev)
+    out = {'shape': [B, T, S], 'diagonals': 2 * reach + 1, 'background': background if np.isfinite(background) else str(background),
+           'workspace_bytes': {'dense': wd.numel(), 'wide': ww.numel()}}
+    calls, us = {}, {}
+    for n in draws:
+        us[n] = torch.rand((B, n, T), device=dev, generator=torch.Generator(device=dev).manual_seed(n))
+        calls[f'dense_{n}'] = lambda n=n: torbi_amd.forward_sample(obs, frames, trans, init, us[n], workspace=wd)
+        calls[f'wide_{n}'] = lambda n=n: torbi_amd.forward_sample_wide_banded(obs, frames, trans, init, us[n], reach, reach,
+                                                                             background, workspace=ww)
+    L = [calls[f'{k}_{draws[0]}']()[1] for k in ('dense', 'wide')]
+    out['finite_L'] = bool(torch.isfinite(L[0]).all() and torch.isfinite(L[1]).all())
+    out['max_abs_L_difference'] = float((L[0].double() - L[1].double()).abs().max())
+    out['ms'] = alternated(calls, repeats)
+    for n in draws:
+        dense, wide = out['ms'][f'dense_{n}'], out['ms'][f'wide_{n}']
+        out[f'dense_over_wide_{n}'] = dense['median'] / wide['median']
+        # what 'auto' asks for: the slowest wide call under the fastest dense call
+        out[f'wide_faster_beyond_spread_{n}'] = wide['max'] < dense['min']
+    return out
+
+
+def wide_band_main(args, dev):
+    print(json.dumps({'device': torch.cuda.get_device_name(0)}), flush=True)
+    for B in args.batches:
+        for tiny in (False, True):
+            print(json.dumps(wide_band_case(B, args.T, 1440, 87.2, (1, 16), tiny, args.repeats, dev)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--wide-band', action='store_true',
+                    help='forward_sample against forward_sample_wide_banded on the pitch matrix of 175 diagonals')
+    ap.add_argument('--batches', type=int, nargs='+', default=[1, 8, 64, 512, 4096], help='with --wide-band: the batch sizes')
     ap.add_argument('--band', action='store_true', help='forward_sample against forward_sample_banded on the pitch matrix')
     ap.add_argument('--trace', action='store_true', help='with --band: kernel times of one call each instead of call times')
     ap.add_argument('--repeats', type=int, default=5)
@@ -211,6 +256,8 @@ def main():
     dev = torch.device('cuda:0')
     if args.band:
         return band_main(args, dev)
+    if args.wide_band:
+        return wide_band_main(args, dev)
     out = {'device': torch.cuda.get_device_name(0)}
     out['a_dense_512'] = dense_case(512, args.T, 1440, (1, 16), args.repeats, dev, not args.no_torch)
     out['a_dense_1'] = dense_case(1, args.T, 1440, (1,), args.repeats, dev, not args.no_torch)

@@ -37,6 +37,7 @@
 // The body of the launch is wide_passes<G, COUNTS>.  fb_wide_band_kernel<G> is its `false` arm.  The `true` arm,
 // fb_wide_band_operands_kernel<G>, also leaves the two factors of every pair of the expected counts in the workspace
 // (counts_wide_band.hpp); it is a second kernel, by counts_band.hpp's reasoning: the posterior route keeps its instances.
+// The forward pass is wide_forward<G>, which fb_wide_band_filter_kernel<G> (sample_wide_band.hpp) runs alone.
 #pragma once
 
 #include "forward_backward_band.hpp"
@@ -243,6 +244,101 @@ __device__ __forceinline__ void band_phase(const Tile<G> &tile, const Plan &p, i
         *reinterpret_cast<f4 *>(tile.slice + ((size_t)sl * G + g) * p.S4 + x0) = f4{acc[g][0], acc[g][1], acc[g][2], acc[g][3]};
 }
 
+// the band sum of state j of item g: the slices in their order
+template <int G>
+__device__ __forceinline__ float slices_of(const Tile<G> &tile, int S4, int KS, int g, int j) {
+    float s = tile.slice[(size_t)g * S4 + j];
+    for (int k = 1; k < KS; ++k) s += tile.slice[((size_t)k * G + g) * S4 + j];
+    return s;
+}
+
+// items b0 .. b0 + G - 1 of the workgroup: their frames, and zero rows (no barrier: the caller's next one covers the rows)
+template <int G>
+__device__ __forceinline__ void tile_begin(Tile<G> &tile, const int32_t *__restrict__ frames, int B, int T) {
+    tile.b0 = blockIdx.x * G;
+    tile.Fmax = 1;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        tile.F[g] = tile.b0 + g < B ? fb::frames_of(frames, tile.b0 + g, T) : 0;    // (0: an item beyond the batch never takes a step)
+        tile.Fmax = tile.F[g] > tile.Fmax ? tile.F[g] : tile.Fmax;
+    }
+    for (int e = threadIdx.x; e < G * tile.stride; e += kThreads) tile.rows[e] = 0.f;
+}
+
+// ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1}; a_t to `out` (rows of `out_stride` floats), c_t
+// to cbuf; ends behind a barrier, with every c_t of the tile stored.  The one forward pass of fb_wide_band_kernel,
+// fb_wide_band_operands_kernel and fb_wide_band_filter_kernel (sample_wide_band.hpp): it fixes the bits of a_t, c_t and L ----
+template <int G>
+FBW_INLINE void wide_forward(const Tile<G> &tile, const float *__restrict__ obs, const float *__restrict__ initial,
+                             const float *__restrict__ Pf, const float *__restrict__ m, float *__restrict__ cbuf,
+                             float *__restrict__ out, int out_stride, float ebg, const Plan &p, int T, int S) {
+    constexpr int kEarly = early_states(G);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int stride = p.stride, S4 = p.S4, KS = p.slices, b0 = tile.b0;
+    const int *F = tile.F;
+    const int Fmax = tile.Fmax;
+    float *const part = tile.part;
+    float *const cur = tile.rows + p.left4[0];
+    for (int t = 0; t < Fmax; ++t) {
+        float mt[G], early[kEarly > 0 ? kEarly : 1][G];
+        auto scalars = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
+        };
+        if (kEarly > 0) scalars();                                   // (a large tile has no registers to hold them over phase A)
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int it = 0; it < kEarly; ++it) {
+                const int j = tid + it * kThreads;
+                early[it][g] = (j < S && t < F[g]) ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;
+            }
+        if (t > 0) {
+            band_phase(tile, p, 0, Pf, S);
+            barrier();
+        }
+        if (kEarly == 0) scalars();
+        float cprev[G], acc[G];
+        if (t > 0) fbb::row_sums(tile, t - 1, cbuf, T, cprev);
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = 0.f;
+        auto state = [&](int j, const float *ot) __attribute__((always_inline)) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (t >= F[g]) continue;
+                const size_t row = (size_t)(b0 + g) * T + t;
+                const float o = ot ? ot[g] : obs[row * S + j], mm = mt[g];
+                float v;
+                if (t == 0) {
+                    v = expf(initial[j] + o - mm);
+                } else {
+                    const float s = slices_of(tile, S4, KS, g, j);
+                    const float e = expf(o - mm), c = cprev[g];
+                    const float u = e * (ebg != 0.f ? fmaf(ebg, c, s) : s);
+                    v = c == 0.f ? u * 0.f : u / c;                  // (after a zero-probability frame: 0, or NaN from NaN)
+                }
+                cur[g * stride + j] = v;
+                out[row * out_stride + j] = v;
+                acc[g] += v;
+            }
+        };
+#pragma unroll
+        for (int it = 0; it < kEarly; ++it)
+            if (tid + it * kThreads < S) state(tid + it * kThreads, early[it]);
+        for (int j = tid + kEarly * kThreads; j < S; j += kThreads) state(j, nullptr);
+        float *w = part + (size_t)(t & 1) * G * kWaves;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float a = fbb::wave_sum(acc[g]);
+            if (lane == 0) w[g * kWaves + wave] = a;
+        }
+        barrier();
+    }
+    float c[G];
+    fbb::row_sums(tile, Fmax - 1, cbuf, T, c);
+    barrier();                                                     // (c_t written by thread 0 is read by all below)
+}
+
 // ---- both passes of G items of one workgroup, the body of the two kernels below.  COUNTS (counts_wide_band.hpp): backward
 // phase B also stores the two operand rows of the counts, Wop[b][t][j] = w_t[j] and Aop[b][t][j] = a_t[j] * (g_b / c_t), rows
 // of S4 floats; `false` is the posterior kernel as it was, and nothing of `true` touches a value `false` computes ----
@@ -255,90 +351,16 @@ FBW_INLINE void wide_passes(unsigned char *lds_raw, const float *__restrict__ ob
     constexpr int kEarly = early_states(G);
     Tile<G> tile(lds_raw, p, S);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int stride = p.stride, S4 = p.S4, KS = p.slices, b0 = blockIdx.x * G;
-    tile.b0 = b0;
-    tile.Fmax = 1;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        tile.F[g] = b0 + g < B ? fb::frames_of(frames, b0 + g, T) : 0;    // (0: an item beyond the batch never takes a step)
-        tile.Fmax = tile.F[g] > tile.Fmax ? tile.F[g] : tile.Fmax;
-    }
+    const int stride = p.stride, S4 = p.S4, KS = p.slices;
+    tile_begin(tile, frames, B, T);
+    const int b0 = tile.b0;
     const int *F = tile.F;
     const int Fmax = tile.Fmax;
     float *const rows = tile.rows, *const part = tile.part;
-    for (int e = tid; e < G * stride; e += kThreads) rows[e] = 0.f;
     fbb::zero_absent_rows(tile, post, B, T, S);
     barrier();
 
-    // the band sum of state j of item g: the slices in their order
-    auto slices_of = [&](int g, int j) __attribute__((always_inline)) {
-        float s = tile.slice[(size_t)g * S4 + j];
-        for (int k = 1; k < KS; ++k) s += tile.slice[((size_t)k * G + g) * S4 + j];
-        return s;
-    };
-
-    // ---- forward: a_0 = exp(pi + o_0 - m_0), a_t = e_t * (E a_{t-1}) / c_{t-1}; a_t to post, c_t to cbuf ----
-    {
-        float *const cur = rows + p.left4[0];
-        for (int t = 0; t < Fmax; ++t) {
-            float mt[G], early[kEarly > 0 ? kEarly : 1][G];
-            auto scalars = [&]() __attribute__((always_inline)) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) mt[g] = t < F[g] ? m[(size_t)(b0 + g) * T + t] : 0.f;
-            };
-            if (kEarly > 0) scalars();                                   // (a large tile has no registers to hold them over phase A)
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int it = 0; it < kEarly; ++it) {
-                    const int j = tid + it * kThreads;
-                    early[it][g] = (j < S && t < F[g]) ? obs[((size_t)(b0 + g) * T + t) * S + j] : 0.f;
-                }
-            if (t > 0) {
-                band_phase(tile, p, 0, Pf, S);
-                barrier();
-            }
-            if (kEarly == 0) scalars();
-            float cprev[G], acc[G];
-            if (t > 0) fbb::row_sums(tile, t - 1, cbuf, T, cprev);
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[g] = 0.f;
-            auto state = [&](int j, const float *ot) __attribute__((always_inline)) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if (t >= F[g]) continue;
-                    const size_t row = (size_t)(b0 + g) * T + t;
-                    const float o = ot ? ot[g] : obs[row * S + j], mm = mt[g];
-                    float v;
-                    if (t == 0) {
-                        v = expf(initial[j] + o - mm);
-                    } else {
-                        const float s = slices_of(g, j);
-                        const float e = expf(o - mm), c = cprev[g];
-                        const float u = e * (ebg != 0.f ? fmaf(ebg, c, s) : s);
-                        v = c == 0.f ? u * 0.f : u / c;                  // (after a zero-probability frame: 0, or NaN from NaN)
-                    }
-                    cur[g * stride + j] = v;
-                    post[row * S + j] = v;
-                    acc[g] += v;
-                }
-            };
-#pragma unroll
-            for (int it = 0; it < kEarly; ++it)
-                if (tid + it * kThreads < S) state(tid + it * kThreads, early[it]);
-            for (int j = tid + kEarly * kThreads; j < S; j += kThreads) state(j, nullptr);
-            float *w = part + (size_t)(t & 1) * G * kWaves;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const float a = fbb::wave_sum(acc[g]);
-                if (lane == 0) w[g * kWaves + wave] = a;
-            }
-            barrier();
-        }
-        float c[G];
-        fbb::row_sums(tile, Fmax - 1, cbuf, T, c);
-        barrier();                                                 // (c_t written by thread 0 is read by all below)
-    }
+    wide_forward(tile, obs, initial, Pf, m, cbuf, post, S, ebg, p, T, S);
     fbb::log_likelihood(tile, m, cbuf, flag, loglik, B, T);
     for (int e = tid; e < G * stride; e += kThreads) rows[e] = 0.f;      // (the backward pass puts state x elsewhere)
     barrier();
@@ -387,7 +409,7 @@ FBW_INLINE void wide_passes(unsigned char *lds_raw, const float *__restrict__ ob
                 const float o = ot ? ot[g] : obs[at_j], a = at ? at[g] : post[at_j], mm = mt[g], c = ct[g];
                 float beta = 1.f;
                 if (t != F[g] - 1) {
-                    const float s = slices_of(g, j);
+                    const float s = slices_of(tile, S4, KS, g, j);
                     beta = ebg != 0.f ? fmaf(ebg, sw[g], s) : s;
                 }
                 const float w = (expf(o - mm) * beta) / c;               // (w_0 is never read)

@@ -53,6 +53,7 @@
 #include "k_best_band.hpp"
 #include "sample.hpp"
 #include "sample_band.hpp"
+#include "sample_wide_band.hpp"
 #include "max_marginals.hpp"
 #include "max_marginals_band.hpp"
 #include "path_statistics.hpp"
@@ -2981,6 +2982,17 @@ int torbi_hip_forward_backward_wide_band_tile(int B, int S, int reach_left, int 
     return fb_wide_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
 }
 
+// What every wide entry launches first: the pack with the check of the promise, then the row maxima.
+static hipError_t fb_wide_band_prepare(const fbw::Layout &l, const float *observation, const int32_t *batch_frames,
+                                       const float *transition, const float *initial, float ebg, float background, int B, int T,
+                                       int S, hipStream_t st) {
+    const hipError_t e = fbw::pack_and_verify(transition, l, ebg, background, S, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
+                       initial, l.m, B, T, S);
+    return hipGetLastError();
+}
+
 // What both wide entries launch: the pack with the check of the promise, the row maxima, then both passes of every item in
 // one launch.  With `Wop` and `Aop` (the counts entry) the instance that also stores the operand rows of the counts.
 static hipError_t fb_wide_band_passes(const fbw::Layout &l, const float *observation, const int32_t *batch_frames,
@@ -2989,10 +3001,8 @@ static hipError_t fb_wide_band_passes(const fbw::Layout &l, const float *observa
                                       int device, hipStream_t st) {
     const float ebg = exp_background(background);
     hipError_t e;
-    if ((e = fbw::pack_and_verify(transition, l, ebg, background, S, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(fb::fb_rowmax_kernel, dim3((unsigned)(((size_t)B * T + 3) / 4)), dim3(256), 0, st, observation, batch_frames,
-                       initial, l.m, B, T, S);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = fb_wide_band_prepare(l, observation, batch_frames, transition, initial, ebg, background, B, T, S, st)) != hipSuccess)
+        return e;
     int G = fb_wide_band_tile(B, l, cu_count(device));
     if (const char *forced = getenv("TORBI_HIP_WIDE_BAND_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per G)
         const int g = atoi(forced);
@@ -3192,6 +3202,63 @@ int torbi_hip_sample_band(const float *observation, const int32_t *batch_frames,
         auto *kernel = &fbb::sample_band_backward_kernel<decltype(vec_)::value>;
         hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, transition, l.c, batch_frames, loglik_out,
                            uniforms, indices_out, ebg, l.reach_left, l.reach_right, T, S, N);
+    });
+    return (int)hipGetLastError();
+}
+
+// ---- posterior path sampling on a wide band (sample_wide_band.hpp) ----
+
+int torbi_hip_sample_wide_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device) {
+    if (N < 1 || N > sample::kMaxDraws) return 0;
+    return torbi_hip_forward_backward_wide_band_covers(B, T, S, reach_left, reach_right, background, device);
+}
+
+size_t torbi_hip_sample_wide_band_workspace_size(int B, int T, int S, int N, int reach_left, int reach_right) {
+    (void)N;
+    if (B < 1 || T < 1 || S < 1 || S > fbw::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbw::sample_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_sample_wide_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                               const float *initial, int reach_left, int reach_right, float background, const float *uniforms,
+                               int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                               int S, int N, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && uniforms && indices_out && loglik_out && workspace,
+        torbi_hip_sample_wide_band_covers(B, T, S, N, reach_left, reach_right, background, device),
+        torbi_hip_sample_wide_band_workspace_size(B, T, S, N, reach_left, reach_right), workspace_bytes,
+        N >= 1 && N <= sample::kMaxDraws, (size_t)B * N * T <= (size_t)1 << 32);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbw::SampleLayout l = fbw::sample_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const float ebg = exp_background(background);
+    hipError_t e;
+    if ((e = fb_wide_band_prepare(l, observation, batch_frames, transition, initial, ebg, background, B, T, S, st)) != hipSuccess)
+        return (int)e;
+    const int G = fb_wide_band_tile(B, l, cu_count(device));             // (fb_wide_band_kernel's tile: the same LDS)
+    const size_t lds = fbw::lds_bytes(G, l);
+    const fbw::Plan &plan = l;
+    e = by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbw::fb_wide_band_filter_kernel<decltype(g)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(fbw::kThreads), lds, st, observation, batch_frames, initial, l.P[0],
+                           l.m, l.c, l.flag, l.rows, loglik_out, ebg, plan, B, T, S);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid(B, (N + sample::kWaves - 1) / sample::kWaves);
+    // (16-byte loads of a matrix row: rows of a multiple of 4 floats behind an aligned base)
+    const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(transition) & 15) == 0;
+    by_value<1, 2, 3>(fbw::sample_rounds(l), [&](auto np) {
+        by_flag(vec, [&](auto vec_) {
+            auto *kernel = &fbw::sample_wide_band_backward_kernel<decltype(np)::value, decltype(vec_)::value>;
+            hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, transition, l.c, batch_frames, loglik_out,
+                               uniforms, indices_out, ebg, l.reach_left, l.reach_right, T, S, N);
+        });
     });
     return (int)hipGetLastError();
 }

@@ -12,8 +12,9 @@ b reads u = uniforms[b, n, t] and goes from the last frame down:
 The HIP route is csrc/sample.hpp behind torbi_hip_sample / _uniform (include/torbi_hip.h): the forward half of
 `forward_backward`, then one launch that draws every path, one wave per draw.  For a matrix that holds one value outside a
 band, csrc/sample_band.hpp behind torbi_hip_sample_band (`forward_sample_banded`, `sample_paths(route=)`) draws at the cost of
-the band.  `gpu=None` runs the dense rule in float64 with torch CPU ops.  SAMPLING.md has the contract, the kernels and the
-numbers.
+the band, up to 64 in-band entries in a matrix row; csrc/sample_wide_band.hpp behind torbi_hip_sample_wide_band
+(`forward_sample_wide_banded`) takes bands of up to 512.  `gpu=None` runs the dense rule in float64 with torch CPU ops.
+SAMPLING.md has the contract, the kernels and the numbers.
 """
 import math
 from typing import Optional, Tuple
@@ -147,6 +148,49 @@ def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torc
     return _run_band(obs, frames, transition, initial, uniforms, left, right, background, workspace)
 
 
+def forward_sample_wide_banded_workspace_bytes(B: int, T: int, S: int, draws: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_sample_wide_banded` needs: the layout of `forward_backward_wide_banded` for this band
+    and the filter rows (B, T, S up to 4) float32 behind it, whatever `draws`."""
+    return int(_lib.load().torbi_hip_sample_wide_band_workspace_size(B, T, S, int(draws), int(reach_left), int(reach_right)))
+
+
+def _wide_covered(B, T, S, N, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_sample_wide_band_covers: the wide band route takes this shape, number of draws, band and background."""
+    return bool(_lib.load().torbi_hip_sample_wide_band_covers(B, T, S, int(N), int(reach_left), int(reach_right), background,
+                                                              index))
+
+
+def _run_wide_band(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
+    """`_run_band` on the wide route (torbi_hip_sample_wide_band)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    N = _check_uniforms(uniforms, B, T)
+    return _lib.run('torbi_hip_sample_wide_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background, uniforms), _outputs(B, N, T, observation.device),
+                    ('torbi_hip_sample_wide_band_workspace_size', (B, T, S, N, reach_left, reach_right)), (B, T, S, N), workspace)
+
+
+def forward_sample_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                               initial: torch.Tensor, uniforms: torch.Tensor, reach_left: int, reach_right: int,
+                               background: float = -math.inf, workspace: Optional[torch.Tensor] = None
+                               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_sample_banded` for a band of up to 512 entries, by kernels of their own (SAMPLING.md, "Wide band route").
+
+    Arguments, promise, the draw rule, outputs and non-finite rules are `forward_sample_banded`'s; the sums are rounded in
+    another order, so for given uniforms a draw may differ from that entry's where u Z lies within rounding of a slot's
+    edge.  The log-likelihood is `forward_backward_wide_banded`'s, bit for bit.  `workspace`: optional uint8 device tensor of
+    >= `forward_sample_wide_banded_workspace_bytes(B, T, S, draws, reach_left, reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_sample_wide_band_covers: what `forward_backward_wide_banded`
+    covers -- up to 4096 states, reach_left + reach_right + 1 <= 512 after clamping to S - 1 --, and 1 <= draws <= 4096).
+    """
+    B, T, S = shape = posterior._shapes('forward_sample_wide_banded', observation, batch_frames, transition, initial)
+    own = ('draws', _check_uniforms(uniforms, B, T))
+    obs, frames, left, right, background = posterior._banded_operands(
+        'forward_sample_wide_banded', 'forward_sample', _wide_covered, shape, own, observation, batch_frames, reach_left,
+        reach_right, background)
+    return _run_wide_band(obs, frames, transition, initial, uniforms, left, right, background, workspace)
+
+
 # Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row, draws) that
 # tools/sample_probe.py --band measured faster than the dense call by more than the spread of the measurement (SAMPLING.md,
 # "Band route", timing).  Each entry: (smallest batch, largest batch, diagonals of 1440 states, most draws).  Measured, all on
@@ -158,6 +202,19 @@ _AUTO_BAND = ((1, 512, 23, 1), (512, 512, 23, 16))
 def _band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
     return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals) and draws <= most
                for low, high, diagonals, most in _AUTO_BAND)
+
+
+# Where 'auto' takes a band that only the wide route covers: the classes that tools/sample_probe.py --wide-band measured
+# faster than the dense call on the same inputs, the wide route's slowest call under the dense route's fastest (SAMPLING.md,
+# "Wide band route", timing).  Each entry as in `_AUTO_BAND`.  Measured at 500 frames x 1440 states on 175 diagonals, -inf and
+# log(tiny) outside: 1, 8, 64, 512 and 4096 items at 1 and at 16 draws; the wide route won all twenty (1.4 x at one item, 2.9 x at
+# 512, 3.4 x at 4096).  A wider band, a larger batch or more draws are not measured and stay dense.
+_AUTO_WIDE_BAND = ((1, 4096, 175, 16),)
+
+
+def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
+    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals) and draws <= most
+               for low, high, diagonals, most in _AUTO_WIDE_BAND)
 
 
 def _band_plan(trans, original, B, T, S, N, index):
@@ -173,11 +230,29 @@ def _band(route, trans, original, B, T, S, N, index):
                              lambda left, right, background: _band_pays(B, S, left, right, N), "sample_paths(route='band')")
 
 
+def _band_run(route, trans, original, B, T, S, N, index):
+    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix to a band route, else None
+    (`posterior._band_run`'s steps).  One plan over both routes' covers, so one look at the matrix.  A band
+    torbi_hip_sample_band_covers takes runs `_run_band` where it did before there was a wide route, bit for bit: under
+    'band', and under 'auto' in a class of `_AUTO_BAND`.  A band only torbi_hip_sample_wide_band_covers takes runs
+    `_run_wide_band`, under 'band' always and under 'auto' in a class of `_AUTO_WIDE_BAND`."""
+    if route == 'dense':
+        return None
+    either = lambda *call: _covered(*call) or _wide_covered(*call)
+    band, why = band_route.plan(trans, original, either, 'torbi_hip_sample_wide_band_covers',
+                                dict(batch=B, frames=T, states=S, draws=N), index)
+    narrow = band is not None and _covered(B, T, S, N, *band, index)
+    pays = lambda left, right, background: (_band_pays if narrow else _wide_band_pays)(B, S, left, right, N)
+    band = band_route.choose(route, band, why, pays, "sample_paths(route='band')")
+    return None if band is None else (_run_band if narrow else _run_wide_band, band)
+
+
 def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, draws: int = 1, gpu: int = 0,
                  log_probs: bool = False) -> str:
     """The route `sample_paths(..., draws, transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
     (batch, frames, states) observation: 'uniform' (no matrix: independent frames), 'band' (one value outside a band, in a
-    class of batch, band width and draws that was measured faster: `forward_sample_banded`) or 'dense' (`forward_sample`)."""
+    class of batch, band width and draws that was measured faster: `forward_sample_banded`, or `forward_sample_wide_banded`
+    for a band beyond its 64 entries) or 'dense' (`forward_sample`)."""
     draws = _check_draws(draws)
     if transition is None:
         return 'uniform'
@@ -188,7 +263,7 @@ def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
         return 'dense'
     device = inputs._compute_device(gpu)
     trans = inputs.device_matrix(transition, log_probs, device)
-    band = _band('auto', trans, trans, int(batch), int(frames), states, draws, device.index or 0)
+    band = _band_run('auto', trans, trans, int(batch), int(frames), states, draws, device.index or 0)
     return 'dense' if band is None else 'band'
 
 
@@ -207,8 +282,9 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         uniforms give equal paths.  None: `torch.rand` on the compute device with `generator`.
     route: which device route a given matrix takes.  'dense' (the default): `forward_sample`, which synchronises nothing and
         whose draws for given uniforms are part of its behaviour.  'band': `forward_sample_banded` on the band
-        `viterbi.band_over` finds (one look, with a host synchronisation, per tensor version), raising with the reason where
-        the matrix has no covered band.  'auto': the band route where such a band is found, the call is covered and its
+        `viterbi.band_over` finds (one look, with a host synchronisation, per tensor version), or
+        `forward_sample_wide_banded` where the band has more than that entry's 64 entries in a matrix row, raising with the
+        reason where the matrix has no covered band.  'auto': the band route where such a band is found, the call is covered and its
         class of batch, band width and draws was measured faster than the dense route (`sample_route` answers which), else
         the dense one.  Both routes draw exactly from the model; for given uniforms their draws differ.  Ignored by
         `transition=None`; `gpu=None` is the float64 dense rule and refuses 'band'.
@@ -234,7 +310,7 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
     band = None
     if gpu is not None and uniform is None and route != 'dense':
         # (before the observation is prepared: a matrix without a band raises before anything runs)
-        band = _band(route, transition, transition, B, T, S, draws, device.index or 0)
+        band = _band_run(route, transition, transition, B, T, S, draws, device.index or 0)
     obs = inputs.observation(observation, log_probs, device)
     if uniforms is None:
         uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)
@@ -242,7 +318,8 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         indices, L = _host(obs, frames, transition, uniform, initial.to(torch.float32), uniforms)
         return indices.to(torch.int32), L.to(torch.float32)
     if band is not None:
-        return _run_band(obs, frames, transition, initial, uniforms, *band)
+        run, band = band
+        return run(obs, frames, transition, initial, uniforms, *band)
     return _run(obs, frames, transition, uniform, initial, uniforms)
 
 

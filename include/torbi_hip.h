@@ -708,6 +708,38 @@ int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t
                                          int B, int T, int S, int device, void *stream);
 
 /*
+ * Log-space band route of forward-backward (added within ABI 17; torbi_amd/posterior.py forward_backward_log_banded,
+ * POSTERIOR.md "Log-space band route"): torbi_hip_forward_backward_band's quantities, promise and outputs for a band of up to
+ * 512 entries, computed on logarithms (csrc/forward_backward_log_band.hpp): every forward and backward row is kept as logs
+ * under its own maximum, every product is a log-sum-exp over the band plus `background` + the log-sum-exp of the whole
+ * operand row, L is the fp64 sum of the forward maxima plus the log-sum-exp of the last row.  A filtered distribution that
+ * spans more than float32's range, where the scaled routes lose states (ENTROPY.md, "Where float32 is not enough"), is
+ * exact here; a frame costs W exponentials per state where the scaled routes spend W multiply-adds.
+ *   A state no path reaches has posterior 0; an item of total probability 0 has L = -inf and NaN rows t < F_b; an item that
+ *   reads a NaN or +inf has L = NaN and NaN rows; rows t >= F_b are 0.  The promise is the band route's, and in addition no
+ *   in-band entry lies under a finite `background` (it would be a negative weight): where either is broken every L and every
+ *   row t < F_b is NaN.  An item's bits depend on (S, band) and its own data only.
+ * _covers: 1 for 1 <= S <= 4096, reach_left + reach_right + 1 <= 512 with the reaches clamped to S - 1 (narrow bands
+ * included), the LDS rows of one item fit, a background that is neither NaN nor +inf, B and T within
+ * torbi_hip_forward_backward's limits; else 0.  It and _workspace_size answer without a device.  _tile: the items per
+ * workgroup a call of B items takes on `device` (1, 2 or 4; 0 for arguments out of range); the environment variable
+ * TORBI_HIP_LOG_BAND_ITEMS (1, 2 or 4, where the tile fits the LDS) overrides it for a call, results do not depend on it
+ * (tools/posterior_log_band_probe.py times every tile).
+ * workspace: torbi_hip_forward_backward_log_band_workspace_size(B, T, S, reach_left, reach_right) bytes -- both packs and the
+ * flag: it depends on neither B nor T --, no initialisation and no alignment.  Three launches per call whatever T is, no host
+ * synchronisation: with a caller-owned workspace a call can be captured into a graph.  Arguments and errors as
+ * torbi_hip_forward_backward_wide_band.
+ */
+int torbi_hip_forward_backward_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                               int device);
+size_t torbi_hip_forward_backward_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_log_band_tile(int B, int S, int reach_left, int reach_right, int device);
+int torbi_hip_forward_backward_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                        const float *initial, int reach_left, int reach_right, float background,
+                                        float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                                        int B, int T, int S, int device, void *stream);
+
+/*
  * Expected counts on a band (added within ABI 17): torbi_hip_forward_backward_band on the same inputs, which writes
  * posterior_out and loglik_out bit for bit as that call does, and in addition the counts of
  * torbi_hip_forward_backward_counts inside the band, diagonal by diagonal, and the initial counts:

@@ -45,6 +45,7 @@
 #include "forward_backward.hpp"
 #include "forward_backward_band.hpp"
 #include "forward_backward_wide_band.hpp"
+#include "forward_backward_log_band.hpp"
 #include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
 #include "counts_wide_band.hpp"
@@ -3044,6 +3045,68 @@ int torbi_hip_forward_backward_wide_band(const float *observation, const int32_t
     if (guard.err != hipSuccess) return (int)guard.err;
     return (int)fb_wide_band_passes(l, observation, batch_frames, transition, initial, background, nullptr, posterior_out,
                                     loglik_out, nullptr, nullptr, B, T, S, device, static_cast<hipStream_t>(stream));
+}
+
+// ---- forward-backward in log space on a band (forward_backward_log_band.hpp) ----
+
+// Items per workgroup of fb_log_band_kernel<G>: fb_wide_band_tile's rule with this kernel's LDS (every workgroup re-reads the
+// pack every frame; POSTERIOR.md, "Log-space band route", has what every G measured).
+static int fb_log_band_tile(int B, const fbw::Plan &plan, int cus) {
+    return items_per_workgroup(fbl::kMaxGroup, B, 1, cus, [&](int G) { return fbl::lds_bytes(G, plan) <= (size_t)fbl::kMaxLdsBytes; });
+}
+
+int torbi_hip_forward_backward_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                               int device) {
+    (void)device;
+    if (B < 1 || T < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    if (!background_ok(background)) return 0;
+    if (!fb_shape_in_range(B, T, S)) return 0;
+    const fbw::Plan plan = fbw::plan_of(S, reach_left, reach_right);
+    return plan.W <= fbl::kMaxWindow && fbl::lds_bytes(1, plan) <= (size_t)fbl::kMaxLdsBytes ? 1 : 0;
+}
+
+size_t torbi_hip_forward_backward_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbl::layout(nullptr, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_log_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return fb_log_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
+}
+
+int torbi_hip_forward_backward_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                        const float *initial, int reach_left, int reach_right, float background,
+                                        float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
+                                        int B, int T, int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && workspace,
+        torbi_hip_forward_backward_log_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_log_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const fbl::Layout l = fbl::layout(fb_base(workspace), S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e = fbl::pack_and_verify(transition, l, background, S, st);
+    if (e != hipSuccess) return (int)e;
+    int G = fb_log_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_LOG_BAND_ITEMS")) {       // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2 || g == 4) && fbl::lds_bytes(g, l) <= (size_t)fbl::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = fbl::lds_bytes(G, l);
+    const dim3 grid((B + G - 1) / G), block(fbl::kThreads);
+    const fbw::Plan &plan = l;
+    return (int)by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbl::fb_log_band_kernel<decltype(g)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, initial, l.P[0], l.P[1], l.flag, posterior_out,
+                           loglik_out, background, plan, B, T, S);
+        return hipGetLastError();
+    });
 }
 
 // ---- expected counts on a wide band (counts_wide_band.hpp) ----

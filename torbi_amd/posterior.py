@@ -10,6 +10,8 @@ For t < F_b (log space, A indexed [next, prev]):
 The HIP route is csrc/forward_backward.hpp behind torbi_hip_forward_backward / _uniform (include/torbi_hip.h), and for a
 matrix that holds one value outside a band csrc/forward_backward_band.hpp behind torbi_hip_forward_backward_band (up to 64
 in-band entries) and csrc/forward_backward_wide_band.hpp behind torbi_hip_forward_backward_wide_band (up to 512);
+csrc/forward_backward_log_band.hpp behind torbi_hip_forward_backward_log_band runs the recurrence on logarithms for such a
+band (`arithmetic='log'`), exact where the scaled float32 rows lose states.
 `gpu=None` runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and
 the numbers.
 """
@@ -238,6 +240,67 @@ def forward_backward_wide_banded(observation: torch.Tensor, batch_frames: Option
     return _run_wide_band(obs, frames, transition, initial, left, right, background, workspace)
 
 
+def forward_backward_log_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_log_banded` needs for a (B, T, S) problem with this band (the two packs of
+    the band: it depends on neither B nor T)."""
+    return int(_lib.load().torbi_hip_forward_backward_log_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
+
+
+def _log_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
+    """torbi_hip_forward_backward_log_band_covers: the log-space band route takes this shape, band and background."""
+    return bool(_lib.load().torbi_hip_forward_backward_log_band_covers(B, T, S, int(reach_left), int(reach_right), background,
+                                                                       index))
+
+
+def _run_log_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
+    """One call of the log-space band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
+    `frames` there: (posterior, log_likelihood)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    return _lib.run('torbi_hip_forward_backward_log_band', observation, frames,
+                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
+                    ('torbi_hip_forward_backward_log_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
+                    workspace)
+
+
+def forward_backward_log_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                                initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
+                                workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_backward_banded` computed on logarithms, for a band of up to 512 entries (POSTERIOR.md, "Log-space band
+    route"): exact where the filtered distribution spans more than float32's range and the scaled routes lose states
+    (mismatched data, left-to-right and permutation matrices), at W exponentials per state and frame.
+
+    Arguments, outputs and non-finite rules are `forward_backward_banded`'s.  The promise too, and in addition no in-band
+    entry lies under a finite `background`; a broken promise is NaN everywhere.  `workspace`: optional uint8 device tensor
+    of >= `forward_backward_log_banded_workspace_bytes(B, T, S, reach_left, reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_forward_backward_log_band_covers: up to 4096 states,
+    reach_left + reach_right + 1 <= 512 after clamping to S - 1, a background that is neither NaN nor +inf).
+    """
+    shape = _shapes('forward_backward_log_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands('forward_backward_log_banded', 'state_posteriors with gpu=None',
+                                                            _log_covered, shape, (), observation, batch_frames, reach_left,
+                                                            reach_right, background)
+    return _run_log_band(obs, frames, transition, initial, left, right, background, workspace)
+
+
+ARITHMETICS = ('scaled', 'log')
+_LOG_ONLY = "state_posteriors(arithmetic='log'): the log arithmetic has a band route only"
+_LOG_HOST = 'gpu=None computes any matrix in float64 on the CPU'
+
+
+def _log_band_run(route, trans, original, B, T, S, index):
+    """(`_run_log_band`, (reach_left, reach_right, background)) for `arithmetic='log'`: 'auto' and 'band' take the log-space
+    band route for any band it covers -- an opt-in for correctness, so no table of measured classes --, and 'dense' or a
+    matrix with no covered band raises: a GPU request never silently changes arithmetic."""
+    if route == 'dense':
+        raise RuntimeError(f"{_LOG_ONLY}, and route='dense' asks for the dense one ({_LOG_HOST})")
+    band, why = band_route.plan(trans, original, _log_covered, 'torbi_hip_forward_backward_log_band_covers',
+                                dict(batch=B, frames=T, states=S), index)
+    if band is None:
+        raise RuntimeError(f'{_LOG_ONLY}: {why} ({_LOG_HOST})')
+    return _run_log_band, band
+
+
 # Where 'auto' takes a band that only the wide route covers: the classes of (batch, band width as a share of the row) that
 # tools/posterior_wide_band_probe.py measured faster than the dense call on the same inputs, the wide route's slowest call
 # under the dense route's fastest (POSTERIOR.md, "Wide band route", measurements).  Each entry: (smallest batch, largest
@@ -300,7 +363,7 @@ def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int,
 
 def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
                      transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None,
-                     log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto'
+                     log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto', arithmetic: str = 'scaled'
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     """P(state_t = j | all frames) of every frame, and log P(observations) of every item.
 
@@ -314,6 +377,12 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
         band that route covers (`posterior_route` answers which), else the dense one; 'dense': always the dense route;
         'band': the band route, raising where the matrix has no covered band.  Both meet the same tolerance against
         float64; their roundings differ.  Ignored by `gpu=None` and `transition=None`.
+    arithmetic: 'scaled' (the default): the float32 scaled recurrence of every route above.  'log': the log-space band
+        route (`forward_backward_log_banded`), exact where the filtered distribution spans more than float32's range --
+        mismatched data, left-to-right matrices -- and slower: 'auto' and 'band' take it for any band it covers;
+        `route='dense'` or a matrix with no covered band raises, since the log arithmetic has a band route only (`gpu=None`
+        computes any matrix in float64).  `transition=None` keeps the closed form, a log-sum-exp per row already;
+        `gpu=None` ignores it.
 
     Returns:
         (posterior (batch, frames, states) float32, log_likelihood (batch,) float32) on the compute device.  Rows
@@ -321,7 +390,12 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
         a NaN or +inf has NaN for both.
     """
     band_route.check_route(route)
+    if arithmetic not in ARITHMETICS:
+        raise RuntimeError(f"arithmetic must be 'scaled' or 'log'; got {arithmetic!r}")
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    log_band = arithmetic == 'log' and gpu is not None and transition is not None and B > 0
+    if log_band and route == 'dense':
+        _log_band_run(route, None, None, B, T, S, 0)                                # (raises before anything runs)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
     transition, uniform, initial = inputs.model(transition, initial, log_probs, S, device, plain=gpu is not None)
@@ -329,7 +403,8 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     if gpu is None:
         gamma, L, _, _ = _host(obs, frames, transition, uniform, initial.to(torch.float32))
         return gamma.to(torch.float32), L.to(torch.float32)
-    band = None if uniform is not None else _band_run(route, transition, transition, B, T, S, device.index or 0)
+    plan = _log_band_run if log_band else _band_run
+    band = None if uniform is not None else plan(route, transition, transition, B, T, S, device.index or 0)
     if band is not None:
         run, band = band
         return run(obs, frames, transition, initial, *band)

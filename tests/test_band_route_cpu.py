@@ -1,6 +1,7 @@
 """The band planner (torbi_amd/band_route.py) without a device: `plan` and `choose` as a table over the route, what the
-matrix and the feature's covers function answer and whether a look is allowed; then the same table through the few lines each
-of the five features keeps, with `viterbi.band_over` and the feature's covers function substituted."""
+matrix and the feature's covers function answer and whether a look is allowed, and `route` over two declared routes; then the
+same table through the planner each feature's public entry runs, with `viterbi.band_over` and the feature's covers function
+substituted."""
 import itertools
 import types
 
@@ -8,7 +9,7 @@ import pytest
 import torch
 
 import torbi_amd
-from torbi_amd import band_route, k_best, posterior, sampling, state, stream, training, viterbi
+from torbi_amd import band_route, entropy, k_best, margins, posterior, sampling, state, stream, training, viterbi
 
 B, T, S = 2, 5, 64
 BAND = (1, 2, -20.)
@@ -22,13 +23,13 @@ LOOKS = ('look', 'known', 'unknown')                        # look=True; look=Fa
 class Fakes:
     """`viterbi.band_over` and a covers function that answer what `matrix` says, and count how often they are asked."""
 
-    def __init__(self, monkeypatch, matrix):
-        self.matrix, self.looks, self.asked = matrix, 0, []
+    def __init__(self, monkeypatch, matrix, band=BAND):
+        self.matrix, self.band, self.looks, self.asked = matrix, band, 0, []
         monkeypatch.setattr(viterbi, 'band_over', self.band_over)
 
     def band_over(self, trans, original, states):
         self.looks += 1
-        return None if self.matrix == 'none' else BAND
+        return None if self.matrix == 'none' else self.band
 
     def covers(self, *args):
         self.asked.append(args)
@@ -78,6 +79,42 @@ def test_plan_and_choose(monkeypatch, route, matrix, look):
     assert fakes.looks == 0                                                   # `choose` asks nobody
 
 
+@pytest.mark.parametrize('route,matrix,look', list(itertools.product(band_route.ROUTES, MATRIX, LOOKS)))
+def test_route_asks_only_the_first_declared_route_that_takes_the_band(monkeypatch, route, matrix, look):
+    """Two declared routes that both take BAND: the first is the one asked, named and returned, and a band it refuses does
+    not fall through to the second, which would cover everything."""
+    fakes = Fakes(monkeypatch, matrix)
+    A = matrix_for(look)
+    second = []
+    table = ((1, B, 1440),) if matrix == 'pays' else ((B + 1, B + 1, 1440),)          # the class of the call, or another
+    routes = (band_route.BandRoute(fakes.covers, 'some_covers', 'first', table, lambda *band: band == (S, 1, 2)),
+              band_route.BandRoute(lambda *call: second.append(call) or True, 'other_covers', 'second', None,
+                                   band_route.any_width))
+    call = lambda: band_route.route(routes, route, A, A, dict(batch=B, states=S), 3, 'who', look=look == 'look')
+    band, why, looked = expected(route, matrix, look)
+    if route == 'dense':
+        assert call() is None and fakes.looks == 0 and fakes.asked == []
+    elif route == 'band' and band is None:
+        with pytest.raises(RuntimeError) as raised:
+            call()
+        assert str(raised.value) == f'who: {why}'
+    else:
+        assert call() == ((routes[0], BAND) if band is not None and (route == 'band' or matrix == 'pays') else None)
+    if route != 'dense':
+        assert fakes.looks == int(looked) and fakes.asked == ([(B, S, *BAND, 3)] if looked and matrix != 'none' else [])
+    assert second == []
+    # a band the first route does not take is the second's
+    assert band_route.taking(routes, S, 2, 2) is routes[1] and band_route.taking(routes, S, 1, 2) is routes[0]
+
+
+def test_entries_and_classes():
+    assert band_route.NARROW_ENTRIES == 64
+    assert band_route.entries(1440, 11, 11) == 23 and band_route.entries(64, 1, 63) == 64 and band_route.entries(4, 9, 9) == 4
+    assert band_route.entries(64, 1, 63, cap=False) == 65 and band_route.entries(4, 9, 9, cap=False) == 7
+    assert band_route.narrow(64, 1, 63) and band_route.narrow(1440, 31, 32) and not band_route.narrow(1440, 32, 32)
+    assert band_route.any_width(1440, 300, 300)
+
+
 def test_plan_of_an_empty_batch_and_the_other_background_text(monkeypatch):
     fakes = Fakes(monkeypatch, 'none')
     A = torch.zeros((S, S))
@@ -116,11 +153,26 @@ def test_every_feature_checks_the_route_name_with_its_own_exception():
         assert type(raised.value) is error
 
 
+WIDE_STATES, WIDE_BAND = 128, (40, 30, -float('inf'))      # 71 in-band entries: beyond the narrow routes' 64
+
+
+def band_of(taken):
+    """The band of what `band_route.route` answers, (route, band) or None."""
+    return None if taken is None else taken[1]
+
+
+def with_minus_inf(reaches):
+    """The band of what `training._counts_band` answers, (reach_left, reach_right) of a band with -inf outside, or None."""
+    return None if reaches is None else (*reaches, -float('inf'))
+
+
 def features(monkeypatch, fakes):
-    """name -> (who, the reason's text before the band, route -> band or None): the lines a feature keeps around the planner,
-    on host tensors, with the feature's covers function substituted."""
+    """name -> (who, the reason's text before the band, route -> band or None): the planner each public entry runs, on host
+    tensors, with the feature's covers function substituted."""
     A, x, f, pi = torch.zeros((S, S)), torch.zeros((B, T, S)), torch.full((B,), T), torch.zeros(S)
-    for module, name in ((posterior, '_covered'), (training, '_counts_covered'), (sampling, '_covered'), (k_best, '_covered'),
+    wide = torch.zeros((WIDE_STATES, WIDE_STATES))
+    for module, name in ((posterior, '_covered'), (training, '_counts_covered'), (training, '_wide_counts_covered'),
+                         (sampling, '_covered'), (entropy, '_covered'), (margins, '_covered'), (k_best, '_covered'),
                          (stream, '_covered')):
         monkeypatch.setattr(module, name, fakes.covers)
     # k-best: `_routed` goes on to the call it chose; the band it hands `_run_band` is the answer
@@ -130,10 +182,21 @@ def features(monkeypatch, fakes):
     return {
         'posteriors': ("state_posteriors(route='band')",
                        f'torbi_hip_forward_backward_band_covers turns down batch={B}, frames={T}, states={S}',
-                       lambda route: posterior._band(route, A, A, B, T, S, 0)),
+                       lambda route: band_of(posterior._band_run(route, A, A, B, T, S, 0))),
         'sampling': ("sample_paths(route='band')",
                      f'torbi_hip_sample_band_covers turns down batch={B}, frames={T}, states={S}, draws=3',
-                     lambda route: sampling._band(route, A, A, B, T, S, 3, 0)),
+                     lambda route: band_of(sampling._band_run(route, A, A, B, T, S, 3, 0))),
+        'entropy': ("path_entropy(route='band')",
+                    f'torbi_hip_path_entropy_band_covers turns down batch={B}, frames={T}, states={S}',
+                    lambda route: band_of(entropy._band(route, A, A, B, T, S, 0))),
+        'max-marginals': ("max_marginals(route='band')",
+                          f'torbi_hip_max_marginals_band_covers turns down batch={B}, frames={T}, states={S}',
+                          lambda route: band_of(margins._band(route, A, A, B, T, S, 0))),
+        'counts (wide)': ("route='band'",
+                          'the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers up to 64 '
+                          'in-band entries, torbi_hip_forward_backward_counts_wide_band_covers beyond) turns down '
+                          f'batch={B}, frames={T}, states={WIDE_STATES}',
+                          lambda route: with_minus_inf(training._counts_band(wide, wide, B, T, WIDE_STATES, 0, route))),
         'k-best': ("k-best decoding with route='band'",
                    f'torbi_hip_k_best_band_covers turns down batch={B}, frames={T}, states={S}, k=2',
                    lambda route: k_best._routed(x, f, A, A, None, pi, 2, route)),
@@ -142,27 +205,33 @@ def features(monkeypatch, fakes):
     }
 
 
+FEATURES = ('posteriors', 'sampling', 'entropy', 'max-marginals', 'counts (wide)', 'k-best', 'stream')
+
+
 # (a covered band takes the streaming decoder on to torbi_hip_stream_band_prepare on the device: tests/test_stream_band_gpu.py)
-@pytest.mark.parametrize('feature,matrix', [(f, m) for f in ('posteriors', 'sampling', 'k-best', 'stream') for m in MATRIX
+@pytest.mark.parametrize('feature,matrix', [(f, m) for f in FEATURES for m in MATRIX
                                             if f != 'stream' or m in ('none', 'uncovered')])
 def test_features_raise_the_planner_s_reason_under_band_and_not_under_auto(monkeypatch, feature, matrix):
     """'band' on a matrix without a covered band: RuntimeError(who: why) from every feature, with `why` the planner's two
     texts and the feature's part in them; 'auto' goes dense there without raising, after the one look."""
-    fakes = Fakes(monkeypatch, matrix)
+    band = WIDE_BAND if feature == 'counts (wide)' else BAND
+    fakes = Fakes(monkeypatch, matrix, band)
     who, asked, call = features(monkeypatch, fakes)[feature]
     if matrix in ('none', 'uncovered'):
         finite = 'a finite value below every entry of the band' if feature == 'stream' else 'finite'
-        why = NO_BAND.format(finite) if matrix == 'none' else f'{asked}, reach 1/2, background -20.0'
+        why = NO_BAND.format(finite) if matrix == 'none' else f'{asked}, reach {band[0]}/{band[1]}, background {band[2]}'
         with pytest.raises(RuntimeError) as raised:
             call('band')
         assert str(raised.value) == f'{who}: {why}' and fakes.looks == 1
         fakes.looks = 0
         assert call('auto') is None and fakes.looks == 1
     else:
-        assert call('band') == BAND and fakes.looks == 1
-        # (posteriors take every covered band; 4 diagonals of 64 states are a share of the row k-best's table holds at k = 2
-        # -- 175 / 1440 -- and sampling's does not -- 23 / 1440)
-        assert call('auto') == (None if feature == 'sampling' else BAND) and fakes.looks == 2
+        assert call('band') == band and fakes.looks == 1
+        # (posteriors take every covered band; 4 diagonals of 64 states are a share of the row the tables of k-best at k = 2
+        # and of max-marginals hold -- 175 / 1440 -- and those of sampling and entropy do not -- 23 / 1440; 71 diagonals of 128
+        # states are more than the 175 / 1440 of the wide counts' table)
+        dense = feature in ('sampling', 'entropy', 'counts (wide)')
+        assert call('auto') == (None if dense else band) and fakes.looks == 2
 
 
 @pytest.mark.parametrize('matrix', MATRIX)

@@ -352,6 +352,17 @@ def run(name, observation, frames, inputs, outputs, need, dims, workspace=None):
     return outputs
 
 
+def covers(name):
+    """The host-only C entry `name` (a torbi_hip_*_covers) as a predicate over (the entry's shape..., reach_left, reach_right,
+    background[, device index = 0]): the band route it speaks for takes this call."""
+    arity = len(SYMBOLS[name][1])
+
+    def covered(*call) -> bool:
+        call += (0,) * (arity - len(call))
+        return bool(getattr(load(), name)(*map(int, call[:-2]), call[-2], int(call[-1])))
+    return covered
+
+
 def build_cpu(force=False, verbose=False):
     """Compile csrc/torbi_cpu.cpp into torbi_amd/libtorbi_cpu.so (in-tree; the CPU operator of gpu=None callers)."""
     deps = [CPU_SOURCE, os.path.join(INCLUDE, 'torbi_cpu.h'), os.path.join(os.path.dirname(CPU_SOURCE), 'file_rows.hpp')]

@@ -1,13 +1,16 @@
-"""How a call with a `route=` argument is sent to the band route or the dense one: ONE planner for state posteriors, expected
-counts, path sampling, k-best decoding and streaming decode.
+"""How a call with a `route=` argument is sent to a band route or the dense one: ONE planner for every feature that has one.
 
     band, why = plan(trans, original, covers, entry, shape, index)      # is there a band, does the feature's route cover it
     band = choose(route, band, why, pays, who)                           # what `route` does with the answer
+    taken = route(routes, route, trans, original, shape, index, who)     # both, over the band routes a feature declares
 
-A feature hands over what is its own: its `covers` function over torbi_hip_*_band_covers, that entry's name and the call's
-shape for a refusal, whether its 'auto' pays for a covered band (`pays`, from its table of measured classes through `share_within`)
-and the exception type of its route-name check.
+A feature declares its band routes as data, one `BandRoute` each in the order they are asked (state posteriors, expected
+counts, path entropy and path sampling a narrow and a wide one, max-marginals one), and `route` answers (the route, the band)
+or None for the dense route.  k-best decoding and the two streaming classes have one band route and extras of their own
+(a plan without a look, a workspace check, a stated band) and call `plan` and `choose` themselves.
 """
+import collections
+
 import torch
 
 from . import state, viterbi
@@ -16,6 +19,13 @@ ROUTES = ('auto', 'dense', 'band')
 # the states of the matrix every table of measured classes was timed on (the reference's pitch matrix); a band's width counts
 # as its share of a row
 _MEASURED_STATES = 1440
+NARROW_ENTRIES = 64                               # in-band entries of a matrix row the narrow band routes take
+
+# One band route of a feature: `covers(*shape, reach_left, reach_right, background, index)` over its torbi_hip_*_covers, `entry`
+# that function's name for a refusal, `run` the call of its kernel, `classes` the table of (smallest batch, largest batch,
+# diagonals of 1440 states[, most draws]) 'auto' takes it in (None: every covered band pays), and `takes(states, reach_left,
+# reach_right)`: this route is the one to ask for this band.
+BandRoute = collections.namedtuple('BandRoute', 'covers entry run classes takes')
 
 
 def check_route(route, error=RuntimeError) -> str:
@@ -35,6 +45,34 @@ def stated(reach_left, reach_right, background):
 def share_within(states: int, reach_left: int, reach_right: int, diagonals: int) -> bool:
     """The band holds at most `diagonals` / 1440 of a matrix row."""
     return (reach_left + reach_right + 1) * _MEASURED_STATES <= diagonals * states
+
+
+def entries(states: int, reach_left: int, reach_right: int, cap: bool = True) -> int:
+    """The in-band entries of a matrix row: the width of the band after clamping each reach to states - 1, and with `cap` at
+    most the row itself."""
+    width = min(reach_left, states - 1) + min(reach_right, states - 1) + 1
+    return min(width, states) if cap else width
+
+
+def narrow(states: int, reach_left: int, reach_right: int) -> bool:
+    """`BandRoute.takes` of a narrow route: at most 64 in-band entries in a row."""
+    return entries(states, reach_left, reach_right) <= NARROW_ENTRIES
+
+
+def any_width(states: int, reach_left: int, reach_right: int) -> bool:
+    """`BandRoute.takes` of a feature's last route: whatever the routes before it left."""
+    return True
+
+
+def taking(routes, states: int, reach_left: int, reach_right: int):
+    """The first of the declared `routes` whose `takes` holds for this band: the one to ask, and the one that runs it."""
+    return next(r for r in routes if r.takes(states, reach_left, reach_right))
+
+
+def in_classes(table, batch: int, states: int, reach_left: int, reach_right: int, draws=None) -> bool:
+    """The call lies in a class of `table`, entries (smallest batch, largest batch, diagonals of 1440 states[, most draws])."""
+    return any(low <= batch <= high and share_within(states, reach_left, reach_right, diagonals)
+               and (not most or draws <= most[0]) for low, high, diagonals, *most in table)
 
 
 def plan(trans: torch.Tensor, original: torch.Tensor, covers, entry: str, shape: dict, index: int = 0, look: bool = True,
@@ -78,3 +116,20 @@ def choose(route: str, band, why: str, pays, who: str):
             raise RuntimeError(f'{who}: {why}')
         return band
     return band if band is not None and (pays is None or pays(*band)) else None
+
+
+def route(routes, route: str, trans: torch.Tensor, original: torch.Tensor, shape: dict, index: int, who: str, look: bool = True):
+    """(the BandRoute, (reach_left, reach_right, background)) where `route` sends the device matrix to one of the band routes
+    a feature declares, else None for the dense route.  'dense' asks nothing; else one `plan`, so one look at the matrix, in
+    which the first of `routes` whose `takes` holds for the band found is the only one whose `covers` is asked, and the one a
+    refusal names; then `choose`, with that route's `classes` (read with batch=, states= and draws= of `shape`) for 'auto'."""
+    if route == 'dense':
+        return None
+    states = shape['states']
+    band, why = plan(trans, original, lambda *call: taking(routes, states, *call[-4:-2]).covers(*call),
+                     lambda left, right, background: taking(routes, states, left, right).entry, shape, index, look)
+    asked = None if band is None else taking(routes, states, *band[:2])
+    pays = None if asked is None or asked.classes is None else lambda left, right, background: in_classes(
+        asked.classes, shape['batch'], states, left, right, shape.get('draws'))
+    band = choose(route, band, why, pays, who)
+    return None if band is None else (asked, band)

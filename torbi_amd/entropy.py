@@ -31,6 +31,7 @@ This module is published as the submodule `torbi_amd.entropy`, like `margins` an
 `torbi_amd.__all__` (every top-level public function that takes an observation has a row in the operand-form table of the
 test suite; the rows of these are run from this feature's own tests).
 """
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -92,22 +93,26 @@ def path_entropy_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int,
     return int(_lib.load().torbi_hip_path_entropy_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
 
 
-def _covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_path_entropy_band_covers: the band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_path_entropy_band_covers(B, T, S, int(reach_left), int(reach_right), background, index))
+def _band_runner(name):
+    """`run(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, prefix=False)`: one
+    call of the band route `name` on the device of `observation` (float32, contiguous, log space)."""
+    def run(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, prefix=False):
+        B, T, S = observation.shape
+        device = observation.device
+        entropy = torch.empty((B,), dtype=torch.float32, device=device)
+        log_likelihood = torch.empty((B,), dtype=torch.float32, device=device)
+        rows = torch.empty((B, T), dtype=torch.float32, device=device) if prefix else None
+        _lib.run(name, observation, frames, (transition, initial, reach_left, reach_right, background),
+                 (entropy, rows, log_likelihood), (name + '_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
+                 workspace)
+        return _answer(entropy, log_likelihood, rows, prefix)
+    return run
 
 
-def _run_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, prefix=False):
-    """One call of the band route on the device of `observation` (float32, contiguous, log space)."""
-    B, T, S = observation.shape
-    device = observation.device
-    entropy = torch.empty((B,), dtype=torch.float32, device=device)
-    log_likelihood = torch.empty((B,), dtype=torch.float32, device=device)
-    rows = torch.empty((B, T), dtype=torch.float32, device=device) if prefix else None
-    _lib.run('torbi_hip_path_entropy_band', observation, frames, (transition, initial, reach_left, reach_right, background),
-             (entropy, rows, log_likelihood), ('torbi_hip_path_entropy_band_workspace_size', (B, T, S, reach_left, reach_right)),
-             (B, T, S), workspace)
-    return _answer(entropy, log_likelihood, rows, prefix)
+_covered = _lib.covers('torbi_hip_path_entropy_band_covers')
+_run_band = _band_runner('torbi_hip_path_entropy_band')
+_wide_covered = _lib.covers('torbi_hip_path_entropy_wide_band_covers')
+_run_wide_band = _band_runner('torbi_hip_path_entropy_wide_band')
 
 
 def forward_entropy_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -151,25 +156,6 @@ def path_entropy_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_left:
     return int(_lib.load().torbi_hip_path_entropy_wide_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
 
 
-def _wide_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_path_entropy_wide_band_covers: the wide band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_path_entropy_wide_band_covers(B, T, S, int(reach_left), int(reach_right), background,
-                                                                    index))
-
-
-def _run_wide_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, prefix=False):
-    """One call of the wide band route on the device of `observation` (float32, contiguous, log space)."""
-    B, T, S = observation.shape
-    device = observation.device
-    entropy = torch.empty((B,), dtype=torch.float32, device=device)
-    log_likelihood = torch.empty((B,), dtype=torch.float32, device=device)
-    rows = torch.empty((B, T), dtype=torch.float32, device=device) if prefix else None
-    _lib.run('torbi_hip_path_entropy_wide_band', observation, frames, (transition, initial, reach_left, reach_right, background),
-             (entropy, rows, log_likelihood),
-             ('torbi_hip_path_entropy_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S), workspace)
-    return _answer(entropy, log_likelihood, rows, prefix)
-
-
 def forward_entropy_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
                                 initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
                                 workspace: Optional[torch.Tensor] = None, prefix: bool = False) -> Tuple[torch.Tensor, ...]:
@@ -203,43 +189,26 @@ _AUTO_BAND = ((1, 512, 23),)
 # diagonals, -inf and log(tiny) outside: 1, 8, 64, 512 and 4096 items; the wide route won all ten (2.3 x at one item, 3.5 x at
 # 512, 3.0 x at 4096).  A wider band or a larger batch is not measured and stays dense.
 _AUTO_WIDE_BAND = ((1, 4096, 175),)
-_NARROW_WINDOW = 64          # in-band entries of a matrix row torbi_hip_path_entropy_band_covers takes
+# (batch, states, reach_left, reach_right) lies in a class of the table: what 'auto' asks through the declaration below
+_band_pays = functools.partial(band_route.in_classes, _AUTO_BAND)
+_wide_band_pays = functools.partial(band_route.in_classes, _AUTO_WIDE_BAND)
 
 
-def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_BAND)
-
-
-def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_WIDE_BAND)
-
-
-def _narrow(states, reach_left, reach_right) -> bool:
-    """The band has at most 64 in-band entries in a matrix row: it is the narrow route's to take or to turn down."""
-    return min(reach_left, states - 1) + min(reach_right, states - 1) + 1 <= _NARROW_WINDOW
-
-
-def _band_plan(trans, original, B, T, S, index):
-    """`band_route.plan` for this feature, over both band routes with one look at the matrix: a band of at most 64 entries
-    is asked of torbi_hip_path_entropy_band_covers, a wider one of torbi_hip_path_entropy_wide_band_covers, and a refusal
-    names the one that was asked."""
-    covers = lambda B, T, S, left, right, background, index: (
-        _covered if _narrow(S, left, right) else _wide_covered)(B, T, S, left, right, background, index)
-    entry = lambda left, right, background: ('torbi_hip_path_entropy_band_covers' if _narrow(S, left, right)
-                                             else 'torbi_hip_path_entropy_wide_band_covers')
-    return band_route.plan(trans, original, covers, entry, dict(batch=B, frames=T, states=S), index)
+def _band_routes():
+    """The band routes, as the module holds them when a call asks (a test substitutes a part by its name): a band of at most
+    64 entries is the narrow route's, bit for bit as before there was a wide route; a wider one is the wide route's."""
+    # (deliberately where it was: the width is not capped at the row, so 64 states with a wider band go to the wide route)
+    narrow = lambda states, left, right: band_route.entries(states, left, right, cap=False) <= band_route.NARROW_ENTRIES
+    return (band_route.BandRoute(_covered, 'torbi_hip_path_entropy_band_covers', _run_band, _AUTO_BAND, narrow),
+            band_route.BandRoute(_wide_covered, 'torbi_hip_path_entropy_wide_band_covers', _run_wide_band, _AUTO_WIDE_BAND,
+                                 band_route.any_width))
 
 
 def _band(route, trans, original, B, T, S, index):
-    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix `trans` (also `original`, the tensor
-    the look is remembered with) to a band route, else None for the dense route (`band_route.choose`).  A band of at most 64
-    entries runs `_run_band` under 'band' and in a class of `_AUTO_BAND` under 'auto', bit for bit as before there was a wide
-    route; a wider one runs `_run_wide_band`, under 'band' always and under 'auto' in a class of `_AUTO_WIDE_BAND`."""
-    pays = lambda left, right, background: (_band_pays if _narrow(S, left, right) else _wide_band_pays)(B, S, left, right)
-    band = band_route.choose(route, *_band_plan(trans, original, B, T, S, index), pays, "path_entropy(route='band')")
-    return None if band is None else (_run_band if _narrow(S, *band[:2]) else _run_wide_band, band)
+    """`band_route.route` over `_band_routes()`: (the route, (reach_left, reach_right, background)), or None for the dense
+    one."""
+    return band_route.route(_band_routes(), route, trans, original, dict(batch=B, frames=T, states=S), index,
+                            "path_entropy(route='band')")
 
 
 def path_entropy_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: Optional[int] = 0,
@@ -308,8 +277,8 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
         H, L, rows = _host(obs, frames, transition, uniform, initial)
         return _answer(H.to(torch.float32), L.to(torch.float32), rows.to(torch.float32), prefix)
     if band is not None:
-        run, stated = band
-        return run(obs, frames, transition, initial, *stated, None, prefix)
+        taken, stated = band
+        return taken.run(obs, frames, transition, initial, *stated, None, prefix)
     return _run(obs, frames, transition, uniform, initial, None, prefix)
 
 

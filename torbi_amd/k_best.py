@@ -121,9 +121,7 @@ def decode_k_best_banded_workspace_bytes(B: int, T: int, S: int, k: int, reach_l
     return int(_lib.load().torbi_hip_k_best_band_workspace_bytes(B, T, S, k, int(reach_left), int(reach_right)))
 
 
-def _covered(B, T, S, k, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_k_best_band_covers: the band route takes this shape, k, band and background."""
-    return bool(_lib.load().torbi_hip_k_best_band_covers(B, T, S, k, int(reach_left), int(reach_right), background, index))
+_covered = _lib.covers('torbi_hip_k_best_band_covers')            # (B, T, S, k, the band, the background)
 
 
 # (k, diagonals of 1440 states) up to which tools/k_best_probe.py measured the band route faster than the dense one by more

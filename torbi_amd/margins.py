@@ -29,6 +29,7 @@ not in `torbi_amd.__all__`.  Every top-level public function that takes an obser
 of the test suite; lifting these names to the top level belongs to a later change that adds their rows there (the same
 rows are already run from this feature's own tests).
 """
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -83,9 +84,7 @@ def max_marginals_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int
     return int(_lib.load().torbi_hip_max_marginals_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
 
 
-def _covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_max_marginals_band_covers: the band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_max_marginals_band_covers(B, T, S, int(reach_left), int(reach_right), background, index))
+_covered = _lib.covers('torbi_hip_max_marginals_band_covers')
 
 
 def _run_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
@@ -139,24 +138,26 @@ def forward_backward_max_banded(observation: torch.Tensor, batch_frames: Optiona
 # on 175 diagonals with log(tiny), the narrowest win, to 23 x).  Anything outside -- a larger batch, a wider band -- is not
 # measured and stays dense.
 _AUTO_BAND = ((1, 512, 175),)
+# (batch, states, reach_left, reach_right) lies in a class of the table: what 'auto' asks through the declaration below
+_band_pays = functools.partial(band_route.in_classes, _AUTO_BAND)
 
 
-def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_BAND)
+def _band_routes():
+    """The one band route, as the module holds it when a call asks (a test substitutes a part by its name)."""
+    return (band_route.BandRoute(_covered, 'torbi_hip_max_marginals_band_covers', _run_band, _AUTO_BAND, band_route.any_width),)
 
 
 def _band_plan(trans, original, B, T, S, index):
-    """`band_route.plan` for this feature: the shape is what torbi_hip_max_marginals_band_covers takes."""
-    return band_route.plan(trans, original, _covered, 'torbi_hip_max_marginals_band_covers', dict(batch=B, frames=T, states=S),
-                           index)
+    """`band_route.plan` alone: the band and '', or None and the reason."""
+    only = _band_routes()[0]
+    return band_route.plan(trans, original, only.covers, only.entry, dict(batch=B, frames=T, states=S), index)
 
 
 def _band(route, trans, original, B, T, S, index):
-    """The band `route` takes for the device matrix `trans` (also `original`, the tensor the look is remembered with), or
-    None for the dense route (`band_route.choose`)."""
-    return band_route.choose(route, *_band_plan(trans, original, B, T, S, index),
-                             lambda left, right, background: _band_pays(B, S, left, right), "max_marginals(route='band')")
+    """`band_route.route` over `_band_routes()`: (the route, (reach_left, reach_right, background)), or None for the dense
+    one."""
+    return band_route.route(_band_routes(), route, trans, original, dict(batch=B, frames=T, states=S), index,
+                            "max_marginals(route='band')")
 
 
 def max_marginals_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
@@ -223,7 +224,8 @@ def max_marginals(observation: torch.Tensor, batch_frames: Optional[torch.Tensor
     if gpu is None:
         return _host(obs, frames, transition, uniform, initial)
     if band is not None:
-        return _run_band(obs, frames, transition, initial, *band)
+        taken, band = band
+        return taken.run(obs, frames, transition, initial, *band)
     return _run(obs, frames, transition, uniform, initial)
 
 

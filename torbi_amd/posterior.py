@@ -103,39 +103,33 @@ def forward_backward_banded_workspace_bytes(B: int, T: int, S: int, reach_left: 
     return int(_lib.load().torbi_hip_forward_backward_band_workspace_bytes(B, T, S, int(reach_left), int(reach_right)))
 
 
-def _covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_forward_backward_band_covers: the band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_band_covers(B, T, S, int(reach_left), int(reach_right), background,
-                                                                   index))
+def _band_runner(name, need, counts=False):
+    """`run(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None,
+    item_weights=None)`: one call of the band route `name` (its workspace size: `need`) on the device of `observation`
+    (float32, contiguous, log space) and (B,) int32 `frames` there: (posterior, log_likelihood), and of a `counts` route
+    (posterior, log_likelihood, band_counts (W, S), initial_counts), the counts weighted by `item_weights` (None = all ones)."""
+    def run(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None, item_weights=None):
+        B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+        model = (transition, initial, reach_left, reach_right, background) + ((item_weights,) if counts else ())
+        rows = band_route.entries(S, reach_left, reach_right, cap=False) if counts else None
+        return _lib.run(name, observation, frames, model, _outputs(B, T, S, observation.device, rows),
+                        (need, (B, T, S, reach_left, reach_right)), (B, T, S), workspace)
+    return run
 
 
-def _run_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
-    """One call of the band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
-    `frames` there: (posterior, log_likelihood)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    return _lib.run('torbi_hip_forward_backward_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
-                    ('torbi_hip_forward_backward_band_workspace_bytes', (B, T, S, reach_left, reach_right)), (B, T, S), workspace)
-
-
-def _counts_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_forward_backward_counts_band_covers: the band counts route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_counts_band_covers(B, T, S, int(reach_left), int(reach_right),
-                                                                          background, index))
-
-
-def _run_band_counts(observation, frames, transition, initial, reach_left, reach_right, background, item_weights=None,
-                     workspace=None):
-    """One call of the band counts route (torbi_hip_forward_backward_counts_band) on the device of `observation` (float32,
-    contiguous, log space) and (B,) int32 `frames` there: (posterior, log_likelihood, band_counts (W, S), initial_counts),
-    the counts weighted by `item_weights` (None = all ones)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    W = min(reach_left, S - 1) + min(reach_right, S - 1) + 1
-    return _lib.run('torbi_hip_forward_backward_counts_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background, item_weights),
-                    _outputs(B, T, S, observation.device, W),
-                    ('torbi_hip_forward_backward_counts_band_workspace_bytes', (B, T, S, reach_left, reach_right)), (B, T, S),
-                    workspace)
+# the band routes of this module and of torbi_amd/training.py: what torbi_hip_*_covers says a route takes, and its call
+_covered = _lib.covers('torbi_hip_forward_backward_band_covers')
+_run_band = _band_runner('torbi_hip_forward_backward_band', 'torbi_hip_forward_backward_band_workspace_bytes')
+_wide_covered = _lib.covers('torbi_hip_forward_backward_wide_band_covers')
+_run_wide_band = _band_runner('torbi_hip_forward_backward_wide_band', 'torbi_hip_forward_backward_wide_band_workspace_size')
+_log_covered = _lib.covers('torbi_hip_forward_backward_log_band_covers')
+_run_log_band = _band_runner('torbi_hip_forward_backward_log_band', 'torbi_hip_forward_backward_log_band_workspace_size')
+_counts_covered = _lib.covers('torbi_hip_forward_backward_counts_band_covers')
+_run_band_counts = _band_runner('torbi_hip_forward_backward_counts_band',
+                                'torbi_hip_forward_backward_counts_band_workspace_bytes', counts=True)
+_wide_counts_covered = _lib.covers('torbi_hip_forward_backward_counts_wide_band_covers')
+_run_wide_band_counts = _band_runner('torbi_hip_forward_backward_counts_wide_band',
+                                     'torbi_hip_forward_backward_counts_wide_band_workspace_size', counts=True)
 
 
 def _banded_operands(what, dense, covers, shape, own, observation, batch_frames, reach_left, reach_right, background,
@@ -194,34 +188,6 @@ def forward_backward_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_l
     return int(_lib.load().torbi_hip_forward_backward_wide_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
 
 
-def _wide_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_forward_backward_wide_band_covers: the wide band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_wide_band_covers(B, T, S, int(reach_left), int(reach_right), background,
-                                                                        index))
-
-
-def _run_wide_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
-    """One call of the wide band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
-    `frames` there: (posterior, log_likelihood)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    return _lib.run('torbi_hip_forward_backward_wide_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
-                    ('torbi_hip_forward_backward_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
-                    workspace)
-
-
-def _run_wide_band_counts(observation, frames, transition, initial, reach_left, reach_right, background, item_weights=None,
-                          workspace=None):
-    """`_run_band_counts` on the wide route (torbi_hip_forward_backward_counts_wide_band)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    W = min(reach_left, S - 1) + min(reach_right, S - 1) + 1
-    return _lib.run('torbi_hip_forward_backward_counts_wide_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background, item_weights),
-                    _outputs(B, T, S, observation.device, W),
-                    ('torbi_hip_forward_backward_counts_wide_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
-                    workspace)
-
-
 def forward_backward_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
                                  initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
                                  workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -244,22 +210,6 @@ def forward_backward_log_banded_workspace_bytes(B: int, T: int, S: int, reach_le
     """Bytes of device scratch `forward_backward_log_banded` needs for a (B, T, S) problem with this band (the two packs of
     the band: it depends on neither B nor T)."""
     return int(_lib.load().torbi_hip_forward_backward_log_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
-
-
-def _log_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_forward_backward_log_band_covers: the log-space band route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_log_band_covers(B, T, S, int(reach_left), int(reach_right), background,
-                                                                       index))
-
-
-def _run_log_band(observation, frames, transition, initial, reach_left, reach_right, background, workspace=None):
-    """One call of the log-space band route on the device of `observation` (float32, contiguous, log space) and (B,) int32
-    `frames` there: (posterior, log_likelihood)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    return _lib.run('torbi_hip_forward_backward_log_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background), _outputs(B, T, S, observation.device),
-                    ('torbi_hip_forward_backward_log_band_workspace_size', (B, T, S, reach_left, reach_right)), (B, T, S),
-                    workspace)
 
 
 def forward_backward_log_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -289,16 +239,17 @@ _LOG_HOST = 'gpu=None computes any matrix in float64 on the CPU'
 
 
 def _log_band_run(route, trans, original, B, T, S, index):
-    """(`_run_log_band`, (reach_left, reach_right, background)) for `arithmetic='log'`: 'auto' and 'band' take the log-space
-    band route for any band it covers -- an opt-in for correctness, so no table of measured classes --, and 'dense' or a
+    """(the route, (reach_left, reach_right, background)) for `arithmetic='log'`, which declares one band route, for any band
+    it covers -- an opt-in for correctness, so no table of measured classes: 'auto' and 'band' take it, and 'dense' or a
     matrix with no covered band raises: a GPU request never silently changes arithmetic."""
     if route == 'dense':
         raise RuntimeError(f"{_LOG_ONLY}, and route='dense' asks for the dense one ({_LOG_HOST})")
-    band, why = band_route.plan(trans, original, _log_covered, 'torbi_hip_forward_backward_log_band_covers',
-                                dict(batch=B, frames=T, states=S), index)
+    only = band_route.BandRoute(_log_covered, 'torbi_hip_forward_backward_log_band_covers', _run_log_band, None,
+                                band_route.any_width)
+    band, why = band_route.plan(trans, original, only.covers, only.entry, dict(batch=B, frames=T, states=S), index)
     if band is None:
         raise RuntimeError(f'{_LOG_ONLY}: {why} ({_LOG_HOST})')
-    return _run_log_band, band
+    return only, band
 
 
 # Where 'auto' takes a band that only the wide route covers: the classes of (batch, band width as a share of the row) that
@@ -310,38 +261,20 @@ def _log_band_run(route, trans, original, B, T, S, index):
 _AUTO_WIDE_BAND = ((1, 4096, 175),)
 
 
-def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_WIDE_BAND)
-
-
-def _band(route, trans, original, B, T, S, index):
-    """(reach_left, reach_right, background) where `route` sends the device matrix `trans` (`inputs.device_matrix`; also
-    `original`, the tensor the look is remembered with) to the NARROW band route alone ('auto' takes every band
-    torbi_hip_forward_backward_band_covers takes), else None.  `state_posteriors` asks `_band_run`, which knows both band
-    routes; this is the planner of the narrow one as tests/test_band_route_cpu.py holds it to the other features'."""
-    if route == 'dense':
-        return None
-    plan = band_route.plan(trans, original, _covered, 'torbi_hip_forward_backward_band_covers', dict(batch=B, frames=T, states=S),
-                           index)
-    return band_route.choose(route, *plan, None, "state_posteriors(route='band')")
+def _band_routes():
+    """The band routes of the scaled arithmetic, as the module holds them when a call asks (a test substitutes a part by its
+    name).  A band of at most 64 entries is the narrow route's under 'auto' and 'band' alike (every class that was measured
+    won), bit for bit as before there was a wide route; a wider one is the wide route's."""
+    return (band_route.BandRoute(_covered, 'torbi_hip_forward_backward_band_covers', _run_band, None, band_route.narrow),
+            band_route.BandRoute(_wide_covered, 'torbi_hip_forward_backward_wide_band_covers', _run_wide_band, _AUTO_WIDE_BAND,
+                                 band_route.any_width))
 
 
 def _band_run(route, trans, original, B, T, S, index):
-    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix to a band route, else None.  One
-    plan over both routes' covers, so one look at the matrix.  A band torbi_hip_forward_backward_band_covers takes runs
-    `_run_band` under 'auto' and 'band', bit for bit as before there was a wide route; a band only
-    torbi_hip_forward_backward_wide_band_covers takes runs `_run_wide_band`, under 'band' always and under 'auto' in a class
-    of `_AUTO_WIDE_BAND`."""
-    if route == 'dense':
-        return None
-    either = lambda *call: _covered(*call) or _wide_covered(*call)
-    band, why = band_route.plan(trans, original, either, 'torbi_hip_forward_backward_wide_band_covers',
-                                dict(batch=B, frames=T, states=S), index)
-    narrow = band is not None and _covered(B, T, S, *band, index)
-    pays = None if narrow else lambda left, right, background: _wide_band_pays(B, S, left, right)
-    band = band_route.choose(route, band, why, pays, "state_posteriors(route='band')")
-    return None if band is None else (_run_band if narrow else _run_wide_band, band)
+    """`band_route.route` over `_band_routes()`: (the route, (reach_left, reach_right, background)), or None for the dense
+    one."""
+    return band_route.route(_band_routes(), route, trans, original, dict(batch=B, frames=T, states=S), index,
+                            "state_posteriors(route='band')")
 
 
 def posterior_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
@@ -406,8 +339,8 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     plan = _log_band_run if log_band else _band_run
     band = None if uniform is not None else plan(route, transition, transition, B, T, S, device.index or 0)
     if band is not None:
-        run, band = band
-        return run(obs, frames, transition, initial, *band)
+        taken, band = band
+        return taken.run(obs, frames, transition, initial, *band)
     return _run(obs, frames, transition, uniform, initial)
 
 

@@ -16,6 +16,7 @@ the band, up to 64 in-band entries in a matrix row; csrc/sample_wide_band.hpp be
 (`forward_sample_wide_banded`) takes bands of up to 512.  `gpu=None` runs the dense rule in float64 with torch CPU ops.
 SAMPLING.md has the contract, the kernels and the numbers.
 """
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -97,20 +98,23 @@ def forward_sample_banded_workspace_bytes(B: int, T: int, S: int, draws: int, re
     return int(_lib.load().torbi_hip_sample_band_workspace_bytes(B, T, S, int(draws), int(reach_left), int(reach_right)))
 
 
-def _covered(B, T, S, N, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_sample_band_covers: the band route takes this shape, number of draws, band and background."""
-    return bool(_lib.load().torbi_hip_sample_band_covers(B, T, S, int(N), int(reach_left), int(reach_right), background,
-                                                         index))
+def _band_runner(name, need):
+    """`run(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None)`: one
+    call of the band route `name` (its workspace size: `need`) on the device of `observation` (float32, contiguous, log space)
+    and (B,) int32 `frames` there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
+    def run(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
+        B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+        N = _check_uniforms(uniforms, B, T)
+        return _lib.run(name, observation, frames, (transition, initial, reach_left, reach_right, background, uniforms),
+                        _outputs(B, N, T, observation.device), (need, (B, T, S, N, reach_left, reach_right)), (B, T, S, N),
+                        workspace)
+    return run
 
 
-def _run_band(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
-    """One call of the band route on the device of `observation` (float32, contiguous, log space) and (B,) int32 `frames`
-    there: (indices (B, N, T) int32, log_likelihood (B,) float32)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    N = _check_uniforms(uniforms, B, T)
-    return _lib.run('torbi_hip_sample_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background, uniforms), _outputs(B, N, T, observation.device),
-                    ('torbi_hip_sample_band_workspace_bytes', (B, T, S, N, reach_left, reach_right)), (B, T, S, N), workspace)
+_covered = _lib.covers('torbi_hip_sample_band_covers')
+_run_band = _band_runner('torbi_hip_sample_band', 'torbi_hip_sample_band_workspace_bytes')
+_wide_covered = _lib.covers('torbi_hip_sample_wide_band_covers')
+_run_wide_band = _band_runner('torbi_hip_sample_wide_band', 'torbi_hip_sample_wide_band_workspace_size')
 
 
 def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -154,21 +158,6 @@ def forward_sample_wide_banded_workspace_bytes(B: int, T: int, S: int, draws: in
     return int(_lib.load().torbi_hip_sample_wide_band_workspace_size(B, T, S, int(draws), int(reach_left), int(reach_right)))
 
 
-def _wide_covered(B, T, S, N, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_sample_wide_band_covers: the wide band route takes this shape, number of draws, band and background."""
-    return bool(_lib.load().torbi_hip_sample_wide_band_covers(B, T, S, int(N), int(reach_left), int(reach_right), background,
-                                                              index))
-
-
-def _run_wide_band(observation, frames, transition, initial, uniforms, reach_left, reach_right, background, workspace=None):
-    """`_run_band` on the wide route (torbi_hip_sample_wide_band)."""
-    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
-    N = _check_uniforms(uniforms, B, T)
-    return _lib.run('torbi_hip_sample_wide_band', observation, frames,
-                    (transition, initial, reach_left, reach_right, background, uniforms), _outputs(B, N, T, observation.device),
-                    ('torbi_hip_sample_wide_band_workspace_size', (B, T, S, N, reach_left, reach_right)), (B, T, S, N), workspace)
-
-
 def forward_sample_wide_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
                                initial: torch.Tensor, uniforms: torch.Tensor, reach_left: int, reach_right: int,
                                background: float = -math.inf, workspace: Optional[torch.Tensor] = None
@@ -197,54 +186,37 @@ def forward_sample_wide_banded(observation: torch.Tensor, batch_frames: Optional
 # 23 diagonals of 1440 states in both forms of the background: 1, 8 and 512 items at one draw (3.5 x, 3.4 x, 5.8 x) and 512
 # items at 16 draws (6.0 x).  Anything outside -- a larger batch, a wider band, more draws -- is not measured and stays dense.
 _AUTO_BAND = ((1, 512, 23, 1), (512, 512, 23, 16))
-
-
-def _band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals) and draws <= most
-               for low, high, diagonals, most in _AUTO_BAND)
-
-
 # Where 'auto' takes a band that only the wide route covers: the classes that tools/sample_probe.py --wide-band measured
 # faster than the dense call on the same inputs, the wide route's slowest call under the dense route's fastest (SAMPLING.md,
 # "Wide band route", timing).  Each entry as in `_AUTO_BAND`.  Measured at 500 frames x 1440 states on 175 diagonals, -inf and
 # log(tiny) outside: 1, 8, 64, 512 and 4096 items at 1 and at 16 draws; the wide route won all twenty (1.4 x at one item, 2.9 x at
 # 512, 3.4 x at 4096).  A wider band, a larger batch or more draws are not measured and stay dense.
 _AUTO_WIDE_BAND = ((1, 4096, 175, 16),)
+# (batch, states, reach_left, reach_right, draws) lies in a class of the table: what 'auto' asks through the declaration below
+_band_pays = functools.partial(band_route.in_classes, _AUTO_BAND)
+_wide_band_pays = functools.partial(band_route.in_classes, _AUTO_WIDE_BAND)
 
 
-def _wide_band_pays(batch: int, states: int, reach_left: int, reach_right: int, draws: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals) and draws <= most
-               for low, high, diagonals, most in _AUTO_WIDE_BAND)
+def _band_routes():
+    """The band routes, as the module holds them when a call asks (a test substitutes a part by its name), split like
+    `posterior._band_routes()`: a band of at most 64 entries is the narrow route's, bit for bit as before there was a wide
+    route; a wider one is the wide route's."""
+    return (band_route.BandRoute(_covered, 'torbi_hip_sample_band_covers', _run_band, _AUTO_BAND, band_route.narrow),
+            band_route.BandRoute(_wide_covered, 'torbi_hip_sample_wide_band_covers', _run_wide_band, _AUTO_WIDE_BAND,
+                                 band_route.any_width))
 
 
 def _band_plan(trans, original, B, T, S, N, index):
-    """`band_route.plan` for this feature: the shape is what torbi_hip_sample_band_covers takes."""
-    return band_route.plan(trans, original, _covered, 'torbi_hip_sample_band_covers', dict(batch=B, frames=T, states=S, draws=N),
-                           index)
-
-
-def _band(route, trans, original, B, T, S, N, index):
-    """The band `route` takes for the device matrix `trans` (`inputs.device_matrix`; also `original`, the tensor the look is
-    remembered with), or None for the dense route (`band_route.choose`)."""
-    return band_route.choose(route, *_band_plan(trans, original, B, T, S, N, index),
-                             lambda left, right, background: _band_pays(B, S, left, right, N), "sample_paths(route='band')")
+    """`band_route.plan` alone, for the narrow route: the band and '', or None and the reason."""
+    narrow = _band_routes()[0]
+    return band_route.plan(trans, original, narrow.covers, narrow.entry, dict(batch=B, frames=T, states=S, draws=N), index)
 
 
 def _band_run(route, trans, original, B, T, S, N, index):
-    """(run, (reach_left, reach_right, background)) where `route` sends the device matrix to a band route, else None
-    (`posterior._band_run`'s steps).  One plan over both routes' covers, so one look at the matrix.  A band
-    torbi_hip_sample_band_covers takes runs `_run_band` where it did before there was a wide route, bit for bit: under
-    'band', and under 'auto' in a class of `_AUTO_BAND`.  A band only torbi_hip_sample_wide_band_covers takes runs
-    `_run_wide_band`, under 'band' always and under 'auto' in a class of `_AUTO_WIDE_BAND`."""
-    if route == 'dense':
-        return None
-    either = lambda *call: _covered(*call) or _wide_covered(*call)
-    band, why = band_route.plan(trans, original, either, 'torbi_hip_sample_wide_band_covers',
-                                dict(batch=B, frames=T, states=S, draws=N), index)
-    narrow = band is not None and _covered(B, T, S, N, *band, index)
-    pays = lambda left, right, background: (_band_pays if narrow else _wide_band_pays)(B, S, left, right, N)
-    band = band_route.choose(route, band, why, pays, "sample_paths(route='band')")
-    return None if band is None else (_run_band if narrow else _run_wide_band, band)
+    """`band_route.route` over `_band_routes()`: (the route, (reach_left, reach_right, background)), or None for the dense
+    one."""
+    return band_route.route(_band_routes(), route, trans, original, dict(batch=B, frames=T, states=S, draws=N), index,
+                            "sample_paths(route='band')")
 
 
 def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, draws: int = 1, gpu: int = 0,
@@ -318,8 +290,8 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         indices, L = _host(obs, frames, transition, uniform, initial.to(torch.float32), uniforms)
         return indices.to(torch.int32), L.to(torch.float32)
     if band is not None:
-        run, band = band
-        return run(obs, frames, transition, initial, uniforms, *band)
+        taken, band = band
+        return taken.run(obs, frames, transition, initial, uniforms, *band)
     return _run(obs, frames, transition, uniform, initial, uniforms)
 
 

@@ -26,9 +26,7 @@ from .stream_ring import INITIAL_CAPACITY
 ROUTES = band_route.ROUTES
 
 
-def _covered(batch, states, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_stream_band_covers: the band route takes this many streams, this band and background."""
-    return bool(_lib.load().torbi_hip_stream_band_covers(int(batch), states, reach_left, reach_right, background, index))
+_covered = _lib.covers('torbi_hip_stream_band_covers')            # (streams, states, the band, the background)
 
 
 def _band_plan(trans: torch.Tensor, original: torch.Tensor, batch: int, states: int, index: int

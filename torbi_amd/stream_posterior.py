@@ -12,6 +12,7 @@ take the band route on the device (csrc/stream_posterior_band.hpp behind torbi_h
 "Streaming posteriors: band route"): a step costs the band, not the matrix.  `route` and `band` choose.
 """
 import ctypes
+import functools
 import math
 import operator
 from typing import List, Optional, Sequence, Tuple
@@ -29,17 +30,8 @@ ROUTES = band_route.ROUTES
 # of the background at lag 8: 1 stream in one-frame pushes (27 x), 8 streams in pushes of 15 (61 x), 512 streams in pushes of
 # 100 (33 x).  Anything outside -- a larger batch, a band that holds more of a row -- is not measured and stays dense.
 _AUTO_BAND = ((1, 512, 23),)
-
-
-def _covered(batch, states, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_stream_smooth_band_covers: the band route takes this many streams, this band and background."""
-    return bool(_lib.load().torbi_hip_stream_smooth_band_covers(int(batch), int(states), reach_left, reach_right, background,
-                                                                index))
-
-
-def _band_pays(batch: int, states: int, reach_left: int, reach_right: int) -> bool:
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_BAND)
+_band_pays = functools.partial(band_route.in_classes, _AUTO_BAND)         # (batch, states, reach_left, reach_right)
+_covered =_lib.covers('torbi_hip_stream_smooth_band_covers')     # (streams, states, the band, the background)
 
 
 def _band_plan(trans: torch.Tensor, original: torch.Tensor, batch: int, states: int, index: int):

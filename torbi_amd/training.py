@@ -20,9 +20,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, band_route, inputs
-from .posterior import (_banded_operands, _counts_covered, _host, _operands, _run, _run_band, _run_band_counts, _run_wide_band,
-                        _run_wide_band_counts, _shapes)
+from . import _lib, band_route, inputs, posterior
+from .posterior import (_banded_operands, _counts_covered, _host, _operands, _run, _run_band_counts, _run_wide_band_counts,
+                        _shapes, _wide_counts_covered)
 
 ROUTES = band_route.ROUTES
 
@@ -89,7 +89,7 @@ def forward_backward_counts_banded(observation: torch.Tensor, batch_frames: Opti
     obs, frames, left, right, background = _banded_operands(
         'forward_backward_counts_banded', 'forward_backward_counts', _counts_covered, shape, (), observation, batch_frames,
         reach_left, reach_right, background, item_weights)
-    return _run_band_counts(obs, frames, transition, initial, left, right, background, item_weights, workspace)
+    return _run_band_counts(obs, frames, transition, initial, left, right, background, workspace, item_weights)
 
 
 def expected_counts_wide_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
@@ -122,13 +122,7 @@ def forward_backward_counts_wide_banded(observation: torch.Tensor, batch_frames:
     obs, frames, left, right, background = _banded_operands(
         'forward_backward_counts_wide_banded', 'forward_backward_counts', _wide_counts_covered, shape, (), observation,
         batch_frames, reach_left, reach_right, background, item_weights)
-    return _run_wide_band_counts(obs, frames, transition, initial, left, right, background, item_weights, workspace)
-
-
-def _wide_counts_covered(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    """torbi_hip_forward_backward_counts_wide_band_covers: the wide band counts route takes this shape, band and background."""
-    return bool(_lib.load().torbi_hip_forward_backward_counts_wide_band_covers(B, T, S, int(reach_left), int(reach_right),
-                                                                               background, index))
+    return _run_wide_band_counts(obs, frames, transition, initial, left, right, background, workspace, item_weights)
 
 
 def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right: int) -> torch.Tensor:
@@ -157,47 +151,31 @@ def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right
 # frames x 1440 states on 175 diagonals, -inf outside: 1, 8, 64, 512 and 4096 items; the wide route won all five (1.7 x at one
 # item, 3.6 x at 512 and at 4096).  A wider band or a larger batch is not measured and stays dense.
 _AUTO_WIDE_COUNTS = ((1, 4096, 175),)
-_NARROW_ENTRIES = 64                              # in-band entries of a row the narrow band routes take
+_COUNTS_ENTRY = ('the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers up to 64 '
+                 'in-band entries, torbi_hip_forward_backward_counts_wide_band_covers beyond)')
 
 
-def _is_wide(S, reach_left, reach_right) -> bool:
-    """The band has more in-band entries in a row than the narrow routes take: its counts are the wide route's."""
-    return min(min(reach_left, S - 1) + min(reach_right, S - 1) + 1, S) > _NARROW_ENTRIES
+def _minus_inf_outside(covers):
+    """`covers` behind the condition of every band counts route: the matrix is -inf outside the band, so that the dense
+    (S, S) result is exactly zero there.  `covers` is not asked about a finite background."""
+    return lambda *call: call[-2] == -math.inf and covers(*call)
 
 
-def _band_runs(S, reach_left, reach_right):
-    """(posteriors, counts): the `_run_*` pair of the route that takes this band."""
-    return (_run_wide_band, _run_wide_band_counts) if _is_wide(S, reach_left, reach_right) else (_run_band, _run_band_counts)
+def _counts_routes():
+    """The band counts routes, as the module holds them when a call asks, split like `posterior._band_routes()` (so a band's
+    counts and its posteriors come from the same route).  A band of at most 64 entries whose plane does not fit is the narrow
+    route's to turn down: it stays dense under 'auto' and raises under 'band', although the wide route would cover it."""
+    return (band_route.BandRoute(_minus_inf_outside(_counts_covered), _COUNTS_ENTRY, _run_band_counts, None, band_route.narrow),
+            band_route.BandRoute(_minus_inf_outside(_wide_counts_covered), _COUNTS_ENTRY, _run_wide_band_counts,
+                                 _AUTO_WIDE_COUNTS, band_route.any_width))
 
 
 def _counts_band(trans, original, B, T, S, index, route):
     """(reach_left, reach_right) when `route` sends the counts of the device matrix `trans` (`inputs.plain_matrix`;
-    `original`: the tensor the look is remembered with) to a band route, else None: the matrix is -inf outside a band (so
-    the dense (S, S) result is exactly zero there), the band's route covers it -- torbi_hip_forward_backward_counts_band_covers
-    for at most 64 in-band entries, torbi_hip_forward_backward_counts_wide_band_covers for more (`_band_runs` says which) --
-    and, for 'auto', the class was measured faster."""
-    if route == 'dense':
-        return None
-    plan = band_route.plan(trans, original, _counts_take,
-                           'the band counts route (-inf outside the band, torbi_hip_forward_backward_counts_band_covers up to 64 '
-                           'in-band entries, torbi_hip_forward_backward_counts_wide_band_covers beyond)',
-                           dict(batch=B, frames=T, states=S), index)
-    band = band_route.choose(route, *plan, lambda left, right, background: _auto_takes(B, S, left, right), "route='band'")
-    return None if band is None else band[:2]
-
-
-def _auto_takes(batch, states, reach_left, reach_right) -> bool:
-    if not _is_wide(states, reach_left, reach_right):
-        return True
-    return any(low <= batch <= high and band_route.share_within(states, reach_left, reach_right, diagonals)
-               for low, high, diagonals in _AUTO_WIDE_COUNTS)
-
-
-def _counts_take(B, T, S, reach_left, reach_right, background, index=0) -> bool:
-    if background != -math.inf:
-        return False
-    covers = _wide_counts_covered if _is_wide(S, reach_left, reach_right) else _counts_covered
-    return covers(B, T, S, reach_left, reach_right, background, index)
+    `original`: the tensor the look is remembered with) to a band route -- `band_route.route` over `_counts_routes()`; the
+    background is -inf, and `band_route.taking` says which route runs the band --, else None."""
+    taken = band_route.route(_counts_routes(), route, trans, original, dict(batch=B, frames=T, states=S), index, "route='band'")
+    return None if taken is None else taken[1][:2]
 
 
 def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
@@ -260,7 +238,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     else:
         band = _counts_band(transition, transition, B, T, S, device.index or 0, route)
     if band is not None:
-        _, L, Xb, I = _band_runs(S, *band)[1](obs, frames, transition, initial, band[0], band[1], -math.inf)
+        _, L, Xb, I = band_route.taking(_counts_routes(), S, *band).run(obs, frames, transition, initial, *band, -math.inf)
         return band_counts_to_dense(Xb, band[0], band[1]), I, L
     _, L, X, I = _run(obs, frames, transition, None, initial, counts=True)
     return X, I, L
@@ -287,7 +265,9 @@ class _LogLikelihood(torch.autograd.Function):
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
             ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
             if ctx.band is not None:
-                gamma, L = _band_runs(S, *ctx.band)[0](obs, frames, trans, init, ctx.band[0], ctx.band[1], -math.inf)
+                # (the posteriors of the route whose counts the backward takes: the two declarations split alike)
+                forward = band_route.taking(posterior._band_routes(), S, *ctx.band)
+                gamma, L = forward.run(obs, frames, trans, init, *ctx.band, -math.inf)
             else:
                 gamma, L = _run(obs, frames, trans, None, init)
             ctx.save_for_backward(obs, frames, trans, init, gamma, L)
@@ -311,8 +291,8 @@ class _LogLikelihood(torch.autograd.Function):
             if need_t:
                 if ctx.band is not None:
                     left, right = ctx.band
-                    _, _, Xb, I = _band_runs(trans.shape[0], left, right)[1](obs, frames, trans, init, left, right, -math.inf,
-                                                                             g.contiguous())
+                    backward = band_route.taking(_counts_routes(), trans.shape[0], left, right)
+                    _, _, Xb, I = backward.run(obs, frames, trans, init, left, right, -math.inf, item_weights=g.contiguous())
                     X = band_counts_to_dense(Xb, left, right)
                 elif obs.is_cuda:
                     _, _, X, I = _run(obs, frames, trans, None, init, counts=True, item_weights=g.contiguous())

@@ -805,6 +805,34 @@ int torbi_hip_forward_backward_counts_wide_band(const float *observation, const 
                                                 size_t workspace_bytes, int B, int T, int S, int device, void *stream);
 
 /*
+ * Expected counts in log space on a band (added within ABI 17): torbi_hip_forward_backward_counts_wide_band's arguments,
+ * outputs, skipping rule, broken-promise rule and in-band-only rule for a finite background, for every band
+ * torbi_hip_forward_backward_log_band covers, computed on logarithms (csrc/counts_log_band.hpp): the route for inputs on
+ * which the scaled float32 recurrence flushes states (left-to-right matrices, data that does not yet match the model).
+ * posterior_out and loglik_out are bit for bit those of torbi_hip_forward_backward_log_band on the same inputs.  The passes'
+ * launch also stores, in base-2 logs, la_t and w_t = o_t + y_t - (M_t + Q_t + log2 sum_j 2^(q_t[j] - Q_t)) per (item, frame),
+ * and one launch sums xi_t(j, i) = 2^(A[j,i] log2 e + la_{t-1}[i] + w_t[j]) over the band with one exponential per term: a
+ * workgroup owns 64 next states, up to 128 diagonals and one of KS contiguous shares of the (item, frame) rows, KS =
+ * _shares(B, T, S, reach_left, reach_right), a function of the shape alone (0 for arguments out of range); the shares are
+ * added in order.  The bits depend on the inputs and the shape only; no float atomics.
+ *
+ * _covers: what torbi_hip_forward_backward_log_band_covers answers.  It, _workspace_size and _shares answer without a device.
+ * workspace: torbi_hip_forward_backward_counts_log_band_workspace_size(...) bytes (256 for arguments out of range), no
+ * initialisation and no alignment: the log route's regions, then the operand rows LAop and Wop, B x T x (S up to 4) fp32
+ * each, the row maxima B x T fp32, then KS planes of S x W fp32, every region starting on a multiple of 256 bytes.
+ * Six launches per call whatever T is, no host synchronisation.  Errors as torbi_hip_forward_backward_counts_band.
+ */
+int torbi_hip_forward_backward_counts_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                      int device);
+size_t torbi_hip_forward_backward_counts_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_counts_log_band_shares(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_forward_backward_counts_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                               const float *initial, int reach_left, int reach_right, float background,
+                                               const float *item_weights, float *posterior_out, float *loglik_out,
+                                               float *band_counts_out, float *initial_counts_out, void *workspace,
+                                               size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
+/*
  * k-best Viterbi decoding (added within ABI 17): the k best state sequences of every item with their exact scores, on the
  * model torbi_hip_viterbi_decode decodes (torbi_amd/k_best.py, KBEST.md).  Inputs as there: observation (B, T, S) log
  * scores, batch_frames (B,) int32 (clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log; 1 <= k <= 32.

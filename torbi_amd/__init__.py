@@ -26,8 +26,9 @@ from .posterior import (forward_backward, forward_backward_banded, forward_backw
                         forward_backward_log_banded, forward_backward_log_banded_workspace_bytes, forward_backward_wide_banded, forward_backward_wide_banded_workspace_bytes,
                         forward_backward_workspace_bytes, posterior_route, state_posteriors)
 from .training import (band_counts_to_dense, counts_route, expected_counts, expected_counts_banded_workspace_bytes,
-                       expected_counts_wide_banded_workspace_bytes, expected_counts_workspace_bytes, forward_backward_counts,
-                       forward_backward_counts_banded, forward_backward_counts_wide_banded, log_likelihood)
+                       expected_counts_log_banded_workspace_bytes, expected_counts_wide_banded_workspace_bytes,
+                       expected_counts_workspace_bytes, forward_backward_counts, forward_backward_counts_banded,
+                       forward_backward_counts_log_banded, forward_backward_counts_wide_banded, log_likelihood)
 from .k_best import (best_paths, decode_k_best, decode_k_best_banded, decode_k_best_banded_workspace_bytes,
                      decode_k_best_workspace_bytes, k_best_route)
 from .sampling import (forward_sample, forward_sample_banded, forward_sample_banded_workspace_bytes,

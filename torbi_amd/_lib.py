@@ -165,6 +165,15 @@ SYMBOLS = {
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p,
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
         _c.c_void_p]),
+    'torbi_hip_forward_backward_counts_log_band_covers': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                                                    _c.c_float, _c.c_int]),
+    'torbi_hip_forward_backward_counts_log_band_workspace_size': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                                                                _c.c_int]),
+    'torbi_hip_forward_backward_counts_log_band_shares': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_forward_backward_counts_log_band': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p,
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+        _c.c_void_p]),
     'torbi_hip_k_best_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     'torbi_hip_k_best': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,

@@ -283,13 +283,25 @@ __device__ __forceinline__ void from_waves(const Tile<G> &tile, int which, float
     }
 }
 
-// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, plan) ----
-template <int G>
+// What the OPS arm of the kernel leaves for the counts (counts_log_band.hpp), all in base-2 logs; rows t >= F_b are never
+// written:
+//     LAop[b][t][i] = la_t[i]                                          rows of S4 floats (the backward pass overwrites `post`)
+//     Mrow[b][t]    = M_t
+//     Wop[b][t][j]  = o_t[j] log2e + y_t[j] - (M_t + Q_t + log2 sum_j 2^(q_t[j] - Q_t))      q_t = la_t + y_t, Q_t its maximum
+// so that xi_t(j, i) = 2^(A[j,i] log2e + LAop[t-1][i] + Wop[t][j]): la_{t-1} and y_t stand for alpha_{t-1} and beta_t up to
+// constants of their rows, gamma_t[j] = 2^(q_t[j] - Q_t) / sum fixes the product of both constants against the likelihood at
+// frame t, and the rows t - 1 and t differ by M_t.  Summed over i it is gamma_t[j].
+struct Operands { float *LAop, *Wop, *Mrow; };
+
+// ---- both passes of G items per workgroup; grid ceil(B / G), dynamic LDS lds_bytes(G, plan).  OPS: also the operand rows
+// above; `false` is the kernel as it was, and `true` adds stores and touches no value that `false` computes ----
+template <int G, bool OPS = false>
 __global__ __launch_bounds__(kThreads) void fb_log_band_kernel(const float *__restrict__ obs, const int32_t *__restrict__ frames,
                                                                const float *__restrict__ initial, const float *__restrict__ Pf,
                                                                const float *__restrict__ Pb, const int32_t *__restrict__ flag,
                                                                float *__restrict__ post, float *__restrict__ loglik,
-                                                               float background, Plan p, int B, int T, int S) {
+                                                               float background, Plan p, int B, int T, int S,
+                                                               Operands ops = Operands{nullptr, nullptr, nullptr}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     Tile<G> tile(lds_raw, p);
     const int tid = threadIdx.x, stride = p.stride;
@@ -350,6 +362,7 @@ __global__ __launch_bounds__(kThreads) void fb_log_band_kernel(const float *__re
             for (int g = 0; g < G; ++g) {
                 top[g] = ref_of(top[g]);
                 if (tid == 0 && t < F[g]) tile.Msum[g] += (double)top[g];
+                if (OPS && tid == 0 && t < F[g]) ops.Mrow[(size_t)(b0 + g) * T + t] = top[g];
                 sum[g] = 0.f;
             }
             for (int j = tid; j < S; j += kThreads)
@@ -359,6 +372,7 @@ __global__ __launch_bounds__(kThreads) void fb_log_band_kernel(const float *__re
                     const float la = cur[g * stride + j] - top[g];
                     cur[g * stride + j] = la;
                     post[((size_t)(b0 + g) * T + t) * S + j] = la;
+                    if (OPS) ops.LAop[((size_t)(b0 + g) * T + t) * p.S4 + j] = la;
                     sum[g] += ex2(la);
                 }
             to_waves<G, false>(tile, 1, sum);
@@ -440,11 +454,18 @@ __global__ __launch_bounds__(kThreads) void fb_log_band_kernel(const float *__re
             to_waves<G, false>(tile, 1, sumr);
             barrier();
             from_waves<G, false>(tile, 4, sumq);
+            float shift[OPS ? G : 1];                                            // what turns the row's r into Wop
+            if (OPS) {
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    shift[g] = t < F[g] ? topr[g] - (ops.Mrow[(size_t)(b0 + g) * T + t] + topq[g] + lg2(sumq[g])) : 0.f;
+            }
             for (int j = tid; j < S; j += kThreads)
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     if (t >= F[g]) continue;
                     post[((size_t)(b0 + g) * T + t) * S + j] = isfinite(tile.L[g]) ? qrow[(size_t)g * p.S4 + j] / sumq[g] : NAN;
+                    if (OPS) ops.Wop[((size_t)(b0 + g) * T + t) * p.S4 + j] = cur[g * stride + j] + shift[g];
                 }
             barrier();                                                           // (phase A writes the slices the line above reads)
         }

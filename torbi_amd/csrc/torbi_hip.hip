@@ -49,6 +49,7 @@
 #include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
 #include "counts_wide_band.hpp"
+#include "counts_log_band.hpp"
 #include "counts.hpp"
 #include "k_best.hpp"
 #include "k_best_band.hpp"
@@ -3075,6 +3076,31 @@ int torbi_hip_forward_backward_log_band_tile(int B, int S, int reach_left, int r
     return fb_log_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
 }
 
+// What both log entries launch: the pack with the check of the promise, then both passes of every item in one launch.  With
+// `ops` (the counts entry) the instance that also stores the operand rows of the counts.
+static hipError_t fb_log_band_passes(const fbl::Layout &l, const float *observation, const int32_t *batch_frames,
+                                     const float *transition, const float *initial, float background, float *posterior_out,
+                                     float *loglik_out, fbl::Operands ops, int B, int T, int S, int device, hipStream_t st) {
+    const hipError_t e = fbl::pack_and_verify(transition, l, background, S, st);
+    if (e != hipSuccess) return e;
+    int G = fb_log_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_LOG_BAND_ITEMS")) {       // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2 || g == 4) && fbl::lds_bytes(g, l) <= (size_t)fbl::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = fbl::lds_bytes(G, l);
+    const dim3 grid((B + G - 1) / G), block(fbl::kThreads);
+    const fbw::Plan &plan = l;
+    return by_value<4, 2, 1>(G, [&](auto g) { return by_flag(ops.Wop != nullptr, [&](auto with_ops) {
+        auto *kernel = &fbl::fb_log_band_kernel<decltype(g)::value, decltype(with_ops)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, initial, l.P[0], l.P[1], l.flag, posterior_out,
+                           loglik_out, background, plan, B, T, S, ops);
+        return hipGetLastError();
+    }); });
+}
+
 int torbi_hip_forward_backward_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
                                         const float *initial, int reach_left, int reach_right, float background,
                                         float *posterior_out, float *loglik_out, void *workspace, size_t workspace_bytes,
@@ -3088,25 +3114,61 @@ int torbi_hip_forward_backward_log_band(const float *observation, const int32_t 
     const fbl::Layout l = fbl::layout(fb_base(workspace), S, reach_left, reach_right);
     const DeviceGuard guard(device);
     if (guard.err != hipSuccess) return (int)guard.err;
+    return (int)fb_log_band_passes(l, observation, batch_frames, transition, initial, background, posterior_out, loglik_out,
+                                   fbl::Operands{nullptr, nullptr, nullptr}, B, T, S, device, static_cast<hipStream_t>(stream));
+}
+
+// ---- expected counts in log space on a band (counts_log_band.hpp) ----
+
+int torbi_hip_forward_backward_counts_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background,
+                                                      int device) {
+    return torbi_hip_forward_backward_log_band_covers(B, T, S, reach_left, reach_right, background, device);
+}
+
+size_t torbi_hip_forward_backward_counts_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fblc::counts_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_forward_backward_counts_log_band_shares(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return fblc::counts_plan(B, T, S, fbw::plan_of(S, reach_left, reach_right)).shares;
+}
+
+int torbi_hip_forward_backward_counts_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                               const float *initial, int reach_left, int reach_right, float background,
+                                               const float *item_weights, float *posterior_out, float *loglik_out,
+                                               float *band_counts_out, float *initial_counts_out, void *workspace,
+                                               size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && posterior_out && loglik_out && band_counts_out &&
+            initial_counts_out && workspace,
+        torbi_hip_forward_backward_counts_log_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_forward_backward_counts_log_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t e = fbl::pack_and_verify(transition, l, background, S, st);
+    const fblc::CountsLayout l = fblc::counts_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    hipError_t e = fb_log_band_passes(l, observation, batch_frames, transition, initial, background, posterior_out, loglik_out,
+                                      fbl::Operands{l.LAop, l.Wop, l.Mrow}, B, T, S, device, st);
     if (e != hipSuccess) return (int)e;
-    int G = fb_log_band_tile(B, l, cu_count(device));
-    if (const char *forced = getenv("TORBI_HIP_LOG_BAND_ITEMS")) {       // (include/torbi_hip.h: the probe's timings per G)
-        const int g = atoi(forced);
-        if ((g == 1 || g == 2 || g == 4) && fbl::lds_bytes(g, l) <= (size_t)fbl::kMaxLdsBytes) G = g;
-    }
-    const size_t lds = fbl::lds_bytes(G, l);
-    const dim3 grid((B + G - 1) / G), block(fbl::kThreads);
-    const fbw::Plan &plan = l;
-    return (int)by_value<4, 2, 1>(G, [&](auto g) {
-        auto *kernel = &fbl::fb_log_band_kernel<decltype(g)::value>;
-        const hipError_t le = ensure_dynamic_lds(kernel, lds);
-        if (le != hipSuccess) return le;
-        hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, initial, l.P[0], l.P[1], l.flag, posterior_out,
-                           loglik_out, background, plan, B, T, S);
+    hipLaunchKernelGGL(fb::fb_initial_counts_kernel, dim3((S + 255) / 256), dim3(256), 0, st, item_weights, loglik_out,
+                       posterior_out, initial_counts_out, B, T, S);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    const fblc::CountsPlan &c = l.counts;
+    e = by_value<32, 24, 16, 8, 4>(c.dq, [&](auto dq) {
+        auto *kernel = &fblc::fb_log_counts_kernel<decltype(dq)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(c.jblocks * c.chunks * c.shares)),
+                           dim3(fblc::kThreads), 0, st, batch_frames, item_weights, loglik_out, transition, l.LAop, l.Wop,
+                           l.partial, c, l.reach_left, l.W, l.S4, T, S);
         return hipGetLastError();
     });
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fblc::fb_log_counts_finalize_kernel, dim3((unsigned)(((size_t)l.W * S + 255) / 256)), dim3(256), 0, st,
+                       l.partial, l.flag, band_counts_out, initial_counts_out, c.shares, l.reach_left, l.W, S);
+    return (int)hipGetLastError();
 }
 
 // ---- expected counts on a wide band (counts_wide_band.hpp) ----

@@ -130,6 +130,9 @@ _run_band_counts = _band_runner('torbi_hip_forward_backward_counts_band',
 _wide_counts_covered = _lib.covers('torbi_hip_forward_backward_counts_wide_band_covers')
 _run_wide_band_counts = _band_runner('torbi_hip_forward_backward_counts_wide_band',
                                      'torbi_hip_forward_backward_counts_wide_band_workspace_size', counts=True)
+_log_counts_covered = _lib.covers('torbi_hip_forward_backward_counts_log_band_covers')
+_run_log_band_counts = _band_runner('torbi_hip_forward_backward_counts_log_band',
+                                    'torbi_hip_forward_backward_counts_log_band_workspace_size', counts=True)
 
 
 def _banded_operands(what, dense, covers, shape, own, observation, batch_frames, reach_left, reach_right, background,
@@ -234,22 +237,34 @@ def forward_backward_log_banded(observation: torch.Tensor, batch_frames: Optiona
 
 
 ARITHMETICS = ('scaled', 'log')
-_LOG_ONLY = "state_posteriors(arithmetic='log'): the log arithmetic has a band route only"
 _LOG_HOST = 'gpu=None computes any matrix in float64 on the CPU'
 
 
-def _log_band_run(route, trans, original, B, T, S, index):
-    """(the route, (reach_left, reach_right, background)) for `arithmetic='log'`, which declares one band route, for any band
-    it covers -- an opt-in for correctness, so no table of measured classes: 'auto' and 'band' take it, and 'dense' or a
-    matrix with no covered band raises: a GPU request never silently changes arithmetic."""
+def check_arithmetic(arithmetic: str) -> str:
+    """`arithmetic=` of `state_posteriors`, `expected_counts` and `log_likelihood`, checked before anything runs."""
+    if arithmetic not in ARITHMETICS:
+        raise RuntimeError(f"arithmetic must be 'scaled' or 'log'; got {arithmetic!r}")
+    return arithmetic
+
+
+def _log_route_run(only, who, route, trans, original, B, T, S, index):
+    """(the route, (reach_left, reach_right, background)) for `arithmetic='log'` of the feature `who`, which declares the one
+    band route `only`, for any band it covers -- an opt-in for correctness, so no table of measured classes: 'auto' and
+    'band' take it, and 'dense' or a matrix with no covered band raises: a GPU request never silently changes arithmetic."""
+    log_only = f"{who}(arithmetic='log'): the log arithmetic has a band route only"
     if route == 'dense':
-        raise RuntimeError(f"{_LOG_ONLY}, and route='dense' asks for the dense one ({_LOG_HOST})")
-    only = band_route.BandRoute(_log_covered, 'torbi_hip_forward_backward_log_band_covers', _run_log_band, None,
-                                band_route.any_width)
+        raise RuntimeError(f"{log_only}, and route='dense' asks for the dense one ({_LOG_HOST})")
     band, why = band_route.plan(trans, original, only.covers, only.entry, dict(batch=B, frames=T, states=S), index)
     if band is None:
-        raise RuntimeError(f'{_LOG_ONLY}: {why} ({_LOG_HOST})')
+        raise RuntimeError(f'{log_only}: {why} ({_LOG_HOST})')
     return only, band
+
+
+def _log_band_run(route, trans, original, B, T, S, index):
+    """`_log_route_run` for the posteriors."""
+    only = band_route.BandRoute(_log_covered, 'torbi_hip_forward_backward_log_band_covers', _run_log_band, None,
+                                band_route.any_width)
+    return _log_route_run(only, 'state_posteriors', route, trans, original, B, T, S, index)
 
 
 # Where 'auto' takes a band that only the wide route covers: the classes of (batch, band width as a share of the row) that
@@ -323,8 +338,7 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
         a NaN or +inf has NaN for both.
     """
     band_route.check_route(route)
-    if arithmetic not in ARITHMETICS:
-        raise RuntimeError(f"arithmetic must be 'scaled' or 'log'; got {arithmetic!r}")
+    check_arithmetic(arithmetic)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     log_band = arithmetic == 'log' and gpu is not None and transition is not None and B > 0
     if log_band and route == 'dense':

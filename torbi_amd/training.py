@@ -13,7 +13,12 @@ csrc/counts_band.hpp behind torbi_hip_forward_backward_counts_band, which gather
 the one launch of `forward_backward_banded`, and for a band beyond its reach (up to 512 entries) csrc/counts_wide_band.hpp
 behind torbi_hip_forward_backward_counts_wide_band, a banded rank-K update on the matrix pipe fed by the one launch of
 `forward_backward_wide_banded`; `gpu=None` and CPU tensors run the same scaled recurrence in float64 with torch CPU ops.
-POSTERIOR.md ("Expected counts", "Band counts", "Wide band counts") has the contract, the kernels and the numbers.
+Where the scaled float32 rows lose states (left-to-right matrices, data that does not yet match the model) `arithmetic='log'`
+takes csrc/counts_log_band.hpp behind torbi_hip_forward_backward_counts_log_band: the launch of
+`forward_backward_log_banded` also stores its rows as base-2 logs, and one kernel sums xi with one exponential per band
+entry and row, the whole exponent kept together.
+POSTERIOR.md ("Expected counts", "Band counts", "Wide band counts", "Log-space band counts") has the contract, the kernels
+and the numbers.
 """
 import math
 from typing import Optional, Tuple
@@ -21,8 +26,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib, band_route, inputs, posterior
-from .posterior import (_banded_operands, _counts_covered, _host, _operands, _run, _run_band_counts, _run_wide_band_counts,
-                        _shapes, _wide_counts_covered)
+from .posterior import (_banded_operands, _counts_covered, _host, _log_counts_covered, _operands, _run, _run_band_counts,
+                        _run_log_band_counts, _run_wide_band_counts, _shapes, _wide_counts_covered)
 
 ROUTES = band_route.ROUTES
 
@@ -125,6 +130,39 @@ def forward_backward_counts_wide_banded(observation: torch.Tensor, batch_frames:
     return _run_wide_band_counts(obs, frames, transition, initial, left, right, background, workspace, item_weights)
 
 
+def expected_counts_log_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_backward_counts_log_banded` needs for a (B, T, S) problem with this band: what
+    `forward_backward_log_banded` needs, two regions of B x T x (S up to 4) float32, one of B x T float32 and the partial
+    planes of the K shares, S x W float32 each."""
+    return int(_lib.load().torbi_hip_forward_backward_counts_log_band_workspace_size(B, T, S, int(reach_left),
+                                                                                     int(reach_right)))
+
+
+def forward_backward_counts_log_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor],
+                                       transition: torch.Tensor, initial: torch.Tensor, reach_left: int, reach_right: int,
+                                       background: float = -math.inf, item_weights: Optional[torch.Tensor] = None,
+                                       workspace: Optional[torch.Tensor] = None):
+    """`forward_backward_counts_banded` computed on logarithms, for a band of up to 512 entries (POSTERIOR.md, "Log-space
+    band counts"): exact where the scaled routes lose states.  The launch of `forward_backward_log_banded` also stores
+    la_t and the backward row as base-2 logs, and one kernel sums xi_t(j, i) = 2^(A[j, i] log2 e + la_{t-1}[i] + w_t[j]) over
+    the band, one exponential per band entry and row.
+
+    Arguments, promise, outputs, the skipping rule and the in-band-only rule for a finite background are
+    `forward_backward_counts_banded`'s; posterior and log_likelihood are bit for bit those of `forward_backward_log_banded`.
+    `workspace`: optional uint8 device tensor of >= `expected_counts_log_banded_workspace_bytes(B, T, S, reach_left,
+    reach_right)` bytes.  The operand rows take twice the bytes of the posterior: a caller short of memory splits the batch
+    and adds the counts, which are additive over items.
+
+    Raises where the route does not cover the call (torbi_hip_forward_backward_counts_log_band_covers: what
+    `forward_backward_log_banded` covers).
+    """
+    shape = _shapes('forward_backward_counts_log_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = _banded_operands(
+        'forward_backward_counts_log_banded', 'expected_counts with gpu=None', _log_counts_covered, shape, (), observation,
+        batch_frames, reach_left, reach_right, background, item_weights)
+    return _run_log_band_counts(obs, frames, transition, initial, left, right, background, workspace, item_weights)
+
+
 def band_counts_to_dense(band_counts: torch.Tensor, reach_left: int, reach_right: int) -> torch.Tensor:
     """The (S, S) matrix [next, prev] of the (W, S) `band_counts` of `forward_backward_counts_banded`: dense[j, j - reach_left
     + k] = band_counts[k, j], zeros outside the band.  On the tensor's device."""
@@ -178,6 +216,28 @@ def _counts_band(trans, original, B, T, S, index, route):
     return None if taken is None else taken[1][:2]
 
 
+def _log_counts_band(who, trans, original, B, T, S, index, route):
+    """(reach_left, reach_right) of the band `arithmetic='log'` sends the counts of the device matrix `trans` to -- the one
+    declared route, `posterior._log_route_run`'s plan: 'dense' or a matrix that is not -inf outside a covered band raises."""
+    only = band_route.BandRoute(_minus_inf_outside(_log_counts_covered),
+                                'torbi_hip_forward_backward_counts_log_band_covers (-inf outside the band)',
+                                _run_log_band_counts, None, band_route.any_width)
+    return posterior._log_route_run(only, who, route, trans, original, B, T, S, index)[1][:2]
+
+
+def _log_asked(who, arithmetic, route, transition, on_device):
+    """Whether the call runs the log-space band counts: `arithmetic='log'` on a device; what it cannot serve raises before
+    anything runs."""
+    if posterior.check_arithmetic(arithmetic) != 'log' or not on_device:
+        return False
+    if route == 'dense':
+        _log_counts_band(who, None, None, 0, 0, 0, 0, route)                        # (raises)
+    if transition is None:
+        raise RuntimeError(f"{who}(arithmetic='log'): the log arithmetic has a band route only, and a uniform transition "
+                           f'matrix has no band ({posterior._LOG_HOST})')
+    return True
+
+
 def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: int = 0,
                  log_probs: bool = False) -> str:
     """The route `expected_counts(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a
@@ -197,7 +257,7 @@ def counts_route(transition: Optional[torch.Tensor], batch: int, frames: int, st
 
 def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
                     transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None,
-                    log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto'
+                    log_probs: bool = False, gpu: Optional[int] = None, route: str = 'auto', arithmetic: str = 'scaled'
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Expected transition and initial-state counts (the E-step of Baum-Welch) and log P(observations) of every item.
 
@@ -213,6 +273,11 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
         either way, exactly zero outside the band; the roundings differ.  Ignored by `gpu=None`.  'auto' and 'band' look at
         the matrix (`viterbi.band_over`: one small kernel and a host synchronisation the first time a tensor version is
         seen, for a dense matrix too when S % 4 == 0 and 64 <= S <= 3072); 'dense' does not.
+    arithmetic: as `state_posteriors`.  'scaled' (the default): the float32 scaled recurrence of every route above.  'log':
+        the log-space band counts (`forward_backward_counts_log_banded`), exact where the filtered distribution spans more
+        than float32's range: 'auto' and 'band' take it for any matrix that is -inf outside a band it covers;
+        `route='dense'`, `transition=None` or a matrix with no such band raises (`gpu=None` computes any matrix in
+        float64).  Ignored by `gpu=None`.
 
     Returns:
         (transition_counts (S, S) [next, prev], initial_counts (S,), log_likelihood (B,)), float32 on the compute device.
@@ -220,6 +285,7 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
         its sum.
     """
     band_route.check_route(route)
+    log_band = _log_asked('expected_counts', arithmetic, route, transition, gpu is not None)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
@@ -231,6 +297,10 @@ def expected_counts(observation: torch.Tensor, batch_frames: Optional[torch.Tens
     if gpu is None:
         _, L, X, I = _host_counts(obs, frames, transition.to(torch.float32), initial.to(torch.float32), None)
         return X.to(torch.float32), I.to(torch.float32), L.to(torch.float32)
+    if log_band and B > 0:
+        band = _log_counts_band('expected_counts', transition, transition, B, T, S, device.index or 0, route)
+        _, L, Xb, I = _run_log_band_counts(obs, frames, transition, initial, *band, -math.inf)
+        return band_counts_to_dense(Xb, band[0], band[1]), I, L
     if original is None:
         if route == 'band':
             raise RuntimeError("route='band': a uniform transition matrix has no band")
@@ -252,24 +322,29 @@ def _host_counts(obs, frames, transition, initial, weights, counts=True):
 
 class _LogLikelihood(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, observation, batch_frames, transition, initial, route):
+    def forward(ctx, observation, batch_frames, transition, initial, route, log_band):
         B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
         ctx.dtypes = (observation.dtype, transition.dtype, initial.dtype)
         ctx.devices = (observation.device, transition.device, initial.device)
         ctx.band = None
+        ctx.log_band = log_band and B > 0
         if observation.is_cuda:
             device = observation.device
             frames = inputs.frames(batch_frames, B, T, device)
             obs = observation.detach().to(dtype=torch.float32).contiguous()
             trans = inputs.plain_matrix(transition.detach().to(device))
             init = initial.detach().to(device=device, dtype=torch.float32).contiguous()
-            ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
-            if ctx.band is not None:
-                # (the posteriors of the route whose counts the backward takes: the two declarations split alike)
-                forward = band_route.taking(posterior._band_routes(), S, *ctx.band)
-                gamma, L = forward.run(obs, frames, trans, init, *ctx.band, -math.inf)
+            if ctx.log_band:
+                ctx.band = _log_counts_band('log_likelihood', trans, transition, B, T, S, device.index or 0, route)
+                gamma, L = posterior._run_log_band(obs, frames, trans, init, *ctx.band, -math.inf)
             else:
-                gamma, L = _run(obs, frames, trans, None, init)
+                ctx.band = _counts_band(trans, transition, B, T, S, device.index or 0, route)
+                if ctx.band is not None:
+                    # (the posteriors of the route whose counts the backward takes: the two declarations split alike)
+                    forward = band_route.taking(posterior._band_routes(), S, *ctx.band)
+                    gamma, L = forward.run(obs, frames, trans, init, *ctx.band, -math.inf)
+                else:
+                    gamma, L = _run(obs, frames, trans, None, init)
             ctx.save_for_backward(obs, frames, trans, init, gamma, L)
             return L
         frames = inputs.frames(batch_frames, B, T, torch.device('cpu'))
@@ -282,7 +357,7 @@ class _LogLikelihood(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
         obs, frames, trans, init, gamma, L = ctx.saved_tensors
-        need_o, _, need_t, need_i, _ = ctx.needs_input_grad
+        need_o, _, need_t, need_i, _, _ = ctx.needs_input_grad
         g = grad.to(device=gamma.device, dtype=gamma.dtype)
         d_obs = d_trans = d_init = None
         if need_o:
@@ -291,8 +366,9 @@ class _LogLikelihood(torch.autograd.Function):
             if need_t:
                 if ctx.band is not None:
                     left, right = ctx.band
-                    backward = band_route.taking(_counts_routes(), trans.shape[0], left, right)
-                    _, _, Xb, I = backward.run(obs, frames, trans, init, left, right, -math.inf, item_weights=g.contiguous())
+                    run = (_run_log_band_counts if ctx.log_band else
+                           band_route.taking(_counts_routes(), trans.shape[0], left, right).run)
+                    _, _, Xb, I = run(obs, frames, trans, init, left, right, -math.inf, item_weights=g.contiguous())
                     X = band_counts_to_dense(Xb, left, right)
                 elif obs.is_cuda:
                     _, _, X, I = _run(obs, frames, trans, None, init, counts=True, item_weights=g.contiguous())
@@ -311,11 +387,11 @@ class _LogLikelihood(torch.autograd.Function):
             d_init = None if not need_i else I
         dtypes, devices = ctx.dtypes, ctx.devices
         cast = lambda v, k: None if v is None else v.to(device=devices[k], dtype=dtypes[k])
-        return cast(d_obs, 0), None, cast(d_trans, 1), cast(d_init, 2), None
+        return cast(d_obs, 0), None, cast(d_trans, 1), cast(d_init, 2), None, None
 
 
 def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
-                   initial: torch.Tensor, route: str = 'auto') -> torch.Tensor:
+                   initial: torch.Tensor, route: str = 'auto', arithmetic: str = 'scaled') -> torch.Tensor:
     """log P(observations) of every item, differentiable in observation, transition and initial (log inputs, the operator
     level, like `forward_backward`).
 
@@ -332,10 +408,15 @@ def log_likelihood(observation: torch.Tensor, batch_frames: Optional[torch.Tenso
     version, so once per step of a training loop that updates the matrix); `route='dense'` keeps the forward free of
     host synchronisation.
 
+    arithmetic: as `expected_counts` -- 'log' makes the forward one `forward_backward_log_banded` call and the backward one
+    `forward_backward_counts_log_banded` call for any device matrix that is -inf outside a band they cover, and raises for
+    `route='dense'` or a matrix with no such band.  Ignored by CPU tensors.
+
     Returns:
         (B,) log-likelihoods
     """
     if transition is None or initial is None:
         raise RuntimeError('log_likelihood needs a transition matrix and an initial distribution')
     band_route.check_route(route)
-    return _LogLikelihood.apply(observation, batch_frames, transition, initial, route)
+    log_band = _log_asked('log_likelihood', arithmetic, route, transition, observation.is_cuda)
+    return _LogLikelihood.apply(observation, batch_frames, transition, initial, route, log_band)

@@ -1174,6 +1174,39 @@ int torbi_hip_path_entropy_wide_band(const float *observation, const int32_t *ba
                                      float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
                                      int S, int device, void *stream);
 
+/*
+ * Log-space band route of path entropy (added within ABI 17; torbi_amd/entropy.py forward_entropy_log_banded, ENTROPY.md
+ * "Log-space band route"): torbi_hip_path_entropy_band's outputs, promise and non-finite rules, computed on logarithms for a
+ * matrix that is -inf outside a band of up to 512 entries (csrc/path_entropy_log_band.hpp).  The forward rows are
+ * torbi_hip_forward_backward_log_band's, operation for operation -- loglik_out equals that entry's bit for bit -- and the
+ * conditional entropies ride beside the band's log-sum-exp as a third running value:
+ *     h_0 = 0,   h_t[j] = sum_{i in band(j)} q_i (h_{t-1}[i] - log q_i),   q_i = softmax_i (A[j][i] + la_{t-1}[i])
+ *     prefix_t = log Z_t + (sum_j exp(la_t[j]) (h_t[j] - la_t[j])) / Z_t,   Z_t = sum_j exp(la_t[j])
+ * exact where the filtered distribution spans more than float32's range and the scaled routes lose states.  -q log q is not
+ * linear in the matrix, so there is no constant outside the band but a zero probability.  An item's bits do not depend on how
+ * many items share its workgroup, nor on the batch.
+ *
+ * torbi_hip_path_entropy_log_band_covers reads no device and answers 1 where `background` is -inf and
+ * torbi_hip_forward_backward_log_band_covers answers 1 (1 <= S <= 4096, reach_left + reach_right + 1 <= 512 with the reaches
+ * clamped to S - 1, B >= 1, T >= 1 within that entry's limits), and one item's rows and triples fit the LDS of a compute unit;
+ * else 0.  _tile: the items per workgroup a call of B items takes on `device` (1 or 2; 0 for arguments out of range).  The
+ * environment variable TORBI_HIP_LOG_BAND_ITEMS (1 or 2 here, where the tile fits the LDS) overrides that choice for a call;
+ * results do not depend on it (tools/path_entropy_log_band_probe.py times every tile).
+ * workspace: device scratch (no initialisation, no alignment) of torbi_hip_path_entropy_log_band_workspace_size bytes: the
+ * forward pack [256-state blocks][dquads][4 KiB], one scalar per item and frame (the prefix where prefix_out is null) and the
+ * promise flag.  It holds no (B, T, S) region.  The size query answers 256 for dimensions below 1, a negative reach or
+ * S > 4096.
+ * Three launches whatever T, no allocation and no host synchronisation: a call can be captured into a graph.  Errors as
+ * torbi_hip_path_entropy_band, in its order and all before a device is touched.  B == 0 launches nothing and returns 0.
+ */
+int torbi_hip_path_entropy_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_path_entropy_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right);
+int torbi_hip_path_entropy_log_band_tile(int B, int S, int reach_left, int reach_right, int device);
+int torbi_hip_path_entropy_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                    const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                    float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                                    int S, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -490,6 +490,11 @@ class _Staging:
             done.record(self.prep)
             torch.cuda.current_stream(self.device).wait_event(done)
             self.pool.give(slab, done)
+            # The lengths were allocated on the copy stream and are read by the decode on the preparation stream; no
+            # pipeline holds them here, and once the caller lets go of the batch the allocator would hand the block to the
+            # next upload's lengths -- written on the copy stream, which waits for nothing -- while the decode still reads
+            # it.  (A few bytes: deferring this free costs nothing; the slab is held by the pool above.)
+            staged.torbi_lengths.record_stream(self.prep)
         return indices
 
 

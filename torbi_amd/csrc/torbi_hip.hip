@@ -62,6 +62,7 @@
 #include "path_entropy.hpp"
 #include "path_entropy_band.hpp"
 #include "path_entropy_wide_band.hpp"
+#include "path_entropy_log_band.hpp"
 
 namespace {
 
@@ -3951,6 +3952,65 @@ int torbi_hip_path_entropy_wide_band(const float *observation, const int32_t *ba
         if (granted != hipSuccess) return granted;
         hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(pew::kThreads), lds, st, observation, batch_frames, initial, l.Pf,
                            l.Pg, l.m, l.c, l.flag, prefix, entropy_out, loglik_out, ebg, gbg, plan, B, T, S);
+        return hipGetLastError();
+    });
+    return (int)e;
+}
+
+// ---- path entropy in log space on a band (path_entropy_log_band.hpp) ----
+
+// Items per workgroup of pe_log_band_kernel<G>: fb_log_band_tile's rule with this kernel's rows and triples.
+static int pe_log_band_tile(int B, const fbw::Plan &plan, int cus) {
+    return items_per_workgroup(pel::kMaxGroup, B, 1, cus, [&](int G) { return pel::lds_bytes(G, plan) <= (size_t)pel::kMaxLdsBytes; });
+}
+
+int torbi_hip_path_entropy_log_band_covers(int B, int T, int S, int reach_left, int reach_right, float background, int device) {
+    // (-q log q is not linear in the matrix: no constant outside the band but a zero probability)
+    if (background != -INFINITY) return 0;
+    if (!torbi_hip_forward_backward_log_band_covers(B, T, S, reach_left, reach_right, background, device)) return 0;
+    return pel::lds_bytes(1, fbw::plan_of(S, reach_left, reach_right)) <= (size_t)pel::kMaxLdsBytes ? 1 : 0;
+}
+
+size_t torbi_hip_path_entropy_log_band_workspace_size(int B, int T, int S, int reach_left, int reach_right) {
+    if (B < 1 || T < 1 || S < 1 || S > pel::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return pel::layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_path_entropy_log_band_tile(int B, int S, int reach_left, int reach_right, int device) {
+    if (B < 1 || S < 1 || S > pel::kMaxStates || reach_left < 0 || reach_right < 0) return 0;
+    return pe_log_band_tile(B, fbw::plan_of(S, reach_left, reach_right), cu_count(device));
+}
+
+int torbi_hip_path_entropy_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                                    const float *initial, int reach_left, int reach_right, float background, float *entropy_out,
+                                    float *prefix_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                                    int S, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && entropy_out && loglik_out && workspace,
+        torbi_hip_path_entropy_log_band_covers(B, T, S, reach_left, reach_right, background, device),
+        torbi_hip_path_entropy_log_band_workspace_size(B, T, S, reach_left, reach_right), workspace_bytes);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const pel::Layout l = pel::layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    hipError_t e;
+    if ((e = pel::pack_and_verify(transition, l, S, st)) != hipSuccess) return (int)e;
+    int G = pe_log_band_tile(B, l, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_LOG_BAND_ITEMS")) {       // (include/torbi_hip.h: the probe's timings per G)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2) && pel::lds_bytes(g, l) <= (size_t)pel::kMaxLdsBytes) G = g;
+    }
+    const size_t lds = pel::lds_bytes(G, l);
+    float *const prefix = prefix_out ? prefix_out : l.prefix;
+    const fbw::Plan &plan = l;
+    e = by_value<2, 1>(G, [&](auto g) {
+        auto *kernel = &pel::pe_log_band_kernel<decltype(g)::value>;
+        const hipError_t granted = ensure_dynamic_lds(kernel, lds);
+        if (granted != hipSuccess) return granted;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(pel::kThreads), lds, st, observation, batch_frames, initial, l.Pf,
+                           l.flag, prefix, entropy_out, loglik_out, plan, B, T, S);
         return hipGetLastError();
     });
     return (int)e;

@@ -24,7 +24,9 @@ The HIP route is csrc/path_entropy.hpp behind torbi_hip_path_entropy / _uniform 
 holds one value outside a band, csrc/path_entropy_band.hpp behind torbi_hip_path_entropy_band (`forward_entropy_banded`, up
 to 64 in-band entries) and csrc/path_entropy_wide_band.hpp behind torbi_hip_path_entropy_wide_band
 (`forward_entropy_wide_banded`, up to 512) run the same recursion at the cost of the band, within the same bound;
-`path_entropy(route=)` chooses among them.  `gpu=None` and host tensors
+`path_entropy(route=)` chooses among them.  Where the scaled float32 rows lose states, csrc/path_entropy_log_band.hpp behind
+torbi_hip_path_entropy_log_band (`forward_entropy_log_banded`, `path_entropy(arithmetic='log')`) runs the recursion on
+logarithms for a matrix that is -inf outside a band of up to 512 entries.  `gpu=None` and host tensors
 run the recursion in float64 with torch CPU ops.  ENTROPY.md has the contract, the kernels and the numbers.
 
 This module is published as the submodule `torbi_amd.entropy`, like `margins` and `paths`; its functions are not in
@@ -41,7 +43,7 @@ from . import _lib, band_route, inputs, posterior
 
 __all__ = ['path_entropy', 'forward_entropy', 'path_entropy_workspace_bytes', 'forward_entropy_banded',
            'path_entropy_banded_workspace_bytes', 'forward_entropy_wide_banded', 'path_entropy_wide_banded_workspace_bytes',
-           'path_entropy_route']
+           'forward_entropy_log_banded', 'path_entropy_log_banded_workspace_bytes', 'path_entropy_route']
 
 
 def path_entropy_workspace_bytes(B: int, T: int, S: int, uniform: bool = False) -> int:
@@ -113,6 +115,8 @@ _covered = _lib.covers('torbi_hip_path_entropy_band_covers')
 _run_band = _band_runner('torbi_hip_path_entropy_band')
 _wide_covered = _lib.covers('torbi_hip_path_entropy_wide_band_covers')
 _run_wide_band = _band_runner('torbi_hip_path_entropy_wide_band')
+_log_covered = _lib.covers('torbi_hip_path_entropy_log_band_covers')
+_run_log_band = _band_runner('torbi_hip_path_entropy_log_band')
 
 
 def forward_entropy_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -175,6 +179,41 @@ def forward_entropy_wide_banded(observation: torch.Tensor, batch_frames: Optiona
     return _run_wide_band(obs, frames, transition, initial, left, right, background, workspace, prefix)
 
 
+def path_entropy_log_banded_workspace_bytes(B: int, T: int, S: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_entropy_log_banded` needs: the forward pack of the band, one scalar per item and
+    frame and the promise flag.  No (B, T, S) region."""
+    return int(_lib.load().torbi_hip_path_entropy_log_band_workspace_size(B, T, S, int(reach_left), int(reach_right)))
+
+
+def forward_entropy_log_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                               initial: torch.Tensor, reach_left: int, reach_right: int, background: float = -math.inf,
+                               workspace: Optional[torch.Tensor] = None, prefix: bool = False) -> Tuple[torch.Tensor, ...]:
+    """`forward_entropy_banded` computed on logarithms, for a matrix that is -inf outside a band of up to 512 entries
+    (ENTROPY.md, "Log-space band route"): exact where the filtered distribution spans more than float32's range and the
+    scaled routes lose states and their share of the entropy (mismatched data, left-to-right and permutation matrices), at
+    W exponentials per state and frame.
+
+    The recursion is the module's with the constant of each row cancelled: with la_t the filtered row in logs up to a
+    constant and q_i = softmax_i(A[j, i] + la_{t-1}[i]) over the band of j,
+
+        h_t[j] = sum_i q_i (h_{t-1}[i] - log q_i)        prefix_t = log Z_t + (sum_j exp(la_t[j]) (h_t[j] - la_t[j])) / Z_t
+
+    Arguments, promise, outputs and non-finite rules are `forward_entropy_banded`'s; the forward rows are
+    `forward_backward_log_banded`'s, so the log-likelihood equals that call's bit for bit.  `workspace`: optional uint8 device
+    tensor of >= `path_entropy_log_banded_workspace_bytes(B, T, S, reach_left, reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_path_entropy_log_band_covers: up to 4096 states,
+    reach_left + reach_right + 1 <= 512 after clamping to S - 1, and `background` -inf: the term -q log q is not linear in
+    the matrix, so a constant outside the band has no cheap form; `path_entropy` with gpu=None computes any matrix in
+    float64 on the CPU).
+    """
+    shape = posterior._shapes('forward_entropy_log_banded', observation, batch_frames, transition, initial)
+    obs, frames, left, right, background = posterior._banded_operands(
+        'forward_entropy_log_banded', 'path_entropy with gpu=None', _log_covered, shape, (), observation, batch_frames,
+        reach_left, reach_right, background)
+    return _run_log_band(obs, frames, transition, initial, left, right, background, workspace, prefix)
+
+
 # Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row) that
 # tools/path_entropy_probe.py measured faster than the dense call on the same inputs by more than the dense call's own
 # spread (ENTROPY.md, "Band route", timing).  Each entry: (smallest batch, largest batch, diagonals of 1440 states).
@@ -211,6 +250,13 @@ def _band(route, trans, original, B, T, S, index):
                             "path_entropy(route='band')")
 
 
+def _log_band(route, trans, original, B, T, S, index):
+    """`posterior._log_route_run` for the path entropy: the one declared route of `arithmetic='log'`."""
+    only = band_route.BandRoute(_log_covered, 'torbi_hip_path_entropy_log_band_covers', _run_log_band, None,
+                                band_route.any_width)
+    return posterior._log_route_run(only, 'path_entropy', route, trans, original, B, T, S, index)
+
+
 def path_entropy_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, gpu: Optional[int] = 0,
                        log_probs: bool = False) -> str:
     """The route `path_entropy(..., transition=transition, log_probs=log_probs, gpu=gpu, route='auto')` takes for a (batch,
@@ -232,7 +278,8 @@ def path_entropy_route(transition: Optional[torch.Tensor], batch: int, frames: i
 
 def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor] = None,
                  transition: Optional[torch.Tensor] = None, initial: Optional[torch.Tensor] = None, log_probs: bool = False,
-                 gpu: Optional[int] = 0, prefix: bool = False, route: str = 'dense') -> Tuple[torch.Tensor, ...]:
+                 gpu: Optional[int] = 0, prefix: bool = False, route: str = 'dense', arithmetic: str = 'scaled'
+                 ) -> Tuple[torch.Tensor, ...]:
     """The entropy of the posterior over whole state paths of every item, and log P(observations) of every item.
 
     Arguments mean what they mean to `from_probabilities`, defaults included (uniform initial log(1/S + tiny), uniform
@@ -251,6 +298,16 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
         found, the call is covered and its class of batch and band width was measured faster than the dense route
         (`path_entropy_route` answers which), else the dense one.  Ignored by `transition=None` except that 'band' raises
         there; `gpu=None` is the host route and refuses 'band'.
+    arithmetic: 'scaled' (the default): the float32 scaled recursion of every route above.  'log': the log-space band
+        route (`forward_entropy_log_banded`), exact where the filtered distribution spans more than float32's range --
+        mismatched data, left-to-right matrices -- and slower.  It has a band route only, and `route` defaults to 'dense',
+        so ask for both:
+
+            H, L = path_entropy(observation, transition=transition, gpu=0, route='band', arithmetic='log')
+
+        'auto' and 'band' take it for any matrix that is -inf outside a band it covers; `route='dense'`, `transition=None`,
+        a finite value outside the band or a matrix with no covered band raises (`gpu=None` computes any matrix in
+        float64).  Ignored by `gpu=None`.
 
     Returns:
         (entropy (batch,) float32, log_likelihood (batch,) float32) on the compute device, and with `prefix` also
@@ -259,7 +316,14 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
         a NaN or +inf has NaN for both.
     """
     band_route.check_route(route)
+    posterior.check_arithmetic(arithmetic)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    log_band = arithmetic == 'log' and gpu is not None and B > 0
+    if log_band and route == 'dense':
+        _log_band(route, None, None, B, T, S, 0)                                    # (raises before anything runs)
+    if log_band and transition is None:
+        raise RuntimeError("path_entropy(arithmetic='log'): the log arithmetic has a band route only, and a uniform "
+                           f'transition matrix has no band ({posterior._LOG_HOST})')
     if route == 'band' and gpu is None:
         raise RuntimeError("path_entropy(route='band') needs a HIP device: gpu=None is the host route")
     if route == 'band' and transition is None:
@@ -271,7 +335,7 @@ def path_entropy(observation: torch.Tensor, batch_frames: Optional[torch.Tensor]
     band = None
     if gpu is not None and uniform is None and route != 'dense':
         # (before the observation is prepared: a matrix without a band raises before anything runs)
-        band = _band(route, transition, transition, B, T, S, device.index or 0)
+        band = (_log_band if log_band else _band)(route, transition, transition, B, T, S, device.index or 0)
     obs = inputs.observation(observation, log_probs, device)
     if gpu is None:
         H, L, rows = _host(obs, frames, transition, uniform, initial)

@@ -970,6 +970,35 @@ int torbi_hip_sample_wide_band(const float *observation, const int32_t *batch_fr
                                int S, int N, int device, void *stream);
 
 /*
+ * Log-space band route of posterior path sampling (added within ABI 17; torbi_amd/sampling.py forward_sample_log_banded,
+ * SAMPLING.md "Log-space band route"): torbi_hip_sample_wide_band's arguments, outputs, promise, non-finite rules, error
+ * codes and order of the checks, computed on logarithms for a matrix that is -inf outside a band of up to 512 entries
+ * (csrc/sample_log_band.hpp).  The filter is the forward half of torbi_hip_forward_backward_log_band, operation for
+ * operation: loglik_out equals that entry's bit for bit, and the rows la_t (logs, the row's maximum 0) go to the workspace.
+ * Frame F-1 draws from exp(la_{F-1}) over the whole row.  Frame t < F-1, with j = j_{t+1}, lo = max(0, j - reach_left) and
+ * hi = min(S - 1, j + reach_right), applies the draw rule to
+ *     w[i] = exp(x[i] - m),   x[i] = transition[j][i] + la_t[i],   m = max_{lo <= i <= hi} x[i]
+ * so the largest weight of a draw's own window is 1 wherever the window lies under the row's maximum: exact where the
+ * filtered distribution spans more than float32's range and the scaled routes draw from a filter that has lost states.
+ * An item whose L is not finite (a NaN or +inf read, total probability 0, a broken promise -- then every L is NaN) has -1
+ * in every column of every draw.  A draw's bits depend on its item and its own row of uniforms alone.
+ *
+ * torbi_hip_sample_log_band_covers reads no device and answers 1 where `background` is -inf,
+ * torbi_hip_forward_backward_log_band_covers answers 1 (1 <= S <= 4096, reach_left + reach_right + 1 <= 512 with the reaches
+ * clamped to S - 1) and 1 <= N <= 4096; else 0.  torbi_hip_sample_log_band_workspace_size:
+ * torbi_hip_forward_backward_log_band_workspace_size(B, T, S, reach_left, reach_right) plus the filter rows (B, T, S4) fp32,
+ * S4 = S rounded up to 4, rounded up to 256 bytes, whatever N; 256 for dimensions below 1, a negative reach or S > 4096; no
+ * initialisation and no alignment of the caller's base.  Four launches whatever T, no allocation and no host
+ * synchronisation: a call can be captured into a graph.  Errors are returned before a device is touched.
+ */
+int torbi_hip_sample_log_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device);
+size_t torbi_hip_sample_log_band_workspace_size(int B, int T, int S, int N, int reach_left, int reach_right);
+int torbi_hip_sample_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                              const float *initial, int reach_left, int reach_right, float background, const float *uniforms,
+                              int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                              int S, int N, int device, void *stream);
+
+/*
  * Max-marginals (added within ABI 17): the largest log score of any complete path of item b that is in state j at frame t,
  * on the model torbi_hip_viterbi_decode decodes (torbi_amd/margins.py, MARGINALS.md).  Inputs as there: observation
  * (B, T, S) log scores, batch_frames (B,) int32 (F: clamped to [1, T]), transition (S, S) log [next][prev], initial (S,) log.

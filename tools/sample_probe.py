@@ -16,6 +16,12 @@
       (synth.banded_transition(1440, 87.2), -inf and log(tiny) outside the band) at --batches x T x 1440 with 1 and 16 draws,
       alternated call by call in one process on the same inputs, each with a caller-owned workspace; one JSON line per case
       (SAMPLING.md, "Wide band route")
+  --log-band: instead of (a) - (d), forward_sample_log_banded against the scaled band route that takes the band
+      (forward_sample_banded on 23 diagonals, forward_sample_wide_banded on 175) and against forward_backward_log_banded, on
+      peaked rows at --batches x T x 1440 with 1 and 16 draws, -inf outside, all calls alternated in one process, each with a
+      caller-owned workspace; one JSON line per case.  Before them one line per wide-range case of
+      tests/test_sample_log_band_gpu.py: the share of -1 draws and the worst d (tests/sample_band_cases.py draw_errors) of
+      forward_sample_wide_banded and of forward_sample_log_banded (SAMPLING.md, "Log-space band route")
 Every time is the median of --repeats calls with its min and max, device synchronised around each call.
 """
 import argparse
@@ -242,11 +248,75 @@ def wide_band_main(args, dev):
             print(json.dumps(wide_band_case(B, args.T, 1440, 87.2, (1, 16), tiny, args.repeats, dev)), flush=True)
 
 
+def log_band_gap(name, dev):
+    """What the scaled wide route and the log route return on one wide-range case of the log route's tests."""
+    import sample_band_cases as sbc
+    import test_sample_log_band_gpu as cases
+    (obs, frames, A, pi, u), band, (a, E, _, F) = cases.case(name)
+    out = {'wide_range_case': name, 'shape': list(obs.shape), 'band': list(band)}
+    for label, entry in (('wide', torbi_amd.forward_sample_wide_banded), ('log', torbi_amd.forward_sample_log_banded)):
+        indices, L = (x.cpu() for x in entry(*(x.to(dev) for x in (obs, frames, A, pi, u)), *band))
+        lost = (indices < 0).any(dim=2)                                   # (B, N): a draw is -1 in every column or in none
+        worst = 0.                                                        # d of the draws that came back, item by item
+        for b in range(indices.shape[0]):
+            if bool((~lost[b]).any()):
+                worst = max(worst, sbc.draw_errors(indices[b:b + 1, ~lost[b]], u[b:b + 1, ~lost[b]], a[b:b + 1], E, F[b:b + 1],
+                                                   band, -float('inf'))[0])
+        out[label] = {'share_of_lost_draws': float(lost.double().mean()), 'worst_d_of_the_rest': worst,
+                      'finite_L': bool(torch.isfinite(L).all())}
+    return out
+
+
+def log_band_case(B, T, S, half_width, draws, repeats, dev):
+    from posterior_probe import peaked_rows
+    reach = int(np.ceil(half_width)) - 1
+    trans = torch.from_numpy(synth.banded_transition(S, half_width)).to(dev)
+    init = torch.full((S,), float(np.log(1. / S)), device=dev)
+    obs = peaked_rows(B, T, S, dev)
+    frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    narrow = 2 * reach + 1 <= 64
+    scaled, scaled_bytes = ((torbi_amd.forward_sample_banded, torbi_amd.forward_sample_banded_workspace_bytes) if narrow else
+                            (torbi_amd.forward_sample_wide_banded, torbi_amd.forward_sample_wide_banded_workspace_bytes))
+    room = lambda size, *more: torch.empty(size(B, T, S, *more, reach, reach), dtype=torch.uint8, device=dev)
+    ws, wl = room(scaled_bytes, max(draws)), room(torbi_amd.forward_sample_log_banded_workspace_bytes, max(draws))
+    wp = room(torbi_amd.forward_backward_log_banded_workspace_bytes)
+    out = {'shape': [B, T, S], 'diagonals': 2 * reach + 1, 'scaled_route': 'band' if narrow else 'wide band',
+           'workspace_bytes': {'scaled': ws.numel(), 'log': wl.numel(), 'log_posterior': wp.numel()}}
+    calls = {'log_posterior': lambda: torbi_amd.forward_backward_log_banded(obs, frames, trans, init, reach, reach, workspace=wp)}
+    us = {}
+    for n in draws:
+        us[n] = torch.rand((B, n, T), device=dev, generator=torch.Generator(device=dev).manual_seed(n))
+        calls[f'scaled_{n}'] = lambda n=n: scaled(obs, frames, trans, init, us[n], reach, reach, workspace=ws)
+        calls[f'log_{n}'] = lambda n=n: torbi_amd.forward_sample_log_banded(obs, frames, trans, init, us[n], reach, reach,
+                                                                           workspace=wl)
+    L = calls[f'log_{draws[0]}']()[1]
+    out['L_equals_log_posterior'] = bool(torch.equal(L, calls['log_posterior']()[1]))
+    out['ms'] = alternated(calls, repeats)
+    for n in draws:
+        out[f'log_over_scaled_{n}'] = out['ms'][f'log_{n}']['median'] / out['ms'][f'scaled_{n}']['median']
+        out[f'log_over_log_posterior_{n}'] = out['ms'][f'log_{n}']['median'] / out['ms']['log_posterior']['median']
+    return out
+
+
+def log_band_main(args, dev):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import test_sample_log_band_gpu as cases
+    print(json.dumps({'device': torch.cuda.get_device_name(0)}), flush=True)
+    for name in cases.WIDE_RANGE:
+        print(json.dumps(log_band_gap(name, dev)), flush=True)
+    for half_width in (12, 87.2):
+        for B in args.batches:
+            print(json.dumps(log_band_case(B, args.T, 1440, half_width, (1, 16), args.repeats, dev)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--wide-band', action='store_true',
                     help='forward_sample against forward_sample_wide_banded on the pitch matrix of 175 diagonals')
-    ap.add_argument('--batches', type=int, nargs='+', default=[1, 8, 64, 512, 4096], help='with --wide-band: the batch sizes')
+    ap.add_argument('--log-band', action='store_true',
+                    help='forward_sample_log_banded against the scaled band routes and forward_backward_log_banded')
+    ap.add_argument('--batches', type=int, nargs='+', default=None,
+                    help='the batch sizes: with --wide-band (default 1 8 64 512 4096) and --log-band (default 1 8 512 4096)')
     ap.add_argument('--band', action='store_true', help='forward_sample against forward_sample_banded on the pitch matrix')
     ap.add_argument('--trace', action='store_true', help='with --band: kernel times of one call each instead of call times')
     ap.add_argument('--repeats', type=int, default=5)
@@ -256,8 +326,12 @@ def main():
     dev = torch.device('cuda:0')
     if args.band:
         return band_main(args, dev)
+    if args.batches is None:
+        args.batches = [1, 8, 512, 4096] if args.log_band else [1, 8, 64, 512, 4096]
     if args.wide_band:
         return wide_band_main(args, dev)
+    if args.log_band:
+        return log_band_main(args, dev)
     out = {'device': torch.cuda.get_device_name(0)}
     out['a_dense_512'] = dense_case(512, args.T, 1440, (1, 16), args.repeats, dev, not args.no_torch)
     out['a_dense_1'] = dense_case(1, args.T, 1440, (1,), args.repeats, dev, not args.no_torch)

@@ -32,6 +32,7 @@ from .training import (band_counts_to_dense, counts_route, expected_counts, expe
 from .k_best import (best_paths, decode_k_best, decode_k_best_banded, decode_k_best_banded_workspace_bytes,
                      decode_k_best_workspace_bytes, k_best_route)
 from .sampling import (forward_sample, forward_sample_banded, forward_sample_banded_workspace_bytes,
+                       forward_sample_log_banded, forward_sample_log_banded_workspace_bytes,
                        forward_sample_wide_banded, forward_sample_wide_banded_workspace_bytes,
                        forward_sample_workspace_bytes, sample_paths, sample_route)
 

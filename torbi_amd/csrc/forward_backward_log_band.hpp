@@ -130,9 +130,10 @@ __global__ __launch_bounds__(64) void fb_log_verify_kernel(const float *__restri
     if (broken) *flag = 1;
 }
 
-inline hipError_t pack_and_verify(const float *A, const Layout &l, float background, int S, hipStream_t st) {
+// `passes` = 1: the forward pack alone (a forward-only caller; P[1] is not written)
+inline hipError_t pack_and_verify(const float *A, const Layout &l, float background, int S, hipStream_t st, int passes = 2) {
     const int most = l.Dq[0] > l.Dq[1] ? l.Dq[0] : l.Dq[1];
-    hipLaunchKernelGGL(fb_log_pack_kernel, dim3((unsigned)(l.blocks * most), 2), dim3(256), 0, st, A, l.P[0], l.P[1], l.flag,
+    hipLaunchKernelGGL(fb_log_pack_kernel, dim3((unsigned)(l.blocks * most), passes), dim3(256), 0, st, A, l.P[0], l.P[1], l.flag,
                        background, static_cast<const Plan &>(l), S);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -56,6 +56,7 @@
 #include "sample.hpp"
 #include "sample_band.hpp"
 #include "sample_wide_band.hpp"
+#include "sample_log_band.hpp"
 #include "max_marginals.hpp"
 #include "max_marginals_band.hpp"
 #include "path_statistics.hpp"
@@ -3384,6 +3385,62 @@ int torbi_hip_sample_wide_band(const float *observation, const int32_t *batch_fr
             auto *kernel = &fbw::sample_wide_band_backward_kernel<decltype(np)::value, decltype(vec_)::value>;
             hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, transition, l.c, batch_frames, loglik_out,
                                uniforms, indices_out, ebg, l.reach_left, l.reach_right, T, S, N);
+        });
+    });
+    return (int)hipGetLastError();
+}
+
+// ---- posterior path sampling in log space on a band (sample_log_band.hpp) ----
+
+int torbi_hip_sample_log_band_covers(int B, int T, int S, int N, int reach_left, int reach_right, float background, int device) {
+    // (the sampler weights a window by the band's own entries: no constant outside the band but a zero probability)
+    if (N < 1 || N > sample::kMaxDraws || background != -INFINITY) return 0;
+    return torbi_hip_forward_backward_log_band_covers(B, T, S, reach_left, reach_right, background, device);
+}
+
+size_t torbi_hip_sample_log_band_workspace_size(int B, int T, int S, int N, int reach_left, int reach_right) {
+    (void)N;
+    if (B < 1 || T < 1 || S < 1 || S > fbl::kMaxStates || reach_left < 0 || reach_right < 0) return 256;
+    return fbls::sample_layout(nullptr, B, T, S, reach_left, reach_right).total;
+}
+
+int torbi_hip_sample_log_band(const float *observation, const int32_t *batch_frames, const float *transition,
+                              const float *initial, int reach_left, int reach_right, float background, const float *uniforms,
+                              int32_t *indices_out, float *loglik_out, void *workspace, size_t workspace_bytes, int B, int T,
+                              int S, int N, int device, void *stream) {
+    const int rc = fb_band_args_ok(
+        B, T, S, reach_left, reach_right,
+        observation && batch_frames && transition && initial && uniforms && indices_out && loglik_out && workspace,
+        torbi_hip_sample_log_band_covers(B, T, S, N, reach_left, reach_right, background, device),
+        torbi_hip_sample_log_band_workspace_size(B, T, S, N, reach_left, reach_right), workspace_bytes,
+        N >= 1 && N <= sample::kMaxDraws, (size_t)B * N * T <= (size_t)1 << 32);
+    if (rc != TORBI_HIP_OK || B == 0) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const fbls::SampleLayout l = fbls::sample_layout(fb_base(workspace), B, T, S, reach_left, reach_right);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    hipError_t e;
+    if ((e = fbl::pack_and_verify(transition, l, background, S, st, 1)) != hipSuccess) return (int)e;
+    const int G = fb_log_band_tile(B, l, cu_count(device));              // (fb_log_band_kernel's tile: the same LDS)
+    const size_t lds = fbl::lds_bytes(G, l);
+    const fbw::Plan &plan = l;
+    e = by_value<4, 2, 1>(G, [&](auto g) {
+        auto *kernel = &fbls::fb_log_band_filter_kernel<decltype(g)::value>;
+        const hipError_t le = ensure_dynamic_lds(kernel, lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(kernel, dim3((B + G - 1) / G), dim3(fbl::kThreads), lds, st, observation, batch_frames, initial, l.P[0],
+                           l.flag, l.rows, loglik_out, plan, B, T, S);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return (int)e;
+    const dim3 grid(B, (N + sample::kWaves - 1) / sample::kWaves);
+    // (16-byte loads of a matrix row: rows of a multiple of 4 floats behind an aligned base)
+    const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(transition) & 15) == 0;
+    by_value<1, 2, 3>(fbw::sample_rounds(l), [&](auto np) {
+        by_flag(vec, [&](auto vec_) {
+            auto *kernel = &fbls::sample_log_band_backward_kernel<decltype(np)::value, decltype(vec_)::value>;
+            hipLaunchKernelGGL(kernel, grid, dim3(64 * sample::kWaves), 0, st, l.rows, transition, batch_frames, loglik_out,
+                               uniforms, indices_out, l.reach_left, l.reach_right, T, S, N);
         });
     });
     return (int)hipGetLastError();

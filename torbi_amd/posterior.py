@@ -247,11 +247,12 @@ def check_arithmetic(arithmetic: str) -> str:
     return arithmetic
 
 
-def _log_route_run(only, who, route, trans, original, B, T, S, index):
+def _log_route_run(only, who, route, trans, original, B, T, S, index, asked="arithmetic='log'"):
     """(the route, (reach_left, reach_right, background)) for `arithmetic='log'` of the feature `who`, which declares the one
     band route `only`, for any band it covers -- an opt-in for correctness, so no table of measured classes: 'auto' and
-    'band' take it, and 'dense' or a matrix with no covered band raises: a GPU request never silently changes arithmetic."""
-    log_only = f"{who}(arithmetic='log'): the log arithmetic has a band route only"
+    'band' take it, and 'dense' or a matrix with no covered band raises: a GPU request never silently changes arithmetic.
+    `asked`: how the caller spelled the request (`sample_paths` has no `arithmetic=`: its `route='log-band'`)."""
+    log_only = f'{who}({asked}): the log arithmetic has a band route only'
     if route == 'dense':
         raise RuntimeError(f"{log_only}, and route='dense' asks for the dense one ({_LOG_HOST})")
     band, why = band_route.plan(trans, original, only.covers, only.entry, dict(batch=B, frames=T, states=S), index)

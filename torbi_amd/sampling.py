@@ -13,7 +13,10 @@ The HIP route is csrc/sample.hpp behind torbi_hip_sample / _uniform (include/tor
 `forward_backward`, then one launch that draws every path, one wave per draw.  For a matrix that holds one value outside a
 band, csrc/sample_band.hpp behind torbi_hip_sample_band (`forward_sample_banded`, `sample_paths(route=)`) draws at the cost of
 the band, up to 64 in-band entries in a matrix row; csrc/sample_wide_band.hpp behind torbi_hip_sample_wide_band
-(`forward_sample_wide_banded`) takes bands of up to 512.  `gpu=None` runs the dense rule in float64 with torch CPU ops.
+(`forward_sample_wide_banded`) takes bands of up to 512.  Where the scaled float32 filter loses states (data the model does
+not yet explain under a -inf band, left-to-right matrices) csrc/sample_log_band.hpp behind torbi_hip_sample_log_band
+(`forward_sample_log_banded`, `sample_paths(route='log-band')`) filters and draws on logarithms.  `gpu=None` runs the dense
+rule in float64 with torch CPU ops.
 SAMPLING.md has the contract, the kernels and the numbers.
 """
 import functools
@@ -115,6 +118,9 @@ _covered = _lib.covers('torbi_hip_sample_band_covers')
 _run_band = _band_runner('torbi_hip_sample_band', 'torbi_hip_sample_band_workspace_bytes')
 _wide_covered = _lib.covers('torbi_hip_sample_wide_band_covers')
 _run_wide_band = _band_runner('torbi_hip_sample_wide_band', 'torbi_hip_sample_wide_band_workspace_size')
+_log_covered = _lib.covers('torbi_hip_sample_log_band_covers')
+_run_log_band = _band_runner('torbi_hip_sample_log_band', 'torbi_hip_sample_log_band_workspace_size')
+LOG_ROUTE = 'log-band'                            # `sample_paths(route=)`: not one of band_route.ROUTES, and never 'auto''s
 
 
 def forward_sample_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
@@ -180,6 +186,42 @@ def forward_sample_wide_banded(observation: torch.Tensor, batch_frames: Optional
     return _run_wide_band(obs, frames, transition, initial, uniforms, left, right, background, workspace)
 
 
+def forward_sample_log_banded_workspace_bytes(B: int, T: int, S: int, draws: int, reach_left: int, reach_right: int) -> int:
+    """Bytes of device scratch `forward_sample_log_banded` needs: the layout of `forward_backward_log_banded` for this band and
+    the filter rows (B, T, S up to 4) float32 behind it, whatever `draws`."""
+    return int(_lib.load().torbi_hip_sample_log_band_workspace_size(B, T, S, int(draws), int(reach_left), int(reach_right)))
+
+
+def forward_sample_log_banded(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                              initial: torch.Tensor, uniforms: torch.Tensor, reach_left: int, reach_right: int,
+                              background: float = -math.inf, workspace: Optional[torch.Tensor] = None
+                              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_sample_wide_banded` computed on logarithms, for a matrix that is -inf outside a band of up to 512 entries
+    (SAMPLING.md, "Log-space band route"): exact where the filtered distribution spans more than float32's range and the
+    scaled routes draw from a filter that has lost states, or return -1 where a whole window underflows.
+
+    With la_t the filtered row in logs (`forward_backward_log_banded`'s forward rows), frame F-1 draws from exp(la_{F-1}) and
+    frame t < F-1, given j = j_{t+1}, from
+
+        w[i] = exp(x[i] - max x),   x[i] = transition[j, i] + la_t[i]      over the band of j
+
+    so the largest weight of a draw's own window is 1.  Arguments, promise, the draw rule, outputs and non-finite rules are
+    `forward_sample_banded`'s; the log-likelihood is `forward_backward_log_banded`'s, bit for bit.  `workspace`: optional
+    uint8 device tensor of >= `forward_sample_log_banded_workspace_bytes(B, T, S, draws, reach_left, reach_right)` bytes.
+
+    Raises where the route does not cover the call (torbi_hip_sample_log_band_covers: up to 4096 states,
+    reach_left + reach_right + 1 <= 512 after clamping to S - 1, 1 <= draws <= 4096, and `background` -inf: a finite
+    background is the scaled band routes', and `sample_paths` with gpu=None draws from any matrix in float64 on the CPU).
+    """
+    B, T, S = shape = posterior._shapes('forward_sample_log_banded', observation, batch_frames, transition, initial)
+    own = ('draws', _check_uniforms(uniforms, B, T))
+    obs, frames, left, right, background = posterior._banded_operands(
+        'forward_sample_log_banded',
+        'forward_sample_banded and forward_sample_wide_banded take a finite background, sample_paths with gpu=None', _log_covered,
+        shape, own, observation, batch_frames, reach_left, reach_right, background)
+    return _run_log_band(obs, frames, transition, initial, uniforms, left, right, background, workspace)
+
+
 # Where 'auto' takes a covered band: the classes of (batch, band width as a share of the row, draws) that
 # tools/sample_probe.py --band measured faster than the dense call by more than the spread of the measurement (SAMPLING.md,
 # "Band route", timing).  Each entry: (smallest batch, largest batch, diagonals of 1440 states, most draws).  Measured, all on
@@ -217,6 +259,13 @@ def _band_run(route, trans, original, B, T, S, N, index):
     one."""
     return band_route.route(_band_routes(), route, trans, original, dict(batch=B, frames=T, states=S, draws=N), index,
                             "sample_paths(route='band')")
+
+
+def _log_band_run(trans, original, B, T, S, N, index):
+    """`posterior._log_route_run` for `sample_paths(route='log-band')`: the one declared log route, asked as 'band'."""
+    only = band_route.BandRoute(lambda B, T, S, *band: _log_covered(B, T, S, N, *band), 'torbi_hip_sample_log_band_covers',
+                                _run_log_band, None, band_route.any_width)
+    return posterior._log_route_run(only, 'sample_paths', 'band', trans, original, B, T, S, index, f'route={LOG_ROUTE!r}')
 
 
 def sample_route(transition: Optional[torch.Tensor], batch: int, frames: int, states: int, draws: int = 1, gpu: int = 0,
@@ -259,22 +308,28 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
         reason where the matrix has no covered band.  'auto': the band route where such a band is found, the call is covered and its
         class of batch, band width and draws was measured faster than the dense route (`sample_route` answers which), else
         the dense one.  Both routes draw exactly from the model; for given uniforms their draws differ.  Ignored by
-        `transition=None`; `gpu=None` is the float64 dense rule and refuses 'band'.
+        `transition=None`; `gpu=None` is the float64 dense rule and refuses 'band'.  'log-band': the log-space band route
+        (`forward_sample_log_banded`), exact where the filtered distribution spans more than float32's range -- data the
+        model does not yet explain under a -inf band, left-to-right matrices -- and slower; for any matrix that is -inf
+        outside a band it covers.  A finite value outside the band, a matrix with no covered band, `transition=None` and
+        `gpu=None` raise (`gpu=None` draws from any matrix in float64).  'auto' never takes it.
 
     Returns:
         (indices (batch, draws, frames) int32, log_likelihood (batch,) float32) on the compute device.  Columns
         t >= batch_frames[b] repeat the path's last state.  An item of total probability 0 has log-likelihood -inf, an item
         that reads a NaN or +inf has NaN; both have -1 in every column of every draw.
     """
-    band_route.check_route(route)
+    log_band = route == LOG_ROUTE                 # (its own value of `route`: band_route.ROUTES is what 'auto' chooses among)
+    if not log_band:
+        band_route.check_route(route)
     draws = _check_draws(draws)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
     if uniforms is not None:
         _check_uniforms(uniforms, B, T, draws)
-    if route == 'band' and gpu is None:
-        raise RuntimeError("sample_paths(route='band') needs a HIP device: gpu=None is the float64 dense rule")
-    if route == 'band' and transition is None:
-        raise RuntimeError("sample_paths(route='band'): there is no transition matrix (the uniform model draws every frame "
+    if route in ('band', LOG_ROUTE) and gpu is None:
+        raise RuntimeError(f'sample_paths(route={route!r}) needs a HIP device: gpu=None is the float64 dense rule')
+    if route in ('band', LOG_ROUTE) and transition is None:
+        raise RuntimeError(f'sample_paths(route={route!r}): there is no transition matrix (the uniform model draws every frame '
                            'independently); the band route needs a matrix that holds one value outside a band')
     device = inputs._compute_device(gpu)
     frames = inputs.frames(batch_frames, B, T, device)
@@ -282,7 +337,11 @@ def sample_paths(observation: torch.Tensor, draws: int = 1, batch_frames: Option
     band = None
     if gpu is not None and uniform is None and route != 'dense':
         # (before the observation is prepared: a matrix without a band raises before anything runs)
-        band = _band_run(route, transition, transition, B, T, S, draws, device.index or 0)
+        index = device.index or 0
+        if not log_band:
+            band = _band_run(route, transition, transition, B, T, S, draws, index)
+        elif B > 0:                                   # (an empty batch launches nothing on any route)
+            band = _log_band_run(transition, transition, B, T, S, draws, index)
     obs = inputs.observation(observation, log_probs, device)
     if uniforms is None:
         uniforms = torch.rand((B, draws, T), dtype=torch.float32, device=device, generator=generator)

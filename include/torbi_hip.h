@@ -740,6 +740,32 @@ int torbi_hip_forward_backward_log_band(const float *observation, const int32_t 
                                         int B, int T, int S, int device, void *stream);
 
 /*
+ * Dense log-space route of forward-backward (added within ABI 17; torbi_amd/posterior.py forward_backward_log, POSTERIOR.md
+ * "Dense log-space route"): torbi_hip_forward_backward_log_band's quantities, outputs and non-finite rules for ANY matrix,
+ * with the band split taken out (csrc/forward_backward_log.hpp): every product is a log-sum-exp over the whole row of the
+ * matrix, every output state under its own running maximum.  There is no promise and no flag: every float32 matrix is a
+ * valid input, -inf in it is a zero probability and makes no NaN.  An item's bits depend on S and its own data only.
+ * _covers: 1 for 1 <= S <= 4096, B >= 1 and T >= 1 within torbi_hip_forward_backward's limits; else 0.  It and
+ * _workspace_size answer without a device.  _tile: the items per tile of the step launches a call of B items takes on
+ * `device` (1, 2, 4 or 8; 0 for arguments out of range); the environment variable TORBI_HIP_LOG_DENSE_ITEMS (1, 2, 4 or 8)
+ * overrides it for a call, results do not depend on it (tools/posterior_log_dense_probe.py times every tile).
+ * workspace: torbi_hip_forward_backward_log_workspace_size(B, T, S) bytes (256 for arguments out of range), no
+ * initialisation and no alignment: with Sp = S rounded up to 64, both packs of the matrix, Sp x Sp fp32 each, the backward
+ * products y, B x Sp fp32, the backward rows r, 2 x B x Sp fp32, and the sums of the forward maxima, B fp64, every region
+ * rounded up to 256 bytes, plus 256 to align the caller's base.  It does not depend on T.
+ * One pack launch, then per frame and pass one step launch (none for a pass's first frame) and one row launch, all on
+ * `stream`; no allocation and no host synchronisation: with a caller-owned workspace a call can be captured into a graph.
+ * Errors, before anything is launched: TORBI_HIP_EINVAL for a null pointer or a call _covers answers 0 for (B = 0 is
+ * TORBI_HIP_OK and launches nothing), TORBI_HIP_EWORKSPACE for a workspace that is too small.
+ */
+int torbi_hip_forward_backward_log_covers(int B, int T, int S, int device);
+size_t torbi_hip_forward_backward_log_workspace_size(int B, int T, int S);
+int torbi_hip_forward_backward_log_tile(int B, int S, int device);
+int torbi_hip_forward_backward_log(const float *observation, const int32_t *batch_frames, const float *transition,
+                                   const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                                   size_t workspace_bytes, int B, int T, int S, int device, void *stream);
+
+/*
  * Expected counts on a band (added within ABI 17): torbi_hip_forward_backward_band on the same inputs, which writes
  * posterior_out and loglik_out bit for bit as that call does, and in addition the counts of
  * torbi_hip_forward_backward_counts inside the band, diagonal by diagonal, and the initial counts:

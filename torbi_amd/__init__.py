@@ -23,6 +23,7 @@ from .core import release_job_memory
 from .stream import StreamDecoder, stream_route
 from .stream_posterior import StreamPosteriors, stream_posterior_route
 from .posterior import (forward_backward, forward_backward_banded, forward_backward_banded_workspace_bytes,
+                        forward_backward_log, forward_backward_log_workspace_bytes,
                         forward_backward_log_banded, forward_backward_log_banded_workspace_bytes, forward_backward_wide_banded, forward_backward_wide_banded_workspace_bytes,
                         forward_backward_workspace_bytes, posterior_route, state_posteriors)
 from .training import (band_counts_to_dense, counts_route, expected_counts, expected_counts_banded_workspace_bytes,

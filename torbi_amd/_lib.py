@@ -148,6 +148,12 @@ SYMBOLS = {
     'torbi_hip_forward_backward_log_band': (_c.c_int, [
         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p,
         _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    'torbi_hip_forward_backward_log_covers': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_forward_backward_log_workspace_size': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_forward_backward_log_tile': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
+    'torbi_hip_forward_backward_log': (_c.c_int, [
+        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     'torbi_hip_forward_backward_counts_band_covers': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                                                 _c.c_float, _c.c_int]),
     'torbi_hip_forward_backward_counts_band_workspace_bytes': (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int,

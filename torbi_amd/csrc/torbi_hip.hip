@@ -46,6 +46,7 @@
 #include "forward_backward_band.hpp"
 #include "forward_backward_wide_band.hpp"
 #include "forward_backward_log_band.hpp"
+#include "forward_backward_log.hpp"
 #include "stream_posterior_band.hpp"
 #include "counts_band.hpp"
 #include "counts_wide_band.hpp"
@@ -3118,6 +3119,85 @@ int torbi_hip_forward_backward_log_band(const float *observation, const int32_t 
     if (guard.err != hipSuccess) return (int)guard.err;
     return (int)fb_log_band_passes(l, observation, batch_frames, transition, initial, background, posterior_out, loglik_out,
                                    fbl::Operands{nullptr, nullptr, nullptr}, B, T, S, device, static_cast<hipStream_t>(stream));
+}
+
+// ---- forward-backward in log space on any matrix (forward_backward_log.hpp) ----
+
+// Items per tile of fb_log_dense_step_kernel<TB>: THE tile rule over the step's grid of ceil(S / 64) state blocks per tile,
+// for 8 workgroups a compute unit both ways -- the 8 wave slots of every SIMD: a tile grows only while 8 workgroups' rows
+// still fit the LDS and the launch still has 8 workgroups for every compute unit.  The walk is a chain of exponentials per
+// item that only other waves cover: at 500 x 1440 a tile of 8 (2 workgroups a compute unit) measured 38 % slower than one of
+// 2 at 512 items, and one of 4 lost to single items at 64 (POSTERIOR.md, "Dense log-space route", has every TB).
+static int fb_log_dense_tile(int B, int S, int cus) {
+    return items_per_workgroup(fbd::kMaxTile, B, fbd::padded_states(S) / fbd::kBlockStates, 8 * cus,
+                               [&](int TB) { return 8 * fbd::lds_bytes(TB, S) <= (size_t)fbd::kMaxLdsBytes; });
+}
+
+int torbi_hip_forward_backward_log_covers(int B, int T, int S, int device) {
+    (void)device;
+    if (B < 1 || T < 1 || S < 1 || S > fbd::kMaxStates) return 0;
+    return fb_shape_in_range(B, T, S) ? 1 : 0;
+}
+
+size_t torbi_hip_forward_backward_log_workspace_size(int B, int T, int S) {
+    if (B < 1 || T < 1 || S < 1 || S > fbd::kMaxStates) return 256;
+    return fbd::layout(nullptr, B, S).total;
+}
+
+int torbi_hip_forward_backward_log_tile(int B, int S, int device) {
+    if (B < 1 || S < 1 || S > fbd::kMaxStates) return 0;
+    return fb_log_dense_tile(B, S, cu_count(device));
+}
+
+int torbi_hip_forward_backward_log(const float *observation, const int32_t *batch_frames, const float *transition,
+                                   const float *initial, float *posterior_out, float *loglik_out, void *workspace,
+                                   size_t workspace_bytes, int B, int T, int S, int device, void *stream) {
+    if (B < 0 || T < 1 || S < 1) return TORBI_HIP_EINVAL;
+    if (B == 0) return TORBI_HIP_OK;
+    if (!observation || !batch_frames || !transition || !initial || !posterior_out || !loglik_out || !workspace)
+        return TORBI_HIP_EINVAL;
+    if (!torbi_hip_forward_backward_log_covers(B, T, S, device)) return TORBI_HIP_EINVAL;
+    if (workspace_bytes < torbi_hip_forward_backward_log_workspace_size(B, T, S)) return TORBI_HIP_EWORKSPACE;
+    const fbd::Layout l = fbd::layout(fb_base(workspace), B, S);
+    const DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return (int)guard.err;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int Sp = l.Sp, blocks = Sp / fbd::kBlockStates;
+    int TB = fb_log_dense_tile(B, S, cu_count(device));
+    if (const char *forced = getenv("TORBI_HIP_LOG_DENSE_ITEMS")) {      // (include/torbi_hip.h: the probe's timings per TB)
+        const int g = atoi(forced);
+        if ((g == 1 || g == 2 || g == 4 || g == 8) && fbd::lds_bytes(g, S) <= (size_t)fbd::kMaxLdsBytes) TB = g;
+    }
+    const size_t lds = fbd::lds_bytes(TB, S);
+    const dim3 grid((B + TB - 1) / TB, blocks), block(fbd::kThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(fbd::fb_log_dense_pack_kernel, dim3(blocks, Sp / 4, 2), dim3(256), 0, st, transition, l.P[0], l.P[1], S, Sp);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    // one step of a pass: `v` the backward pass's previous rows (forward: the posterior's own row t - 1)
+    auto step = [&](auto backward, const float *v, int t) {
+        return by_value<8, 4, 2, 1>(TB, [&](auto tb) {
+            auto *kernel = &fbd::fb_log_dense_step_kernel<decltype(tb)::value, decltype(backward)::value>;
+            const hipError_t le = ensure_dynamic_lds(kernel, lds);
+            if (le != hipSuccess) return le;
+            hipLaunchKernelGGL(kernel, grid, block, lds, st, observation, batch_frames, l.P[decltype(backward)::value ? 1 : 0], v,
+                               posterior_out, l.y, t, B, T, S, Sp);
+            return hipGetLastError();
+        });
+    };
+    for (int t = 0; t < T; ++t) {
+        if (t > 0 && (e = step(std::false_type(), nullptr, t)) != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(fbd::fb_log_dense_forward_row_kernel, dim3(B), block, 0, st, observation, batch_frames, initial,
+                           posterior_out, loglik_out, l.Msum, t, T, S);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    const size_t plane = (size_t)B * Sp;                                 // r_t lives in plane t & 1
+    for (int t = T - 1; t >= 0; --t) {
+        if (t < T - 1 && (e = step(std::true_type(), l.r + ((t + 1) & 1) * plane, t)) != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(fbd::fb_log_dense_backward_row_kernel, dim3(B), block, 0, st, observation, batch_frames, loglik_out, l.y,
+                           posterior_out, l.r + (t & 1) * plane, t, T, S, Sp);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    return TORBI_HIP_OK;
 }
 
 // ---- expected counts in log space on a band (counts_log_band.hpp) ----

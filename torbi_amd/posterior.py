@@ -11,7 +11,8 @@ The HIP route is csrc/forward_backward.hpp behind torbi_hip_forward_backward / _
 matrix that holds one value outside a band csrc/forward_backward_band.hpp behind torbi_hip_forward_backward_band (up to 64
 in-band entries) and csrc/forward_backward_wide_band.hpp behind torbi_hip_forward_backward_wide_band (up to 512);
 csrc/forward_backward_log_band.hpp behind torbi_hip_forward_backward_log_band runs the recurrence on logarithms for such a
-band (`arithmetic='log'`), exact where the scaled float32 rows lose states.
+band (`arithmetic='log'`), exact where the scaled float32 rows lose states, and csrc/forward_backward_log.hpp behind
+torbi_hip_forward_backward_log does so for any matrix (`forward_backward_log`, `route='log-dense'`).
 `gpu=None` runs the same scaled recurrence in float64 with torch CPU ops.  POSTERIOR.md has the contract, the kernels and
 the numbers.
 """
@@ -236,6 +237,43 @@ def forward_backward_log_banded(observation: torch.Tensor, batch_frames: Optiona
     return _run_log_band(obs, frames, transition, initial, left, right, background, workspace)
 
 
+def forward_backward_log_workspace_bytes(B: int, T: int, S: int) -> int:
+    """Bytes of device scratch `forward_backward_log` needs for a (B, T, S) problem (both packs of the matrix and three
+    rows per item: it does not depend on T)."""
+    return int(_lib.load().torbi_hip_forward_backward_log_workspace_size(B, T, S))
+
+
+def _run_log_dense(observation, frames, transition, initial, workspace=None):
+    """One call of torbi_hip_forward_backward_log on the device of `observation` (float32, contiguous, log space)."""
+    B, T, S = inputs.check_shapes(observation, frames, transition, initial)
+    return _lib.run('torbi_hip_forward_backward_log', observation, frames, (transition, initial),
+                    _outputs(B, T, S, observation.device), ('torbi_hip_forward_backward_log_workspace_size', (B, T, S)),
+                    (B, T, S), workspace)
+
+
+def forward_backward_log(observation: torch.Tensor, batch_frames: Optional[torch.Tensor], transition: torch.Tensor,
+                         initial: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`forward_backward` computed on logarithms, for ANY matrix (POSTERIOR.md, "Dense log-space route"): exact where the
+    filtered distribution spans more than float32's range and the scaled route loses states -- data the model does not yet
+    explain, left-to-right models with skips, permutation-like matrices -- at S exponentials per state and frame.
+
+    Arguments and outputs are `forward_backward`'s, the non-finite rules `forward_backward_log_banded`'s: a state no path
+    reaches has posterior 0, an item of total probability 0 has log-likelihood -inf and NaN rows, an item that reads a NaN
+    or +inf has NaN for both, and -inf in the matrix is a zero probability.  There is no band to state and no promise.
+    `workspace`: optional uint8 device tensor of >= `forward_backward_log_workspace_bytes(B, T, S)` bytes (then the call
+    allocates nothing but its outputs and can be captured into a graph).
+
+    Raises where the route does not cover the call (torbi_hip_forward_backward_log_covers: up to 4096 states).
+    """
+    B, T, S = _shapes('forward_backward_log', observation, batch_frames, transition, initial)
+    if B > 0 and not _lib.load().torbi_hip_forward_backward_log_covers(B, T, S, 0):
+        raise RuntimeError(f'forward_backward_log does not cover B={B}, T={T}, S={S} (state_posteriors with gpu=None takes '
+                           'any shape)')
+    obs, frames = _moved('forward_backward_log', observation, batch_frames, B, T)
+    return _run_log_dense(obs, frames, transition, initial, workspace)
+
+
+_LOG_DENSE = 'log-dense'                          # `state_posteriors(route=)`: not one of band_route.ROUTES, and never 'auto''s
 ARITHMETICS = ('scaled', 'log')
 _LOG_HOST = 'gpu=None computes any matrix in float64 on the CPU'
 
@@ -325,7 +363,10 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
     route: which device route a given matrix takes.  'auto': the band route where the matrix holds one value outside a
         band that route covers (`posterior_route` answers which), else the dense one; 'dense': always the dense route;
         'band': the band route, raising where the matrix has no covered band.  Both meet the same tolerance against
-        float64; their roundings differ.  Ignored by `gpu=None` and `transition=None`.
+        float64; their roundings differ.  Ignored by `gpu=None` and `transition=None`.  'log-dense': the dense log-space
+        route (`forward_backward_log`) for any matrix of up to 4096 states, exact where the filtered distribution spans
+        more than float32's range and the matrix has no band, and much slower; it never looks at the matrix and ignores
+        `arithmetic`, 'auto' never takes it, and `gpu=None` and `transition=None` raise.
     arithmetic: 'scaled' (the default): the float32 scaled recurrence of every route above.  'log': the log-space band
         route (`forward_backward_log_banded`), exact where the filtered distribution spans more than float32's range --
         mismatched data, left-to-right matrices -- and slower: 'auto' and 'band' take it for any band it covers;
@@ -338,9 +379,22 @@ def state_posteriors(observation: torch.Tensor, batch_frames: Optional[torch.Ten
         t >= batch_frames[b] are 0; an item of total probability 0 has log-likelihood -inf and NaN rows, an item that reads
         a NaN or +inf has NaN for both.
     """
-    band_route.check_route(route)
+    log_dense = route == _LOG_DENSE               # (its own value of `route`: band_route.ROUTES is what 'auto' chooses among)
+    if not log_dense:
+        band_route.check_route(route)
     check_arithmetic(arithmetic)
     B, T, S = inputs.check_shapes(observation, batch_frames, transition, initial)
+    if log_dense:
+        if gpu is None:
+            raise RuntimeError(f'state_posteriors(route={route!r}) needs a HIP device: gpu=None is the float64 route, which '
+                               'takes any matrix')
+        if transition is None:
+            raise RuntimeError(f'state_posteriors(route={route!r}): there is no transition matrix (the closed form of the '
+                               'uniform model is a log-sum-exp per row already)')
+        device = inputs._compute_device(gpu)
+        frames = inputs.frames(batch_frames, B, T, device)
+        transition, _, initial = inputs.model(transition, initial, log_probs, S, device, plain=True)
+        return forward_backward_log(inputs.observation(observation, log_probs, device), frames, transition, initial)
     log_band = arithmetic == 'log' and gpu is not None and transition is not None and B > 0
     if log_band and route == 'dense':
         _log_band_run(route, None, None, B, T, S, 0)                                # (raises before anything runs)
